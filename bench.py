@@ -16,12 +16,21 @@ THE TIMED STATE IS PART OF THE WORKLOAD, NOT OF THE FLAGS.  The lattice is first
 (untimed, always; BASELINE.md §2 "settle") so that the boxes are piled up (~3.3 contacts per body); only then come the
 caller's W warm-up steps and the K timed steps.  The CPU baseline settles its sample with the same 240 steps.  `--warmup`
 therefore no longer changes what is being measured; the line carries `settle_steps`, contacts and contacts per body, and
-the run refuses to time a scene with fewer than 2 contacts per body.  A second figure, `at_rest`, times the same pile after
+the run refuses to time a scene with fewer than 2 contacts per body.  A second figure, `at_rest` (--full), times the same pile after
 1 500 steps in total (everything has come to rest: ~4.7 contacts per body).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = the contact PGS solver,
-k_contact_solve_persist, one launch for all sweeps of a step; algorithmic bytes from SURVEY.md §8(d)) and `cpu_baseline`
-(the REFERENCE's own code, oracle/_ref/libref_fast.so: scalar path and AVX2 path, on the host cores) objects.
+Prints ONE JSON line on rank 0 (contract in the task statement) with a `roofline` object (dominant kernel = the contact PGS solver,
+k_contact_solve_persist, one launch for all sweeps of a step; algorithmic bytes from SURVEY.md §8(d)) taken from the timed steps.
+
+A plain run does only what the headline needs: build the scene, settle, warm up, time the K steps, write the outputs
+(`--dump-outputs DIR`), print the line.  Everything that takes steps or processes of its own comes with `--full`: the
+per-stage and whole-step device times and the event-pair sample (6 extra steps), the timed region again with the rounds-2-4
+event set, `at_rest`, `cpu_baseline` (the REFERENCE's own code, oracle/_ref/libref_fast.so: scalar path and AVX2 path, on the
+host cores) and `--pmc`.
+
+`--dump-outputs DIR`: what the last timed step computed, as a caller of the step receives it — physics poses and velocities of
+every entity (DIR/positions.npy [n, 3], rotations.npy [n, 4], linear_velocity.npy [n, 3], angular_velocity.npy [n, 3], float32;
+N > 1: rank 0's world).  The scene is seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -67,7 +76,34 @@ def parse():
     ap.add_argument("--cpu-grid", type=int, nargs=3, default=[32, 16, 32])
     ap.add_argument("--cpu-steps", type=int, default=20)
     ap.add_argument("--cpu-cores", type=int, default=0, help="reference replicas for the CPU baseline (0 = all usable host cores)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline: stage / whole-step device times, the event-pair and rounds-2-4 samples, "
+                                                         "at_rest, cpu_baseline, --pmc (the --no-* options above apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB)")
+    args = ap.parse_args()
+    if args.pmc and not args.full:
+        ap.error("--pmc is part of the full measurement: add --full")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(world, out_dir):
+    """The arrays a caller of the step receives after it, as float32 .npy files; beyond DUMP_MAX_BYTES a fixed, seeded sample of the
+    entities (their indices in sample_rows.npy, float64)."""
+    pos, rot = world.physics_transforms()
+    lin, ang = world.velocities()
+    arrays = {"positions": pos, "rotations": rot, "linear_velocity": lin, "angular_velocity": ang}
+    n = pos.shape[0]
+    row_bytes = sum(a.shape[1] * 4 for a in arrays.values())
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=DUMP_MAX_BYTES // (row_bytes + 8) - 64, replace=False))   # (64 rows: room for the .npy headers)
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(d / f"{k}.npy", np.ascontiguousarray(a, dtype=np.float64 if k == "sample_rows" else np.float32))
 
 
 # --------------------------------------------------------------------------------------------------------------- CPU baseline
@@ -293,46 +329,50 @@ def main():
     solve_ms = stage_acc["solve"]
     launches = sw.world.solve_launches() * args.steps
     counts = sw.world.counts()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sw.world, args.dump_outputs)      # (before any further step: the state the last timed step left)
 
-    # per-stage breakdown + a dedicated HIP event pair around every solver launch: 3 extra steps outside the timed region
-    prof_launches = 0; prof_ms = 0.0; prof_updates = 0
-    sw.world.set_stage_timing(1)       # every stage
-    stage_prof = {}
-    for _ in range(3):
-        n_l, ms, upd = sw.world.step_profiled(settings, dt)
-        if world_size > 1:
-            sw.exchange()
-        for k, v in sw.world.stage_times().items():
-            stage_prof[k] = stage_prof.get(k, 0.0) + v / 3.0
-        prof_launches += n_l; prof_ms += ms; prof_updates += upd
-    sw.world.set_stage_timing(2)       # the whole step and the solve stage: three more steps for the whole step's device time
-    total_dev_ms = 0.0
-    for _ in range(3):
-        sw.step(settings, dt)
-        total_dev_ms += sw.world.stage_times()["total"] / 3.0
-    total_dev_ms *= args.steps           # (kept as a sum over the timed steps' count: the fields below divide by args.steps)
-    # the same number of steps once more with the events of rounds 2-4 (whole step + solve stage): what the protocol change of round 5 is worth on THIS box, in the line itself
+    total_dev_ms = None
     elapsed_l2 = None
-    if world_size == 1:
-        elapsed_l2, _, acc_l2, _ = timed_region(sw, settings, dt, args.steps, barrier)
-        total_dev_ms_l2 = acc_l2.get("total", 0.0)
-    sw.world.set_stage_timing(TIMED_LEVEL)
-
-    # ---- second state: the same pile at rest (1500 steps in total)
     at_rest = None
-    if not args.no_at_rest and world_size == 1 and args.settle >= SETTLE_STEPS:
-        done = args.settle + args.warmup + args.steps + 6
-        for _ in range(max(0, AT_REST_STEPS - done)):
+    if args.full:
+        # per-stage breakdown + a dedicated HIP event pair around every solver launch: 3 extra steps outside the timed region
+        prof_launches = 0; prof_ms = 0.0; prof_updates = 0
+        sw.world.set_stage_timing(1)       # every stage
+        stage_prof = {}
+        for _ in range(3):
+            n_l, ms, upd = sw.world.step_profiled(settings, dt)
+            if world_size > 1:
+                sw.exchange()
+            for k, v in sw.world.stage_times().items():
+                stage_prof[k] = stage_prof.get(k, 0.0) + v / 3.0
+            prof_launches += n_l; prof_ms += ms; prof_updates += upd
+        sw.world.set_stage_timing(2)       # the whole step and the solve stage: three more steps for the whole step's device time
+        total_dev_ms = 0.0
+        for _ in range(3):
             sw.step(settings, dt)
-        n_rest = min(120, args.steps)
-        e2, sm2, acc2, ci2 = timed_region(sw, settings, dt, n_rest, barrier)
-        c2 = sw.world.counts()
-        at_rest = {"steps_before": max(done, AT_REST_STEPS), "timed_steps": n_rest, "value": n_rest / e2, "unit": "steps/s", "ms_per_step": e2 / n_rest * 1e3,
-                   "contacts": c2["num_contacts"], "manifolds": c2["num_collisions"], "broadphase_overlaps": c2["num_broadphase_overlaps"],
-                   "contacts_per_body": c2["num_contacts"] / max(1, c2["num_rigid_bodies"]),
-                   "solver_avg_launch_us": acc2["solve"] * 1e3 / max(1, sw.world.solve_launches() * n_rest),
-                   "solver_frac_algorithmic": (BYTES_PER_CONTACT_ITER * ci2) / (acc2["solve"] * 1e-3) / 1e9 / HBM_PEAK_GBPS if acc2["solve"] > 0 else None,
-                   "step_frac_algorithmic": step_algorithmic_bytes(c2, args.iterations) / (e2 / n_rest) / 1e9 / HBM_PEAK_GBPS}
+            total_dev_ms += sw.world.stage_times()["total"] / 3.0
+        total_dev_ms *= args.steps           # (kept as a sum over the timed steps' count: the fields below divide by args.steps)
+        # the same number of steps once more with the events of rounds 2-4 (whole step + solve stage): what the protocol change of round 5 is worth on THIS box, in the line itself
+        if world_size == 1:
+            elapsed_l2, _, acc_l2, _ = timed_region(sw, settings, dt, args.steps, barrier)
+            total_dev_ms_l2 = acc_l2.get("total", 0.0)
+        sw.world.set_stage_timing(TIMED_LEVEL)
+
+        # ---- second state: the same pile at rest (1500 steps in total)
+        if not args.no_at_rest and world_size == 1 and args.settle >= SETTLE_STEPS:
+            done = args.settle + args.warmup + args.steps + 6
+            for _ in range(max(0, AT_REST_STEPS - done)):
+                sw.step(settings, dt)
+            n_rest = min(120, args.steps)
+            e2, sm2, acc2, ci2 = timed_region(sw, settings, dt, n_rest, barrier)
+            c2 = sw.world.counts()
+            at_rest = {"steps_before": max(done, AT_REST_STEPS), "timed_steps": n_rest, "value": n_rest / e2, "unit": "steps/s", "ms_per_step": e2 / n_rest * 1e3,
+                       "contacts": c2["num_contacts"], "manifolds": c2["num_collisions"], "broadphase_overlaps": c2["num_broadphase_overlaps"],
+                       "contacts_per_body": c2["num_contacts"] / max(1, c2["num_rigid_bodies"]),
+                       "solver_avg_launch_us": acc2["solve"] * 1e3 / max(1, sw.world.solve_launches() * n_rest),
+                       "solver_frac_algorithmic": (BYTES_PER_CONTACT_ITER * ci2) / (acc2["solve"] * 1e-3) / 1e9 / HBM_PEAK_GBPS if acc2["solve"] > 0 else None,
+                       "step_frac_algorithmic": step_algorithmic_bytes(c2, args.iterations) / (e2 / n_rest) / 1e9 / HBM_PEAK_GBPS}
 
     global_counts = None
     per_rank = None
@@ -343,7 +383,7 @@ def main():
         l_launches = max(sw.world.solve_launches() * args.steps, 1)
         l_solve_s = stage_acc["solve"] * 1e-3 / l_launches
         mine = {
-            "rank": rank, "device": device, "elapsed_s": elapsed, "ms_per_step": elapsed / args.steps * 1e3, "device_ms_per_step": total_dev_ms / args.steps,
+            "rank": rank, "device": device, "elapsed_s": elapsed, "ms_per_step": elapsed / args.steps * 1e3, "device_ms_per_step": total_dev_ms / args.steps if total_dev_ms is not None else None,
             "owned_bodies": ex["owned_bodies"], "ghost_bodies": ex["ghost_bodies"], "local_contacts": lc["num_contacts"], "local_manifolds": lc["num_collisions"], "colors": lc["num_colors"],
             "roofline": {"kernel": sw.world.solver_kernel(), "avg_launch_us": l_solve_s * 1e6,
                          "achieved_GBps": (BYTES_PER_CONTACT_ITER * contact_iters / l_launches) / l_solve_s / 1e9 if l_solve_s > 0 else 0.0,
@@ -381,7 +421,7 @@ def main():
         achieved = alg_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
         traffic, traffic_note = _scaled_traffic(kernel, contact_iters / max(launches, 1))
         traffic_source = "committed constant (profiles/traffic.json) x this run's contact-sweeps" if traffic else None
-        if args.pmc and world_size == 1:
+        if args.pmc and world_size == 1:         # (--pmc comes with --full only)
             m, note = _measured_traffic(kernel, args)
             if m:
                 traffic, traffic_note, traffic_source = m, note, "measured: rocprofv3 --pmc passes of this command, this run"
@@ -411,16 +451,19 @@ def main():
             "avg_launch_us": avg_launch_s * 1e6, "launches_per_step": launches_per_step,
             "algorithmic_bytes_per_launch": alg_per_launch,
             "bound_note": ("the kernel is bound by its dependency chain (colours x sweeps serial hops), not by bytes: DESIGN.md §4"),
-            "event_pair_per_launch": {"avg_launch_us": prof_ms * 1e3 / max(prof_launches, 1), "launches_per_step": prof_launches / 3,
-                                      "achieved_GBps": (BYTES_PER_CONTACT_ITER * prof_updates) / (prof_ms * 1e-3) / 1e9 if prof_ms > 0 else 0.0,
-                                      "note": "3 extra steps (outside the timed region) with a dedicated HIP event pair around each solver launch"},
-            "whole_step": {"algorithmic_bytes": b_step, "ms": total_dev_ms / args.steps, "achieved_GBps": b_step / (total_dev_ms / args.steps * 1e-3) / 1e9,
-                           "frac": b_step / (total_dev_ms / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                           "frac_of_achievable": b_step / (total_dev_ms / args.steps * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBPS,
-                           "note": "B_step of SURVEY.md §8(d) from this step's counts / device time of the whole step (HIP events on the world's stream; mean of three extra steps after the timed region — inside it only the solver launch carries events)"},
             "note": ("rank 0, timed region: 236 B x contacts x sweeps / HIP-event time of the solve stage on the world's stream; "
                      "rocprofv3 --kernel-trace --stats of the same command: profiles/"),
         }
+        if args.full:
+            roofline.update({
+                "event_pair_per_launch": {"avg_launch_us": prof_ms * 1e3 / max(prof_launches, 1), "launches_per_step": prof_launches / 3,
+                                          "achieved_GBps": (BYTES_PER_CONTACT_ITER * prof_updates) / (prof_ms * 1e-3) / 1e9 if prof_ms > 0 else 0.0,
+                                          "note": "3 extra steps (outside the timed region) with a dedicated HIP event pair around each solver launch"},
+                "whole_step": {"algorithmic_bytes": b_step, "ms": total_dev_ms / args.steps, "achieved_GBps": b_step / (total_dev_ms / args.steps * 1e-3) / 1e9,
+                               "frac": b_step / (total_dev_ms / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                               "frac_of_achievable": b_step / (total_dev_ms / args.steps * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBPS,
+                               "note": "B_step of SURVEY.md §8(d) from this step's counts / device time of the whole step (HIP events on the world's stream; mean of three extra steps after the timed region — inside it only the solver launch carries events)"},
+            })
         # N > 1: the whole scene's contacts per body (owner-rule counts summed over the ranks); rank 0's local counts cover its tile + ghost strip
         cpb_timed = (global_counts["contacts"] / max(1, global_counts["bodies"])) if global_counts else counts["num_contacts"] / max(1, counts["num_rigid_bodies"])
         out = {
@@ -438,7 +481,6 @@ def main():
                        "broadphase_overlaps": counts["num_broadphase_overlaps"], "colors": counts["num_colors"],
                        "global_counts": global_counts, "sharding": sharding_note},
             "roofline": roofline,
-            "stage_ms": stage_prof, "stage_ms_note": "per-stage device times of the 3 extra steps after the timed region (stage timing enabled only there)",
             "step_ms_median": float(np.median(step_ms)),
             "step_ms_p95": float(np.percentile(step_ms, 95)) if args.steps >= 50 else None,
             "step_ms_p95_note": None if args.steps >= 50 else f"not reported: {args.steps} timed steps are too few for a 95th percentile (>= 50); step_ms_max is the slowest of them",
@@ -446,14 +488,19 @@ def main():
             "timed_ms_total": elapsed * 1e3,
             "step_modes_timed": {"internal_steps": mode1[0] - mode0[0], "speculative": mode1[1] - mode0[1], "synchronous_reruns": mode1[2] - mode0[2],
                                  "note": "a speculative step sizes its launches from the previous step and reads back once; one whose bounds did not hold is re-run synchronously (counted here, timed like any step)"},
-            "device_ms_per_step": total_dev_ms / args.steps,
-            "device_ms_per_step_note": "mean of a 3-step sample taken AFTER the timed region with whole-step events on (not the timed steps themselves)",
             "timed_region_events": "solver launch only (since r05; rounds 2-4 also bracketed the whole step: two more ~5 us gaps per step)",
-            "with_whole_step_events": ({"value": args.steps / elapsed_l2, "ms_per_step": elapsed_l2 / args.steps * 1e3, "device_ms_per_step": total_dev_ms_l2 / args.steps,
-                                        "note": "the same number of steps timed again right after the 3-step samples, with the rounds-2-4 event set (whole step + solver): compare with `value` for what measuring less is worth"}
-                                       if elapsed_l2 else None),
             "solver_kind": sw.world.solver_kind(),
+            "full": args.full,
         }
+        if args.full:
+            out.update({
+                "stage_ms": stage_prof, "stage_ms_note": "per-stage device times of the 3 extra steps after the timed region (stage timing enabled only there)",
+                "device_ms_per_step": total_dev_ms / args.steps,
+                "device_ms_per_step_note": "mean of a 3-step sample taken AFTER the timed region with whole-step events on (not the timed steps themselves)",
+                "with_whole_step_events": ({"value": args.steps / elapsed_l2, "ms_per_step": elapsed_l2 / args.steps * 1e3, "device_ms_per_step": total_dev_ms_l2 / args.steps,
+                                            "note": "the same number of steps timed again right after the 3-step samples, with the rounds-2-4 event set (whole step + solver): compare with `value` for what measuring less is worth"}
+                                           if elapsed_l2 else None),
+            })
         if per_rank is not None:
             out["per_rank"] = per_rank
             out["per_rank_note"] = ("every rank's own wall clock over the timed steps, its solver launch against the HBM roofline, the device time of one exchange "
@@ -464,7 +511,7 @@ def main():
                                              "rebalanced_every": args.rebalance_every if args.rebalance_every else "never (uniform tiles)"}
         if at_rest is not None:
             out["at_rest"] = at_rest
-        if not args.no_cpu_baseline and world_size == 1:   # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world_size == 1:   # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(args, bodies_per_gpu, args.settle)
         print(json.dumps(out), flush=True)
     if dist is not None:
@@ -495,7 +542,7 @@ def _measured_traffic(kernel, args):
     if not prof:
         return None, "rocprofv3 not found"
     child = [sys.executable, str(Path(__file__).resolve()), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--grid", *map(str, args.grid),
-             "--iterations", str(args.iterations), "--settle", str(args.settle), "--no-cpu-baseline", "--no-at-rest"]
+             "--iterations", str(args.iterations), "--settle", str(args.settle), "--full", "--no-cpu-baseline", "--no-at-rest"]
     vals = {}
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="bench_pmc_", dir="/tmp")

@@ -6,6 +6,7 @@
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 ulimit -c 0
+export OUT=${OUT:-bench_runs}; mkdir -p "$OUT"
 cd oracle && make >/dev/null 2>&1; cd ..
 T0=$(date +%s)
 timeout 1500 python -m pytest tests -q -m gpu --durations=8 > gpurun_out/fin_pytest.log 2>&1; echo "pytest rc=$?" >> gpurun_out/fin_pytest.log
@@ -14,16 +15,16 @@ timeout 600 python -m pytest tests/test_gpu_reference_direct.py -q -m gpu -s 2>&
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
 echo "suite + smoke at $(( $(date +%s) - T0 )) s"
 bash tools/gpu_pmc.sh 2>&1 | tail -4
-timeout 300 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > gpurun_out/fin_bench_driver_flags.json
-timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-at-rest --pmc 2>gpurun_out/fin_pmc_err.log | tail -1 > gpurun_out/fin_bench_pmc.json
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-at-rest"
-MI_PERSIST_RESIDENT=0 timeout 300 $B 2>/dev/null | tail -1 > gpurun_out/fin_bench_no_resident_rows.json
-timeout 300 $B 2>/dev/null | tail -1 > gpurun_out/fin_bench_driver_flags_again.json
+timeout 300 python bench.py --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > "$OUT"/fin_bench_driver_flags.json
+timeout 900 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-at-rest --pmc 2>"$OUT"/fin_pmc_err.log | tail -1 > "$OUT"/fin_bench_pmc.json
+B="python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-at-rest"
+MI_PERSIST_RESIDENT=0 timeout 300 $B 2>/dev/null | tail -1 > "$OUT"/fin_bench_no_resident_rows.json
+timeout 300 $B 2>/dev/null | tail -1 > "$OUT"/fin_bench_driver_flags_again.json
 python - <<'PY'
-import json
+import json, os
 for f in ("bench_default", "fin_bench_driver_flags", "fin_bench_pmc", "fin_bench_no_resident_rows", "fin_bench_driver_flags_again"):
     try:
-        d = json.load(open(f"gpurun_out/{f}.json"))
+        d = json.load(open(os.path.join(os.environ["OUT"], f + ".json")))
         print(f, "value", round(d["value"], 1), "ms", round(d["ms_per_step"], 4), "contacts", d["config"]["contacts"], "frac", round(d["roofline"]["frac"], 3), "bound", d["roofline"]["bound"],
               "launch us", round(d["roofline"]["avg_launch_us"], 1), "hop us", round(d["roofline"]["chain"]["us_per_hop"], 3), "kind", d.get("solver_kind"), "traffic", d["roofline"]["traffic"], d["roofline"].get("traffic_source"),
               "traffic frac", d["roofline"]["traffic_frac"], "step frac", round(d["roofline"]["whole_step"]["frac"], 3), "at_rest", d.get("at_rest", {}).get("value"), "reruns", d["step_modes_timed"]["synchronous_reruns"],
