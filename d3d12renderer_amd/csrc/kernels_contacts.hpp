@@ -193,6 +193,14 @@ __global__ __launch_bounds__(256) void k_schedule_finish(uint32_t lastRound, con
     }
 }
 
+// The colour history after a caller-ordered step (mi_debug_set_solve_order, include/mi_physics.h): every entry of the NEXT step's table — it holds this step's
+// manifolds only, the kept ones entered by k_emit_manifolds with their old colours, the new ones by k_schedule_finish with the order's levels (or 64) — gets
+// the overflow colour, so the next free step colours every manifold afresh.  Keys stay: begin / end events still pair up.
+__global__ __launch_bounds__(256) void k_history_overflow(HistSlot* __restrict__ tab, uint32_t tabMask) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s <= tabMask && tab[s].key != 0ull) tab[s].val = kOverflowColor;
+}
+
 // The constraint rows are written once here and read by the solver from memory: stored non-temporally they do not push the bodies this kernel gathers
 // (one slab of the scene per XCD) out of that XCD's L2: 81 -> 76 us for the stage (A/B against a build with plain stores, same box; -DMI_NO_STREAM_ROWS).
 typedef float mi_vf4 __attribute__((ext_vector_type(4)));

@@ -606,6 +606,9 @@ enqueue_section:
             colorBatch = 8;
         }
         colorRoundsLaunched = round;
+        // a caller-ordered step leaves the overflow colour for every one of its manifolds in the history (its colours were levels of the order, or 64, mixed with
+        // the kept manifolds' old colours: together no valid colouring); the next free step colours them afresh, as the oracle does
+        if (debugOrderPending) L.launch(k_history_overflow, dim3(divUp(tabMask[tabCur ^ 1] + 1u, B)), dim3(B), 0, st, tab[tabCur ^ 1].p, tabMask[tabCur ^ 1]);
         if (seamOn) L.launch(k_seam_stats, dim3(divUp(nmBound, B)), dim3(B), 0, st, sc, colWork.p, color.p, shard.enabled ? shard.active.p : nullptr);
         {   // colour history for the next step, into the OTHER table (it becomes current only if this step turns out valid)
             const int nt = tabCur ^ 1;   // sized and cleared before k_emit_manifolds (narrow phase stage)

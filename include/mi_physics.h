@@ -349,7 +349,11 @@ MI_API int mi_debug_set_solve_order(mi_world* world, const uint32_t* pairs, uint
  *                              so the colour-major dataflow schedule — bins, tiles, version bookkeeping, k_contact_solve_persist's tile code — performs the caller's
  *                              sequence of updates on every body: the caller's sequential result, bit for bit.  Needs an order at most 64 levels deep and no joints;
  *                              otherwise that step uses the one-lane kernel as before.  mi_debug_solve_order_depth: the depth the last such step ran with (0: it did not).
- *                              The reference's per-contact update it must reproduce: src/physics/constraints.cpp:3381-3449, its order 3748-3770. */
+ *                              The reference's per-contact update it must reproduce: src/physics/constraints.cpp:3381-3449, its order 3748-3770.
+ *   the colour history after an ordered step (either kernel): every manifold of that step enters the history with the overflow colour 64 — its key is kept
+ *                              (collision begin / end events pair up as after any step), its colour is not: the next free step colours every manifold afresh
+ *                              (greedy in descending pair priority, as for a world's first step), so the colours it solves in never mix the order's levels with
+ *                              older colours.  mi_world_get_manifold_colors after an ordered step reports the colours that step ran with (levels, or 64). */
 MI_API int mi_debug_set_solve_dataflow(mi_world* world, uint32_t enable);
 MI_API int mi_debug_solve_order_depth(mi_world* world, uint32_t* out_depth);
 

@@ -859,8 +859,11 @@ void World::stepInternal(const mi_step_settings& settings, float dt) {
     solveOrder.reserve(ncontacts);
     if (orderMode == 0) {
         for (uint32_t i = 0; i < ncontacts; ++i) solveOrder.push_back(i);
-    } else if (debugOrderPending) {   // the caller's manifold order (mi_debug_set_solve_order); the colouring still runs: the history stays what the product's is
+    } else if (debugOrderPending) {   // the caller's manifold order (mi_debug_set_solve_order)
         colorManifolds(*this);
+        // the history after an ordered step (include/mi_physics.h): every manifold enters it with the overflow colour, so the next free step colours them all afresh
+        // (the product solved this step in levels of the order or in one lane, not in these colours; its history holds 64 for every manifold of the step as well)
+        for (auto& kv : prevPairColor) kv.second = 64;
         uint32_t nm = (uint32_t)colliderPairs.size();
         std::vector<uint32_t> firstContact(nm);
         { uint32_t off = 0; for (uint32_t m = 0; m < nm; ++m) { firstContact[m] = off; off += contactCounts[m]; } }
@@ -1315,6 +1318,14 @@ MI_API int ora_world_get_mass_properties(World* w, float* invMass, float* invIne
         if (invMass) invMass[i] = im;
         if (invInertia) std::memcpy(invInertia + 9 * i, ii.data(), 36);
         if (cog) { cog[3 * i] = c.x; cog[3 * i + 1] = c.y; cog[3 * i + 2] = c.z; }
+    }
+    return MI_OK;
+}
+MI_API int ora_world_entities_to_bodies(World* w, uint32_t n, const uint32_t* ents, uint32_t* out) {   // (mi_world_entities_to_bodies)
+    if (!w || (n && (!ents || !out))) return MI_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (ents[i] >= w->entities.size() || w->entities[ents[i]].rb < 0) return MI_ERR_INVALID_ARGUMENT;
+        out[i] = (uint32_t)w->entities[ents[i]].rb;
     }
     return MI_OK;
 }

@@ -33,6 +33,52 @@ def two_body_scene(descs, iterations=30, gravity=0.0):
     return scenes.Scene("pair", e, np.arange(n, dtype=np.uint32), c, iterations)
 
 
+def manifold_colors(w):
+    """(oriented collider pairs (n, 2), first contact of each manifold, colour of each manifold) of a world's last step, from its own
+    contact list and its own colour getter (the product and the oracle list both in the order of their contact list)."""
+    con = w.contacts()
+    nm = w.counts()["num_collisions"]
+    colors = np.zeros(nm, np.uint32)
+    import ctypes as C
+    w.L.check(w.L.fn("world_get_manifold_colors")(w.h, colors.ctypes.data_as(C.c_void_p), C.c_uint32(nm)), "world_get_manifold_colors")
+    first = np.r_[True, (con["collider_a"][1:] != con["collider_a"][:-1]) | (con["collider_b"][1:] != con["collider_b"][:-1])] if len(con) else np.zeros(0, bool)
+    assert int(first.sum()) == nm, f"{int(first.sum())} runs of contacts, {nm} manifolds"
+    pairs = np.stack([con["collider_a"][first], con["collider_b"][first]], axis=1).astype(np.uint32)
+    return pairs, con[first], colors
+
+
+def dynamic_bodies(w):
+    """Body indices (as the contact list names them) of the bodies with an inverse mass: the only ones two manifolds of one colour may not share."""
+    im = w.mass_properties()[0]
+    ents = np.nonzero(im != 0.0)[0].astype(np.uint32)
+    return set(int(b) for b in w.entities_to_bodies(ents)) if len(ents) else set()
+
+
+def assert_schedule_valid(w, oracle_world=None, check_overflow=False, tag=""):
+    """The rule k_emit_manifolds trusts the colour history with: no two manifolds of one colour below 64 share a dynamic body (colour 64 = overflow,
+    solved one after the other; `check_overflow` holds it to the rule as well).  With `oracle_world`: every manifold has the oracle's colour too,
+    manifolds matched by their oriented collider pair.  Returns the colours, in the order of the contact list."""
+    pairs, heads, colors = manifold_colors(w)
+    dyn = dynamic_bodies(w)
+    for col in np.unique(colors):
+        if col >= 64 and not check_overflow:
+            continue
+        sel = colors == col
+        bodies = [int(b) for b in np.concatenate([heads["body_a"][sel], heads["body_b"][sel]]) if int(b) in dyn]
+        if len(set(bodies)) != len(bodies):
+            shared = sorted(b for b in set(bodies) if bodies.count(b) > 1)
+            raise AssertionError(f"{tag}colour {col} reuses dynamic bodies {shared[:8]} ({int(sel.sum())} manifolds of that colour)")
+    if oracle_world is not None:
+        opairs, _, ocolors = manifold_colors(oracle_world)
+        mine = {(int(a), int(b)): int(c) for (a, b), c in zip(pairs, colors)}
+        theirs = {(int(a), int(b)): int(c) for (a, b), c in zip(opairs, ocolors)}
+        assert len(mine) == len(pairs) and len(theirs) == len(opairs), f"{tag}a collider pair is listed twice"
+        assert mine.keys() == theirs.keys(), f"{tag}manifolds differ: {sorted(mine.keys() ^ theirs.keys())[:8]}"
+        diff = [(k, mine[k], theirs[k]) for k in sorted(mine) if mine[k] != theirs[k]]
+        assert not diff, f"{tag}{len(diff)} of {len(mine)} manifold colours differ from the oracle's ((pair), product, oracle): {diff[:6]}"
+    return colors
+
+
 def contact_set(contacts):
     """Order-independent, bit-exact representation of a contact list."""
     rows = []
@@ -181,3 +227,56 @@ def replay_reference_order(make_candidate, make_reference, sc, steps, dataflow=F
         assert cand.get_body_states(ids).tobytes() == ref.get_body_states(ids).tobytes(), f"step {i}: body states differ from the reference's"
         most = max(most, cr["num_contacts"])
     return most
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# Caller-ordered steps (mi_debug_set_solve_order) among free ones
+def next_manifolds(sc, oracle_mod, oracle_world):
+    """The oriented collider pairs of the manifolds `oracle_world`'s NEXT step will find, in its list order: a scout oracle world loaded from a
+    checkpoint of it takes that step (the world itself, its event queue included, is left alone)."""
+    scout = sc.populate(oracle_mod.create_world(oracle_mod.ORDER_CANONICAL))
+    scout.load_checkpoint(oracle_world.save_checkpoint())
+    scout.step_fixed(sc.settings(), sc.dt, 1)
+    pairs = manifold_order(scout.contacts())
+    scout.close()
+    return pairs
+
+
+def make_order(pairs, prev_pairs, rng, kind):
+    """A permutation of `pairs`: "random", or "new first" (the manifolds absent from the previous step's list first, each group shuffled)."""
+    pairs = np.asarray(pairs, np.uint32).reshape(-1, 2)
+    if kind == "random":
+        return pairs[rng.permutation(len(pairs))]
+    assert kind == "new first", kind
+    old = {(int(a), int(b)) for a, b in np.asarray(prev_pairs).reshape(-1, 2)}
+    is_new = np.array([(int(a), int(b)) not in old for a, b in pairs], bool)
+    new, kept = pairs[is_new], pairs[~is_new]
+    return np.concatenate([new[rng.permutation(len(new))], kept[rng.permutation(len(kept))]]).reshape(-1, 2)
+
+
+def pair_priority(a, b):
+    """pairPriority(colliderA, colliderB) (oracle/ora_world.cpp, kernels: the order of the greedy colouring), in Python integers."""
+    m52 = (1 << 52) - 1
+    x = (int(a) << 26) | int(b)
+    x ^= x >> 25; x = (x * 0x9E3779B97F4A7) & m52
+    x ^= x >> 27; x = (x * 0xC2B2AE3D27D4F) & m52
+    x ^= x >> 23
+    return x
+
+
+def greedy_colors(pairs, heads, dyn):
+    """Every manifold coloured from nothing: greedy in descending pair priority, the lowest colour below 64 free on both of its dynamic bodies
+    (64 = overflow) — what a free step gives a manifold whose history colour is the overflow colour."""
+    used = {}
+    out = np.full(len(pairs), 64, np.uint32)
+    for m in sorted(range(len(pairs)), key=lambda m: -pair_priority(*pairs[m])):
+        bs = [int(b) for b in (heads["body_a"][m], heads["body_b"][m]) if int(b) in dyn]
+        mask = 0
+        for b in bs:
+            mask |= used.get(b, 0)
+        free = [c for c in range(64) if not (mask >> c) & 1]
+        if free:
+            out[m] = free[0]
+            for b in bs:
+                used[b] = used.get(b, 0) | (1 << free[0])
+    return out

@@ -11,7 +11,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 import make_golden  # noqa: E402
 from d3d12renderer_amd import scenes, capi  # noqa: E402
-from helpers import contact_set, single_body_scene  # noqa: E402
+from helpers import assert_schedule_valid, contact_set, single_body_scene  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 REL_TOL = 1e-4   # north_star tolerance for float state; the assertions below are stricter (bit-exact)
@@ -726,21 +726,8 @@ def test_gpu_full_size_properties(mi_lib):
     nb = sc.num_bodies
     assert p[:nb, 1].min() > 0.0
     assert np.allclose(np.linalg.norm(q, axis=1), 1.0, atol=1e-4)
-    # colouring: no two manifolds of one colour share a dynamic body
-    c = w.contacts()
-    L = w.L
-    import ctypes as C
-    nm = w.counts()["num_collisions"]
-    colors = np.zeros(nm, np.uint32)
-    L.check(L.fn("world_get_manifold_colors")(w.h, colors.ctypes.data_as(C.c_void_p), C.c_uint32(nm)), "colors")
-    first = np.r_[True, (c["collider_a"][1:] != c["collider_a"][:-1]) | (c["collider_b"][1:] != c["collider_b"][:-1])]
-    ba, bb = c["body_a"][first], c["body_b"][first]
-    assert len(ba) == nm
-    for col in np.unique(colors):
-        sel = colors == col
-        bodies = np.concatenate([ba[sel], bb[sel]])
-        bodies = bodies[bodies < nb]
-        assert len(np.unique(bodies)) == len(bodies), f"colour {col} reuses a body"
+    # colouring: no two manifolds of one colour share a dynamic body (the overflow colour included)
+    assert len(assert_schedule_valid(w, check_overflow=True)) == w.counts()["num_collisions"]
 
 
 def test_gpu_body_state_exchange_api(mi_lib):
