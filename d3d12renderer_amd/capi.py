@@ -30,6 +30,12 @@ contact_dtype = np.dtype([
     ("friction_restitution", "<u4"), ("collider_a", "<u4"), ("collider_b", "<u4"),
     ("body_a", "<u4"), ("body_b", "<u4")])
 assert entity_desc.itemsize == 68 and collider_desc.itemsize == 72 and contact_dtype.itemsize == 48
+# mi_ray_hit (mi_world_raycast): entity / collider MI_RAY_MISS on a miss, MI_RAY_TERRAIN for the heightmap
+ray_hit_dtype = np.dtype([("entity", "<u4"), ("collider", "<u4"), ("t", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), ("object_type", "<u4")])
+assert ray_hit_dtype.itemsize == 40
+RAY_MISS, RAY_TERRAIN = 0xFFFFFFFF, 0xFFFFFFFE
+QUERY_RIGID_BODIES, QUERY_STATIC, QUERY_TERRAIN, QUERY_TRIGGERS, QUERY_FORCE_FIELDS = 1, 2, 4, 8, 16
+QUERY_DEFAULT = QUERY_RIGID_BODIES | QUERY_STATIC | QUERY_TERRAIN
 
 distance_constraint = np.dtype([("local_anchor_a", "<f4", 3), ("local_anchor_b", "<f4", 3), ("global_length", "<f4")])
 ball_constraint = np.dtype([("local_anchor_a", "<f4", 3), ("local_anchor_b", "<f4", 3)])
@@ -267,6 +273,31 @@ class World:
         s = np.ascontiguousarray(strengths, dtype=np.float32) if strengths is not None else None
         r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(-1, 2) if entity_ranges is not None else None
         self.L.check(self.L.fn("world_test_interactions")(self.h, C.c_uint32(len(o)), _ptr(o), _ptr(d), _ptr(s), _ptr(r)), "world_test_interactions")
+
+    # --- ray-cast scene queries (closest hit with point and normal; read-only)
+    def _raycast(self, name, origins, directions, max_t, include, entity_ranges):
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        assert len(d) == len(o)
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(max_t, np.float32), (len(o),))) if max_t is not None else None
+        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(o), 2) if entity_ranges is not None else None
+        out = np.zeros(len(o), dtype=ray_hit_dtype)
+        self.L.check(self.L.fn(name)(self.h, C.c_uint32(len(o)), _ptr(o), _ptr(d), _ptr(m), C.c_uint32(include), _ptr(r), _ptr(out)), name)
+        return out
+
+    def raycast(self, origins, directions, max_t=None, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_world_raycast: the first hit of every ray as a `ray_hit_dtype` array (max_t: None = unbounded, a scalar or one per ray)."""
+        return self._raycast("world_raycast", origins, directions, max_t, include, entity_ranges)
+
+    def debug_raycast_exhaustive(self, origins, directions, max_t=None, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_debug_raycast_exhaustive: the same hits from the scan over every collider (byte for byte what raycast returns)."""
+        return self._raycast("debug_raycast_exhaustive", origins, directions, max_t, include, entity_ranges)
+
+    def raycast_device_async(self, n, rays_ptr, out_ptr, include=QUERY_DEFAULT, ranges_ptr=0):
+        """mi_world_raycast_device_async: device buffers (rays: n x 8 float32 = origin, direction, max_t, pad; out: n x 40 bytes),
+        enqueued on the world's stream without a host synchronisation."""
+        self.L.check(self.L.fn("world_raycast_device_async")(self.h, C.c_uint32(n), C.c_void_p(rays_ptr), C.c_uint32(include),
+                                                              C.c_void_p(ranges_ptr or None), C.c_void_p(out_ptr)), "world_raycast_device_async")
 
     def update_constraints(self, ctype, ids, pods):
         """getConstraint(scene, handle) = ... for many constraints of one type."""

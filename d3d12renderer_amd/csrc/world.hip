@@ -31,6 +31,7 @@
 #include "heightmap.hpp"
 #include "cloth.hpp"
 #include "knobs.hpp"
+#include "kernels_query.hpp"
 
 using namespace mi;
 
@@ -391,6 +392,15 @@ struct mi_world {
     std::vector<uint64_t> debugOrder; std::vector<uint32_t> debugRank; bool debugOrderPending = false, debugOrderDataflow = false, debugOrderLevelled = false; uint32_t debugOrderDepth = 0, debugOrderDepthLast = 0;
     int applyDebugOrder();       // all manifolds into the sequential (overflow) colour; their slots in the caller's order
     int orientPairsLikeDebugOrder();   // equal-type pairs listed the other way round are turned (ties on the sweep axis: the reference's orientation follows its endpoint array's history)
+    // ray-cast queries (world_query.inc): anything that moves or changes a collider bumps the pose epoch; the query structure is rebuilt for a new one
+    uint64_t poseEpoch = 0;
+    struct QueryCache {
+        uint64_t builtEpoch = ~0ull; uint32_t nc = 0;
+        DBuf<float4> shape, mn, mx; DBuf<QueryGrid> grid; DBuf<QPartial> partials; DBuf<uint32_t> count, start, entries, large;
+        DeviceScan<uint32_t> scan; Launcher L;
+        DBuf<float> rays; DBuf<uint32_t> ranges, hits;   // staging of the blocking variants
+    } query;
+    int queryBuild();
 };
 
 int mi_world::init(int dev) {
@@ -488,3 +498,4 @@ mi_world::~mi_world() {
 #include "world_capi.inc"   // the C ABI of include/mi_physics.h and include/mi_constraints.h
 #include "world_shard.inc"   // sharded world: include/mi_shard.h (tiles, ghosts, RCCL transport, exact seam, load balance)
 #include "world_state.inc"   // checkpoints, body states on the device, stage dumps, debug entry points
+#include "world_query.inc"   // ray-cast scene queries: include/mi_physics.h mi_world_raycast*

@@ -237,6 +237,7 @@ int mi_world::upload() {
     }
     HIP_TRY(hipStreamSynchronize(stream));
     topologyDirty = false; hostStale = false; haveEstimates = false; gridValid = false;
+    ++poseEpoch;
     if (seamTiling.on && !shard.enabled) { int rc = shardBuildRoots(); if (rc != MI_OK) return rc; }
     if (shard.enabled) {   // the previous step's counts say nothing about the new topology
         int rc = shardBuildRoots(); if (rc != MI_OK) return rc;

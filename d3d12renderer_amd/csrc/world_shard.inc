@@ -554,6 +554,7 @@ MI_API int mi_world_shard_import(mi_world* w, const void* msg) {
     HIP_TRY(w->shard.importBuf.ensure(w->shard.messageFloats()));   // its own staging: a tile without neighbours (1 x 1 grid) has no receive buffer
     HIP_TRY(hipMemcpyAsync(w->shard.importBuf.p, msg, (size_t)(count + 1u) * kShardRecordFloats * sizeof(float), hipMemcpyHostToDevice, w->stream));
     ShardBufs one{}; one.p[0] = w->shard.importBuf.p;
+    ++w->poseEpoch;
     if (count) k_shard_unpack<<<dim3(divUp(count, 256), 1), 256, 0, w->stream>>>(nb, one, w->shard.capacity, w->bPos.p, w->bRot.p, w->bLinVel.p, w->bAngVel.p, w->shard.known.p, ShardCaps{{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}}, nullptr, 0u,
                                                                                    w->shard.blockStamp.p, (uint32_t)w->totalSteps + 1u);
     HIP_TRY(hipStreamSynchronize(w->stream));     // `msg` is the caller's (possibly pageable) memory

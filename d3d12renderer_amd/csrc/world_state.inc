@@ -186,7 +186,7 @@ MI_API int mi_world_load_checkpoint(mi_world* w, const void* data, uint64_t size
         }
         w->clothsDirty = true;
         w->timer = h.timer; w->sapAxis = h.sapAxis; w->eventsEnabled = h.eventsEnabled != 0; w->pendingEvents.clear();
-        w->topologyDirty = true; w->haveEstimates = false; w->scalarsClean = false;
+        w->topologyDirty = true; w->haveEstimates = false; w->scalarsClean = false; ++w->poseEpoch;
         if (w->shard.enabled) {   // the rank's view of that moment (or, from a blob of an unsharded / fully synchronised world: every copy is current)
             mi_world::ShardState& sh = w->shard;
             for (size_t i = 0; i < w->bodies.size(); ++i) w->bodies[i].shardKnown = hasShard ? (known[i] ? 1 : 0) : 1;
@@ -533,7 +533,7 @@ static int statesDevice(mi_world* w, uint32_t n, const uint32_t* idsDev, float* 
     if (!w || (n && (!idsDev || (!outDev && !inDev)))) return fail(MI_ERR_INVALID_ARGUMENT, "null");
     int rc = ensureUploaded(w); if (rc != MI_OK) return rc;
     if (n && outDev) k_gather_states<<<divUp(n, 256), 256, 0, w->stream>>>(n, idsDev, w->bPos.p, w->bRot.p, w->bLinVel.p, w->bAngVel.p, outDev);
-    if (n && inDev) { w->ahead.stale = true;   // (what ran ahead of the next step read the poses this call replaces)
+    if (n && inDev) { w->ahead.stale = true; ++w->poseEpoch;   // (what ran ahead of the next step read the poses this call replaces)
                       k_scatter_states<<<divUp(n, 256), 256, 0, w->stream>>>(n, idsDev, inDev, w->bPos.p, w->bRot.p, w->bLinVel.p, w->bAngVel.p, w->shard.enabled ? w->shard.known.p : nullptr); w->hostStale = true; w->shard.prevValid = false; w->shard.rearmFullSize(); w->pose.valid = false; }   // (pose rows produced before this write are stale)
     if (sync) HIP_TRY(hipStreamSynchronize(w->stream));
     return MI_OK;

@@ -248,6 +248,52 @@ MI_API int mi_entities_apply_forces(mi_world* world, uint32_t count, const uint3
 MI_API int mi_world_test_interactions(mi_world* world, uint32_t count, const float* origins3, const float* directions3,
                                       const float* strengths, const uint32_t* entity_ranges2);
 
+/*
+ * Batched ray-cast scene queries: what does ray i hit first, where, and with what surface normal.  Read-only: the world's state and
+ * every later step are unchanged.  The poses queried are physics_transform1 (those mi_world_test_interactions uses), pending host
+ * edits included; the async variant sees the state at its point in the world's stream.
+ *   - Per collider, t is what the reference's ray::intersect* returns in the entity's frame (the test mi_world_test_interactions
+ *     runs), quirks included: a sphere that contains the origin reports t = 0 (a capsule too, unless its cylinder part answers first);
+ *     a box (AABB / OBB) seen from inside reports no hit; the cylinder test (also the capsule's middle) can answer with a cap
+ *     BEHIND the origin, and such a negative t is no hit (as any negative or non-finite t; mi_world_test_interactions still
+ *     pushes a body whose only candidate is such a cap).  The reference's sphere test assumes a unit direction: here it runs on
+ *     direction / |direction| and its t is rescaled, so t is in the direction's units for every shape.
+ *   - The terrain: the heightmap's collision triangles (two per cell, as heightmap contacts use them; not the bilinear
+ *     mi_heightmap_get_height surface, which they meet at the grid vertices and edges); chunks without heights are holes.
+ *   - Closest hit = smallest t; ties go to the lowest world collider index; a collider wins a tie against the terrain.  A hit
+ *     with t > max_t is a miss; so is a ray with a zero or non-finite direction or origin (never an error).  Cloth is not hit.
+ *   - entity_ranges2 NULL = the whole scene, otherwise ray i sees the colliders of entities [lo_i, hi_i) only (the terrain, entity
+ *     MI_RAY_TERRAIN, only when the range contains that value, i.e. the whole scene).
+ *   - normal: unit, outward: sphere from the centre, capsule from the closest point of its segment, cylinder side or cap, box the
+ *     entering slab's face, hull / terrain the hit triangle's normal; at t = 0 it is -normalize(direction).
+ * A sharded world returns MI_ERR_UNSUPPORTED.  The accelerated structure (a uniform grid over the colliders' world AABBs) is built
+ * on the device by the first query after anything moved, and reused until then.
+ */
+#define MI_RAY_MISS 0xFFFFFFFFu
+#define MI_RAY_TERRAIN 0xFFFFFFFEu
+typedef struct mi_ray_hit {
+    uint32_t entity;      /* MI_RAY_MISS when nothing is hit; MI_RAY_TERRAIN for the heightmap */
+    uint32_t collider;    /* world collider index, as in mi_contact; MI_RAY_MISS / MI_RAY_TERRAIN likewise */
+    float t;              /* hit = origin + t * direction (direction need not be unit length); +inf on a miss */
+    float point[3];       /* world space (0 on a miss) */
+    float normal[3];      /* world space, unit, outward from the surface that was hit (0 on a miss) */
+    uint32_t object_type; /* mi_object_type of the collider; MI_OBJECT_STATIC_COLLIDER for the terrain; 0 on a miss */
+} mi_ray_hit;             /* 40 bytes */
+enum {
+    MI_QUERY_RIGID_BODIES = 1, MI_QUERY_STATIC = 2, MI_QUERY_TERRAIN = 4, MI_QUERY_TRIGGERS = 8, MI_QUERY_FORCE_FIELDS = 16,
+    MI_QUERY_DEFAULT = 7
+};
+/* max_t NULL = +inf; include = MI_QUERY_* flags. */
+MI_API int mi_world_raycast(mi_world* world, uint32_t count, const float* origins3, const float* directions3,
+                            const float* max_t, uint32_t include, const uint32_t* entity_ranges2, mi_ray_hit* out);
+/* Device buffers (e.g. torch tensors' data_ptr()), only enqueued on the world's stream (mi_world_get_stream): no host
+ * synchronisation.  rays8_dev: per ray origin3, direction3, max_t, pad (16-byte aligned); ranges2_dev may be NULL. */
+MI_API int mi_world_raycast_device_async(mi_world* world, uint32_t count, const float* rays8_dev, uint32_t include,
+                                         const uint32_t* ranges2_dev, mi_ray_hit* out_dev);
+/* The same result from the exhaustive scan over every collider and terrain cell (the yardstick of the accelerated path): byte for byte equal. */
+MI_API int mi_debug_raycast_exhaustive(mi_world* world, uint32_t count, const float* origins3, const float* directions3,
+                                       const float* max_t, uint32_t include, const uint32_t* entity_ranges2, mi_ray_hit* out);
+
 /* physicsStep(scene, arena, timer, settings, dt) (src/physics/physics.cpp:1364-1413). */
 MI_API int mi_world_step(mi_world* world, const mi_step_settings* settings, float dt);
 /* n × physicsStepInternal(scene, arena, settings, dt) (src/physics/physics.cpp:1180-1362); no interpolation. */

@@ -10,6 +10,7 @@
 #include <vector>
 #include <functional>
 #include <array>
+#include <cmath>
 #include "mi_physics.h"
 #include "mi_constraints.h"
 #include "mi_shard.h"
@@ -134,6 +135,14 @@ public:
     void applyForce(scene_entity e, vec3 force, vec3 torque) { check(mi_entity_apply_force(w_, e.id, &force.x, &torque.x), "mi_entity_apply_force"); }
     // testPhysicsInteraction(scene, ray, strength) — src/physics/physics.h:404
     void testPhysicsInteraction(ray r, float strength = 1000.f) { check(mi_world_test_interactions(w_, 1, &r.origin.x, &r.direction.x, &strength, nullptr), "mi_world_test_interactions"); }
+    // Closest hit of each ray (mi_world_raycast): entity, collider, t, point, normal; read-only (the scene query the reference's editor lacks).
+    std::vector<mi_ray_hit> raycast(const std::vector<ray>& rays, float maxT = INFINITY, uint32_t include = MI_QUERY_DEFAULT) {
+        std::vector<vec3> o(rays.size()), d(rays.size()); std::vector<float> m(rays.size(), maxT); std::vector<mi_ray_hit> out(rays.size());
+        for (size_t i = 0; i < rays.size(); ++i) { o[i] = rays[i].origin; d[i] = rays[i].direction; }
+        if (!rays.empty()) check(mi_world_raycast(w_, (uint32_t)rays.size(), &o[0].x, &d[0].x, m.data(), include, nullptr, out.data()), "mi_world_raycast");
+        return out;
+    }
+    mi_ray_hit raycast(ray r, float maxT = INFINITY, uint32_t include = MI_QUERY_DEFAULT) { return raycast(std::vector<ray>{r}, maxT, include)[0]; }
 
     // deleteConstraint / deleteAllConstraintsFromEntity / deleteAllConstraints — src/physics/physics.h:251-260
     void deleteConstraint(constraint_handle h) { check(mi_constraint_destroy(w_, h.type, h.id), "mi_constraint_destroy"); }
