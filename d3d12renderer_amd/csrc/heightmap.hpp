@@ -293,10 +293,10 @@ __device__ __forceinline__ void hmCollider(const uint32_t i, const uint32_t lane
         count = active ? (uint32_t)hmPacked[i] : 0u;
         if (!count || (hmSlow[i] != 0) != LARGE || !out.ready()) return;
         first = out.sc->numPairs + (uint32_t)hmScan[i];
-        if (!LARGE && stash && count <= kHmStash && hm.chunksPerDim <= 256u) return;   // every hit of this collider is in the stash: k_hm_write_stashed recomputes just those
+        if (!LARGE && count <= kHmStash && hm.chunksPerDim <= 256u) return;   // every hit of this collider is in the stash: k_hm_write_stashed recomputes just those
     } else if (LARGE) { if (!active || !hmSlow[i]) return; }                            // (the flags are the plain instance's, launched before this one)
     else if (!active) { if (lane == 0) { hmPacked[i] = 0ull; hmSlow[i] = 0; } return; }
-    auto keep = [&](uint32_t j, uint32_t id) { if (!LARGE && stash && j < kHmStash) stash[(size_t)i * kHmStash + j] = id; };
+    auto keep = [&](uint32_t j, uint32_t id) { if (!LARGE && j < kHmStash) stash[(size_t)i * kHmStash + j] = id; };
     const Shape s = loadShape(wShape, i, type);
     const TriShape ts(s);
     const HmVolume vol(hm, xyz(mn), V3(mx.x, mx.y + 10.f, mx.z));
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256) void k_hm_contacts(uint32_t nc, HeightmapParam
         bool mine = k < nc && (hmSlow[k] != 0) == LARGE;
         if (WRITE && mine) {
             const uint32_t count = (uint32_t)hmPacked[k];
-            mine = count && (LARGE || !(stash && count <= kHmStash && hm.chunksPerDim <= 256u));
+            mine = count && (LARGE || !(count <= kHmStash && hm.chunksPerDim <= 256u));
         }
         for (unsigned long long m = __ballot(mine); m; m &= m - 1ull)
             hmCollider<WRITE, LARGE>(base + (uint32_t)__ffsll((long long)m) - 1u, lane, nc, hm, wShape, aabbMin, aabbMax, hmPacked, hmSlow, hmScan, out, hulls, stash);

@@ -202,15 +202,11 @@ __global__ __launch_bounds__(256) void k_history_overflow(HistSlot* __restrict__
 }
 
 // The constraint rows are written once here and read by the solver from memory: stored non-temporally they do not push the bodies this kernel gathers
-// (one slab of the scene per XCD) out of that XCD's L2: 81 -> 76 us for the stage (A/B against a build with plain stores, same box; -DMI_NO_STREAM_ROWS).
+// (one slab of the scene per XCD) out of that XCD's L2: 81 -> 76 us for the stage (A/B against a build with plain stores, same box).
 typedef float mi_vf4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void storeStream(float4* p, float4 v) {
-#ifdef MI_NO_STREAM_ROWS
-    *p = v;
-#else
     mi_vf4 x = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(x, reinterpret_cast<mi_vf4*>(p));
-#endif
 }
 // private joint islands (joints.hpp "PRIVATE islands"): what k_contact_init needs of them
 constexpr uint32_t kIslandMaxContacts = 64;
@@ -544,18 +540,11 @@ __device__ __forceinline__ void solveTileK(uint32_t k, uint32_t tile, uint32_t c
 }
 
 // K12 "Solve collision constraints": one launch per colour, one wave per tile; lanes own disjoint dynamic bodies.
-// Blocks are ordered 4-contact tiles first (longest first).  With `swizzle`, consecutive tiles (= spatially
-// coherent manifolds, hence neighbouring bodies) are dealt to one XCD (block b runs on XCD b % 8) so the body
-// velocity lines of a region stay in that XCD's L2.
-struct ColorLaunch { uint32_t tileStart[4]; uint32_t blockEnd[4]; uint32_t ctStart[4]; uint32_t numBlocks; uint32_t swizzle; };
+// Blocks are ordered 4-contact tiles first (longest first).
+struct ColorLaunch { uint32_t tileStart[4]; uint32_t blockEnd[4]; uint32_t ctStart[4]; uint32_t numBlocks; };
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_contact_solve(ColorLaunch cl, const uint4* __restrict__ slotMeta, const float4* __restrict__ slotNormal,
                                                       const float2* __restrict__ slotMass, const float4* __restrict__ rows, float4* __restrict__ imp, float4* __restrict__ gVel) {
-    uint32_t b = blockIdx.x;
-    if (cl.swizzle) {
-        uint32_t per = (cl.numBlocks + 7u) >> 3;
-        b = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-        if (b >= cl.numBlocks) return;
-    }
+    const uint32_t b = blockIdx.x;
     uint32_t lane = threadIdx.x;
     // blockEnd is cumulative over k = 4, 3, 2, 1
     if (b < cl.blockEnd[0]) { solveTile<4>(cl.tileStart[3] + b, cl.ctStart[3] + b * 4u, lane, slotMeta, slotNormal, slotMass, rows, imp, gVel); return; }

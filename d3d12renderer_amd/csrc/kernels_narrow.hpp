@@ -184,12 +184,10 @@ __global__ __launch_bounds__(256) void k_narrow_clip(uint32_t queueRegion, const
                                                      // workgroup became the kernel's tail in a sharded world (8 192 partial rows: 74 instead of 57 us)
                                                      const Shards* __restrict__ statsShards, StepScalars* statsSc, uint32_t statsNc, uint32_t statsBlocks, const unsigned long long* __restrict__ statsPartials,
                                                      const int* __restrict__ statsBounds, GridParams* statsGridNext, uint32_t statsCellCap, const uint8_t* __restrict__ statsCbLive) {
+    // (workgroup 0, not the last one: dispatched first, it runs beside all the others; as the last one its ~4 us — 12 us over the 8 192 partial rows
+    // of a 2 M-collider sharded scene — started when the kernel was all but over and became its tail)
     if (statsShards && blockIdx.x == 0u) { pairFinishStats(statsShards, statsSc, statsNc, statsBlocks, statsPartials, statsBounds, statsGridNext, statsCellCap, statsCbLive); return; }
-#ifdef MI_CLIP_PINGPONG
-    __shared__ float4 polyMem[2 * kLdsPolyVerts * kLdsPolyStride];   // 64 KiB: two clip polygons per lane, [vertex][lane]
-#else
     __shared__ float4 polyMem[kLdsPolyVerts * kLdsPolyStride];       // 32 KiB: ONE clip polygon per lane, [vertex][lane], clipped in place (narrow.hpp clipPolygonLds)
-#endif
     const uint32_t t = (blockIdx.x - (statsShards ? 1u : 0u)) * blockDim.x + threadIdx.x;
     const uint32_t q = t / queueRegion, idx = t % queueRegion;       // queueRegion is a multiple of 256: a workgroup never straddles queues
     if (q >= kBoxQueues || idx >= queueShards->c[q].boxHits) return;
@@ -202,13 +200,8 @@ __global__ __launch_bounds__(256) void k_narrow_clip(uint32_t queueRegion, const
     boxPairShapes(wShape, a, b, ta, arot, acen, arad, brot, bcen, brad);
     ObbSat res; res.normal = V3(h.nx, h.ny, h.nz); res.faceHit = (h.flags & 1u) != 0u; res.bFace = (h.flags & 2u) != 0u;
     Manifold m; m.count = 0;
-#ifdef MI_CLIP_PINGPONG
-    LdsPoly polyA{polyMem + threadIdx.x, 0u}, polyB{polyMem + kLdsPolyVerts * kLdsPolyStride + threadIdx.x, 0u};
-    bool hit = obbContacts(arot, acen, arad, brot, bcen, brad, res, polyA, polyB, m);
-#else
     LdsPoly poly{polyMem + threadIdx.x, 0u};
     bool hit = obbContactsLds(arot, acen, arad, brot, bcen, brad, res, poly, m);
-#endif
     writeManifold(h.pair, hit, m, npPacked, npNormal, npPoints);
 }
 
@@ -346,16 +339,11 @@ __global__ __launch_bounds__(256) void k_emit_manifolds(uint32_t nc, uint32_t nb
                                                         unsigned long long* __restrict__ bodyUsed, uint8_t* __restrict__ isNew, StepScalars* sc,
                                                         float2 terrainMaterial /* (restitution, friction) of the heightmap */,
                                                         HistSlot* __restrict__ nextTab, uint32_t nextMask, uint8_t* __restrict__ manKept, const uint32_t* __restrict__ prevHint, uint32_t* __restrict__ nextHint /* the tables' probe hints (tableFind; one array while the tables keep their size) */,
-                                                        const Shards* __restrict__ statsShards /* non-null: workgroup 0 runs pairFinishStats instead */, uint32_t statsBlocks,
-                                                        const unsigned long long* __restrict__ statsPartials, const int* __restrict__ statsBounds, GridParams* statsGridNext, uint32_t statsCellCap, const uint8_t* __restrict__ statsCbLive,
                                                         const uint32_t* __restrict__ seamId /* exact seam: per body, the tile border it is shared across (0 = none); or null */,
                                                         unsigned long long* __restrict__ topRound1 /* non-null: colouring round 0 happens right here — an uncoloured manifold proposes itself on its bodies
                                                                                                        for round 1 (k_color_round's "lost" branch at round 0: every uncoloured manifold loses round 0) */,
                                                         uint32_t* __restrict__ roundFlags) {
-    // (workgroup 0, not the last one: dispatched first, it runs beside all the others; as the last one its ~4 us — 12 us over the 8 192 partial rows
-    // of a 2 M-collider sharded scene — started when the kernel was all but over and became its tail)
-    if (statsShards && blockIdx.x == 0u) { pairFinishStats(statsShards, sc, nc, statsBlocks, statsPartials, statsBounds, statsGridNext, statsCellCap, statsCbLive); return; }
-    uint32_t p = (blockIdx.x - (statsShards ? 1u : 0u)) * blockDim.x + threadIdx.x;
+    uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t numPairs = sc->numPairs;
     if (p >= numPairs) return;
     const uint64_t* __restrict__ pairKeys = sc->partitioned ? pairsB : pairsA;

@@ -214,11 +214,7 @@ __device__ __forceinline__ void processTile(uint32_t ctBase, uint32_t lane, uint
     const uint32_t bA = meta.x, bB = meta.y, pk = meta.z;
     const float imA = mass.x, imB = mass.y;
     const bool valid = meta.w != 0u;
-#ifdef MI_DBG_ALLLOCAL
-    const bool locA = XCD, locB = XCD;
-#else
     const bool locA = XCD && (meta.w & 0x100u) != 0u, locB = XCD && (meta.w & 0x200u) != 0u;
-#endif
     const bool live = valid && (imA != 0.f || imB != 0.f);
     const uint32_t degA = (pk >> 7) & 127u, degB = (pk >> 21) & 127u;
     const uint32_t expA = it * degA + (pk & 127u), expB = it * degB + ((pk >> 14) & 127u);
@@ -428,10 +424,10 @@ template <int NPOS> __device__ __forceinline__ void accCopyResident(uint32_t q, 
 // IMPLDS = false (piles beyond ~1.2 M manifolds): nothing per slot but a 20-byte descriptor stays in LDS; the accumulated
 // impulses travel as tagged granules in `imp` exactly as in k_contact_solve_flow (no size limit left).
 #define MI_PERSIST_PARAMS uint32_t sweeps, uint32_t maxSlots, const uint2* __restrict__ tileDesc, const uint4* slotMeta, const float4* __restrict__ slotNormal, \
-    const float2* __restrict__ slotMass, const float4* __restrict__ rows, float4* gVel, StepScalars* sc, uint32_t xcdOnly, \
+    const float2* __restrict__ slotMass, const float4* __restrict__ rows, float4* gVel, StepScalars* sc, \
     const uint32_t* __restrict__ xcdTiles, uint32_t listCap, const unsigned long long* __restrict__ bodyOwner, float4* gVelL, uint4* slotMetaW, float4* imp, uint32_t xcdFault, \
     uint32_t resident /* 1: rows of the first tiles stay in a0..a143 (and v208..v255) */
-#define MI_PERSIST_PASS sweeps, maxSlots, tileDesc, slotMeta, slotNormal, slotMass, rows, gVel, sc, xcdOnly, xcdTiles, listCap, bodyOwner, gVelL, slotMetaW, imp, xcdFault, resident
+#define MI_PERSIST_PASS sweeps, maxSlots, tileDesc, slotMeta, slotNormal, slotMass, rows, gVel, sc, xcdTiles, listCap, bodyOwner, gVelL, slotMetaW, imp, xcdFault, resident
 template <bool METALDS, bool XCD, bool IMPLDS>
 __device__ __forceinline__ void persistSolveBody(MI_PERSIST_PARAMS) {
     // LDS per workgroup: [maxSlots] x { meta uint4[64], normal float4[64], mass float2[64] } (constant over the sweeps; METALDS only), then the
@@ -443,11 +439,10 @@ __device__ __forceinline__ void persistSolveBody(MI_PERSIST_PARAMS) {
     float2* lMass = reinterpret_cast<float2*>(lNormal + metaSlots * 64u);
     float2* lImp = lMass + metaSlots * 64u;
     uint32_t* lDesc = reinterpret_cast<uint32_t*>(lImp + (IMPLDS ? (size_t)maxSlots * 4u * 64u : 0));   // [maxSlots][3]
-    if (xcdOnly && (blockIdx.x & 7u) != 0u) return;   // development experiment: only the workgroups of one XCD work
     const uint32_t lane = threadIdx.x;
     const uint32_t xcd = blockIdx.x & 7u;
     const bool isVoid = stepIsVoid(sc);   // (a speculative step already known to be void: no tiles, the workgroup leaves — kernels_common.hpp; loaded beside the tile counts, no round trip of its own)
-    uint32_t numTiles = isVoid ? 0u : sc->totalTiles, numWaves = xcdOnly ? gridDim.x / 8u : gridDim.x, wid = xcdOnly ? blockIdx.x / 8u : blockIdx.x;
+    uint32_t numTiles = isVoid ? 0u : sc->totalTiles, numWaves = gridDim.x, wid = blockIdx.x;
     if (XCD) {
         uint32_t hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(hw));

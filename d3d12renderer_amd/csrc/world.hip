@@ -51,7 +51,7 @@ template <typename T>
 struct DBuf {
     T* p = nullptr;
     size_t cap = 0;
-    unsigned flags = 0;   // hipExtMallocWithFlags flags (0 = plain hipMalloc); development experiments only
+    unsigned flags = 0;   // hipExtMallocWithFlags flags (0 = plain hipMalloc)
     ~DBuf() { if (p) (void)hipFree(p); }
     hipError_t ensure(size_t n, bool keep = false, hipStream_t st = nullptr) {
         if (n <= cap) return hipSuccess;
@@ -325,19 +325,21 @@ struct mi_world {
 #if defined(MI_DBG_KNOCKOUT) || defined(MI_DBG_TIMELINE)
     bool knockPending = false, knockPendingEmit = false, knockPendingBp = false; double knockMsSum = 0.0; uint32_t knockLaunches = 0; unsigned long long* dbgTimelineBuf = nullptr;   // development builds only (world_step.inc)
 #endif
-    bool persistSolver = true, persistMetaLds = true, persistImpLds = true, usedPersist = false; uint32_t xcdOnly = 0; uint32_t persistWaves = 1024;   // one resident workgroup per SIMD owns its tiles through all sweeps (k_contact_solve_persist)
-    uint32_t flowLds = 0;                  // dynamic LDS bytes per 64-lane workgroup: caps resident waves per CU (160 KiB / flowLds)
+    bool persistSolver = true, persistMetaLds = true, persistImpLds = true, usedPersist = false; uint32_t persistWaves = 1024;   // one resident workgroup per SIMD owns its tiles through all sweeps (k_contact_solve_persist)
     uint32_t flowFallbacks = 0;
     uint32_t launchFallbackSteps = 0;     // > 0: the dispatch-ordered dataflow kernel ran out of spin budget (shared device?) -> per-colour launches for this many steps
     bool flowFaultTest = false, flowFaultFired = false;   // MI_FLOW_FAULT: tests inject one such failure
     bool flowSolver = true;               // dataflow PGS sweep (one launch per iteration); MI_SOLVER=launch selects one launch per colour
     BinInfo bins[kSchedBins]{};           // host copy of the last step's schedule
     uint32_t totalTiles = 0;
-    bool xcdSwizzle = false;
 
     StepScalars hs{};            // host copy of the last step's scalars
     struct Readback { StepScalars sc; uint32_t flags[96]; uint32_t seq; uint32_t pad[3]; };   // seq: written last by k_publish_readback (the host spins on it)
-    uint32_t readbackSeq = 0; bool spinReadback = true, stageEvents = false /* time every stage */, stepEvents = false /* time the whole step and the solve stage */, solveEventsOnly = false /* ... the solve stage alone */, timesPendingEnds = true;
+    uint32_t readbackSeq = 0; bool spinReadback = true;
+    // stage timing (mi_world_set_stage_timing): 0 nothing, 1 every stage, 2 the whole step and the solve stage, 3 the solve stage alone
+    uint32_t timingLevel = 0;
+    static bool timesStages(uint32_t level) { return level == 1u; }              // events at every stage boundary
+    static bool timesEnds(uint32_t level) { return level == 1u || level == 2u; }  // the step's own start / stop events
     Readback* hsPinned = nullptr; // pinned staging for the end-of-step read-back (one async copy, no pageable bounce)
     mi_stage_times timesSum{}; uint32_t timesSteps = 0; uint64_t contactUpdatesSum = 0;   // accumulated since the last mi_world_get_accumulated_stage_times(reset)
     mi_step_counts counts{};
@@ -345,7 +347,7 @@ struct mi_world {
     // two sets of step events, alternating per valid step: the elapsed times of step k are read at the START of step k + 1, after its first launches are
     // enqueued (three hipEventElapsedTime calls cost the host ~10 us it would otherwise spend with the device idle between two steps), or by whoever asks first
     hipEvent_t evSets[2][10]{}; hipEvent_t* ev = evSets[0]; int evSet = 0;
-    bool timesPending = false; int timesPendingSet = 0; bool timesPendingStages = false; uint64_t timesPendingUpdates = 0;
+    bool timesPending = false; int timesPendingSet = 0; uint32_t timesPendingLevel = 0; uint64_t timesPendingUpdates = 0;   // timesPendingLevel: the level the step ran with (the caller may change it before finishTimes)
     void finishTimes();
     uint32_t numColorsUsed = 0, solveLaunches = 0;
     bool profileSolve = false;            // per-launch HIP events around k_contact_solve (mi_world_step_profiled)
@@ -370,7 +372,7 @@ struct mi_world {
     struct StepGraph { uint64_t sig = 0; hipGraphExec_t exec = nullptr; uint64_t lastUse = 0; };
     std::vector<StepGraph> stepGraphs;   // at most kMaxStepGraphs; when full, ALL are dropped with the stream idle (never one next to live ones)
     static constexpr size_t kMaxStepGraphs = 64;
-    bool graphsEnabled = true, graphsForAll = false, graphNoEvents = false, graphNoCapture = false; uint32_t graphMaxColliders = 32768;
+    bool graphsEnabled = true, graphsForAll = false;
     uint64_t graphLastSig = 0, graphPrevSig = 0, graphUseClock = 0;   // signatures of the last two steps (the buffer sets alternate: a steady scene repeats with period 2)
     uint32_t graphHits = 0, graphCaptures = 0, graphPlain = 0; bool graphDebug = false;
     std::vector<uint64_t> graphPrevOps, graphPrevOps2;
@@ -434,36 +436,25 @@ int mi_world::init(int dev) {
     if (kn.graph == "0") graphsEnabled = false;   // never replay steps as HIP graphs
     if (kn.graph == "force") graphsEnabled = true;
     graphsForAll = kn.graph == "all";             // also the large scenes
-    graphMaxColliders = kn.graphMaxColliders; graphDebug = kn.graphDebug; graphNoEvents = kn.graphNoEvents; graphNoCapture = kn.graphNoCapture;
+    graphDebug = kn.graphDebug;
     pose.enabled = kn.poseStream;
     spinReadback = spinReadback && kn.spinReadback;
-    stageEvents = kn.stageEvents; stepEvents = kn.stepEvents;   // default: nothing is timed (mi_world_set_stage_timing)
-    xcdSwizzle = kn.xcdSwizzle;
     const std::string& sv = kn.solver;
     flowSolver = sv != "launch";
     specEnabled = kn.speculative;
-    if (kn.flowLds) flowLds = kn.flowLds;
-    // The solver-side body velocities (and the impulse granules) are exchanged between workgroups through 16-byte sc1
-    // transactions: memory the L2 never caches (MTYPE_UC) serves them measurably faster than default device memory
-    // (solve 0.86 -> 0.79 ms at 262144 bodies).  MI_GVEL_ALLOC / MI_IMP_ALLOC = plain | finegrained | uncached override.
-    auto allocFlags = [](const std::string& v, unsigned dflt) {
-        if (v.empty()) return dflt;
-        return v == "finegrained" ? (unsigned)hipDeviceMallocFinegrained : v == "uncached" ? (unsigned)hipDeviceMallocUncached : 0u;
-    };
-    gVel.flags = allocFlags(kn.gvelAlloc, hipDeviceMallocUncached);
-    imp.flags = allocFlags(kn.impAlloc, 0u);
+    // The solver-side body velocities are exchanged between workgroups through 16-byte sc1 transactions: memory the L2 never
+    // caches (MTYPE_UC) serves them measurably faster than default device memory (solve 0.86 -> 0.79 ms at 262144 bodies).
+    gVel.flags = hipDeviceMallocUncached;
     persistSolver = sv.empty() || sv == "persist" || sv == "persist-global" || sv == "persist-granules" || sv == "blocks";   // default; MI_SOLVER=flow / launch select the other contact solvers
     persistImpLds = sv != "persist-granules";   // persist-granules: impulses as tagged granules as well (what the largest piles get automatically)
     persistMetaLds = sv != "persist-global" && sv != "persist-granules";   // persist-global: slot data always from global memory (the variant larger problems get automatically)
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) persistWaves = 4u * (uint32_t)prop.multiProcessorCount; }
     if (kn.persistWaves) persistWaves = kn.persistWaves;
-    xcdOnly = kn.persistXcdOnly ? 1u : 0u;                                   // development experiment: one XCD's workgroups do all the work
     if (kn.persistXcd >= 0) persistXcd = kn.persistXcd != 0;                 // 0: no XCD partitioning (every body through memory)
     if (kn.islandPrivate >= 0) privateIslandsEnabled = kn.islandPrivate != 0;   // development / tests: every island through the dataflow
     if (kn.persistXcdSingle >= 0) persistXcdSingle = kn.persistXcdSingle != 0;   // 0: small piles on all XCDs, every body through memory
     xcdFaultTest = kn.xcdFault; flowFaultTest = kn.flowFault;
     if (kn.xcdMinManifolds >= 0) xcdMinManifolds = (uint32_t)kn.xcdMinManifolds;   // smallest manifold count that is partitioned (tests: 1)
-    if (flowLds > 65536) (void)hipFuncSetAttribute((const void*)k_contact_solve_flow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flowLds);
     return MI_OK;
 }
 mi_world::~mi_world() {

@@ -168,8 +168,7 @@ int JointSet::upload(mi_world& w, hipStream_t st) {
     hinge.computeOrder(invMass); cone.computeOrder(invMass); slider.computeOrder(invMass);
     {
         std::vector<IslandDesc> islands; std::vector<IslandStep> steps; std::vector<uint32_t> islandBodies;
-        const bool useIslands = w.knobs.jointIslands;
-        if (useIslands) buildIslands(invMass, islands, steps, islandBodies);
+        buildIslands(invMass, islands, steps, islandBodies);
         releaseIslands();
         if (!islands.empty()) {
             HIP_TRY(hipMalloc((void**)&dIslands, islands.size() * sizeof(IslandDesc)));

@@ -231,8 +231,7 @@ int mi_world::upload() {
     int rc = joints.upload(*this, stream);
     if (rc != MI_OK) return rc;
     if (heightmap) {
-        HIP_TRY(hmPacked.ensure(nc + 1)); HIP_TRY(hmScan.ensure(nc + 1)); HIP_TRY(hmSlow.ensure(nc + 1));
-        if (knobs.hmStash) HIP_TRY(hmStash.ensure((size_t)(nc + 1) * kHmStash));
+        HIP_TRY(hmPacked.ensure(nc + 1)); HIP_TRY(hmScan.ensure(nc + 1)); HIP_TRY(hmSlow.ensure(nc + 1)); HIP_TRY(hmStash.ensure((size_t)(nc + 1) * kHmStash));
         rc = uploadHeightmap(); if (rc != MI_OK) return rc;
     }
     HIP_TRY(hipStreamSynchronize(stream));

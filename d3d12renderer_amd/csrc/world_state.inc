@@ -477,7 +477,7 @@ MI_API int mi_debug_tile_owner(uint32_t tile_in_bin, uint32_t tiles_in_bin, uint
 // accumulated step and contact-update counts still count every valid step); level 2 = the whole step and the solve stage, level 3 = the solve stage alone, level 1 = every stage.
 MI_API int mi_world_set_stage_timing(mi_world* w, uint32_t level) {
     if (!w || level > 3u) return fail(MI_ERR_INVALID_ARGUMENT, "level: 0 off, 1 every stage, 2 the whole step and the solve stage, 3 the solve stage alone");
-    w->stageEvents = level == 1u; w->stepEvents = level == 2u || level == 3u; w->solveEventsOnly = level == 3u; return MI_OK;
+    w->timingLevel = level; return MI_OK;
 }
 MI_API int mi_world_get_stage_times(mi_world* w, mi_stage_times* out) { if (!w || !out) return fail(MI_ERR_INVALID_ARGUMENT, "null"); w->finishTimes(); *out = w->times; return MI_OK; }
 

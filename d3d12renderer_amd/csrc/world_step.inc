@@ -219,17 +219,14 @@ int mi_world::runStep(const mi_step_settings& settings, float dt, bool spec) {
     bool attached = !debugSync;   // (set per pass below: a graph cannot hold the attached form, it gets recorded events)
     // Timing is opt-in (mi_world_set_stage_timing): even ATTACHED events are not free — the start / stop events riding on the solver's dispatch cost ~11 us of idle
     // device per step (the kernels before / after wait for the signals), the step's two ~1.5 us: 12 us of a 1.0 ms step for numbers nobody asked for.
-    const int stepEventsMode = stepEvents || stageEvents ? 2 : 0;   // (0 none; 2 step + solve stage)
-    const bool timeStepEnds = (stepEventsMode == 2 || stageEvents) && !(solveEventsOnly && !stageEvents);   // level 3: the solve stage alone (the step's own start / stop events cost two more gaps)
     auto mark = [&]() {
         const int id = evi++;
         if (debugSync && !L.dry) { std::fprintf(stderr, "[mi_physics] step %llu: waiting for the stage ending at mark %d\n", (unsigned long long)totalSteps, id); std::fflush(stderr);   // (a memory fault ends the process inside the wait: the last line names the stage)
             hipError_t e = hipStreamSynchronize(st); if (e != hipSuccess) std::fprintf(stderr, "[mi_physics] step %llu (%s): stage ending at mark %d: %s\n", (unsigned long long)totalSteps, spec ? "speculative" : "synchronous", id, hipGetErrorString(e)); }
-        if (!stageEvents && (stepEventsMode == 0 || (stepEventsMode == 1 && (id == 0 || id == 8)))) return;
+        if (!timingLevel) return;
         if (attached && (id == 0 || id == 6 || id == 7 || id == 8)) return;
-        if (!timeStepEnds && (id == 0 || id == 8)) return;
-        if (!stageEvents && id != 0 && id != 6 && id != 7 && id != 8) return;   // level 2: only the step and the solve stage
-        if (L.hashing && !stageEvents && graphNoEvents) return;
+        if (!timesEnds(timingLevel) && (id == 0 || id == 8)) return;   // level 3: the solve stage alone (the step's own start / stop events cost two more gaps)
+        if (!timesStages(timingLevel) && id != 0 && id != 6 && id != 7 && id != 8) return;   // levels 2 and 3: no stage boundaries
         L.eventRecord(ev[id], st);
     };
     auto bound = [](uint32_t last, uint32_t slack) { return last + last / 8u + slack; };
@@ -238,8 +235,9 @@ int mi_world::runStep(const mi_step_settings& settings, float dt, bool spec) {
     // Passes over the enqueue section below (launcher.hpp): a speculative step of a small scene first runs it DRY (signature only); a known
     // signature is replayed from its captured graph, one seen in the previous step as well is captured now, anything else runs plainly.
     const bool debugSyncG = debugSync;
+    constexpr uint32_t kGraphMaxColliders = 32768;   // larger scenes are not launch-bound (MI_GRAPH=all replays them too)
     const bool graphStep = spec && graphsEnabled && !profileSolve && !xcdFaultTest && !flowFaultTest && !debugSyncG && !launchFallbackSteps &&
-                           (graphsForAll || nc <= graphMaxColliders) && readbackSeqDev.p;
+                           (graphsForAll || nc <= kGraphMaxColliders) && readbackSeqDev.p;
     enum { PASS_PLAIN, PASS_DRY, PASS_CAPTURE };
     int pass = graphStep ? PASS_DRY : PASS_PLAIN;
     // k_reset_scalars' work rides at the end of k_publish_readback (`scalarsClean`: the previous attempt's publish has done it): the step then starts with k_bp_prepare, whose 27 us
@@ -253,7 +251,7 @@ int mi_world::runStep(const mi_step_settings& settings, float dt, bool spec) {
     // kernel on exactly those inputs; otherwise what it counted is cleared (cell histogram here, the scalars / counter shards by k_reset_scalars) and the step starts as usual.
     const bool aheadFits = ahead.pending && !ahead.stale && spec && pass == PASS_PLAIN && skipReset && !shard.enabled && nc && gridValid && knobs.fuseWorld && !heightmap && !usesInteractions &&
                            ahead.nc == nc && ahead.nb == nb && ahead.gridIdx == gridCur && ahead.axis == sapAxis && ahead.pos == bPos.p && ahead.rot == bRot.p && ahead.shape == cShape.p &&
-                           !timeStepEnds && !stageEvents && !debugSync && !debugOrderPending;
+                           !timesEnds(timingLevel) && !debugSync && !debugOrderPending;
     if (ahead.pending && !aheadFits) {
         skipReset = false;
         if (cellCount.p) HIP_TRY(hipMemsetAsync(cellCount.p, 0, cellCount.cap * sizeof(uint32_t), st));   // (16 MB; this path is rare: an outside write, a void step, another step mode)
@@ -268,7 +266,7 @@ enqueue_section:
     attached = !debugSync && pass == PASS_PLAIN;
     mark();  // 0
     if (skipReset) {}   // (the step's start event rides on k_bp_prepare below)
-    else if (attached && timeStepEnds) hipExtLaunchKernelGGL(k_reset_scalars, dim3(1), dim3(128), 0, st, ev[0], nullptr, 0, sc, shards.p, roundFlagsPtr(), keyCount.p);
+    else if (attached && timesEnds(timingLevel)) hipExtLaunchKernelGGL(k_reset_scalars, dim3(1), dim3(128), 0, st, ev[0], nullptr, 0, sc, shards.p, roundFlagsPtr(), keyCount.p);
     else L.launch(k_reset_scalars, dim3(1), dim3(128), 0, st, sc, shards.p, roundFlagsPtr(), keyCount.p);
     // sharded world: the per-body / per-collider passes run a fixed number of workgroups that stride over the blocks of 256 and skip those with nothing simulated in them
     const bool blockSkip = shard.enabled && nb && knobs.shardBlockSkip;
@@ -314,8 +312,8 @@ enqueue_section:
                      nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPos.p, bRot.p, hullAabb.p, wShape.p, aabbMin.p, aabbMax.p, sapAxis, shard.enabled ? shard.axisDev.p : nullptr, \
                      blockSkip ? cbRange.p : nullptr, blockSkip ? shard.blockLive.p : nullptr, blockSkip ? shard.cbLive.p : nullptr
             if (useAhead) {}   // (the previous step ran it: step-ahead)
-            else if (skipReset && attached && timeStepEnds && !blockSkip) hipExtLaunchKernelGGL(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, ev[0], nullptr, 0, MI_PREPARE_ARGS);   // first kernel of the step: it carries the start event
-            else if (skipReset && attached && timeStepEnds) hipExtLaunchKernelGGL(k_bp_prepare<true>, dim3(bodyGrid(divUp(nc, 256))), dim3(256), 0, st, ev[0], nullptr, 0, MI_PREPARE_ARGS);   // (sharded: k_shard_classify before it is not in the step's time)
+            else if (skipReset && attached && timesEnds(timingLevel) && !blockSkip) hipExtLaunchKernelGGL(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, ev[0], nullptr, 0, MI_PREPARE_ARGS);   // first kernel of the step: it carries the start event
+            else if (skipReset && attached && timesEnds(timingLevel)) hipExtLaunchKernelGGL(k_bp_prepare<true>, dim3(bodyGrid(divUp(nc, 256))), dim3(256), 0, st, ev[0], nullptr, 0, MI_PREPARE_ARGS);   // (sharded: k_shard_classify before it is not in the step's time)
             else if (blockSkip) L.launch(k_bp_prepare<true>, dim3(bodyGrid(divUp(nc, 256))), dim3(256), 0, st, MI_PREPARE_ARGS);
             else L.launch(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, MI_PREPARE_ARGS);
 #undef MI_PREPARE_ARGS
@@ -342,12 +340,12 @@ enqueue_section:
     const bool round0InEmit = knobs.round0InEmit && !debugOrderPending;   // colouring round 0 inside k_emit_manifolds (the caller's order re-colours everything by itself)
     // XCD partitioning pays once the pile is big enough to keep eight L2s busy; it needs the persistent kernel (no joints)
     const bool exactSeamStep = shard.enabled && shard.exact;   // every sweep ends in an exchange with the neighbours: one launch per sweep (the generic dataflow path), nothing persistent
-    const bool xcdAble = flowSolver && persistSolver && persistXcd && !xcdOnly && joints.count() == 0 && (persistWaves & 7u) == 0u && !debugOrderPending && !exactSeamStep;
+    const bool xcdAble = flowSolver && persistSolver && persistXcd && joints.count() == 0 && (persistWaves & 7u) == 0u && !debugOrderPending && !exactSeamStep;
     // small piles: the 128 waves of ONE XCD run the whole solve, every body hand-over goes through that XCD's L2 (tileOwner(..., single))
     auto xcdSingleFor = [&](uint32_t nm) { return xcdAble && persistXcdSingle && nm && nm < xcdMinManifolds && divUp(divUp(nm, 64) + kSchedBins + 8, persistWaves / 8u) <= 16u; };
     auto xcdPlanFor = [&](uint32_t nm) { return xcdAble && (nm >= xcdMinManifolds || xcdSingleFor(nm)); };
     bool finishInNarrow = false;  // k_narrow derives the pair list's final counts itself (no k_pair_finish launch)
-    GridParams* statsGridNext = nullptr; uint32_t statsCellCap = 0, statsBlocks = 0;   // (speculative steps: pairFinishStats runs beside k_emit_manifolds)
+    GridParams* statsGridNext = nullptr; uint32_t statsCellCap = 0, statsBlocks = 0;   // (speculative steps: pairFinishStats runs beside k_narrow_clip)
     if (nc) {
         uint32_t nblk = divUp(nc, 256);
         // the cell table (histogram + scan) covers cellCap cells; k_bp_grid_setup enlarges the cells if the grid would need more
@@ -387,7 +385,7 @@ enqueue_section:
             if ((knobs.knockout >> 16) && !L.dry && attempt == 0) {
                 static DBuf<uint64_t> kPairs; static DBuf<unsigned char> kSc, kSh; static hipEvent_t k0 = nullptr, k1 = nullptr;
                 if (!k0) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); }
-                if (knockPendingBp) { HIP_TRY(hipEventSynchronize(k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess && stepEvents) { knockMsSum += ms; ++knockLaunches; } knockPendingBp = false; }
+                if (knockPendingBp) { HIP_TRY(hipEventSynchronize(k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess && timingLevel >= 2u) { knockMsSum += ms; ++knockLaunches; } knockPendingBp = false; }
                 HIP_TRY(kPairs.ensure(pairKeys.cap)); HIP_TRY(kSc.ensure(sizeof(StepScalars))); HIP_TRY(kSh.ensure(sizeof(Shards)));
                 HIP_TRY(hipMemcpyAsync(kSc.p, sc, sizeof(StepScalars), hipMemcpyDeviceToDevice, st)); HIP_TRY(hipMemsetAsync(kSh.p, 0, sizeof(Shards), st));
                 static uint32_t word, zero = 0u; word = (knobs.knockout >> 16) >= 0x80u ? 0u : (knobs.knockout & 0xFF0000u);   // (0x800000: nothing removed)
@@ -408,13 +406,12 @@ enqueue_section:
             }
             // (a box pile: nearly every pair is of one type and k_pair_finish decides against partitioning — k_pair_partition then does nothing but cost its
             // launch slot: a speculative step whose predecessor was not partitioned leaves it out; if this step wants it after all, k_pair_finish voids the step)
-            const bool skipPartitionEnabled = knobs.skipPartition;
-            skippedPartition = spec && skipPartitionEnabled && havePartitionFlag && !lastPartitioned;
+            skippedPartition = spec && havePartitionFlag && !lastPartitioned;
             // (and without k_pair_partition nothing needs the list's final counts before k_narrow: its workgroups derive them themselves — one launch less)
-            finishInNarrow = skippedPartition && knobs.finishInNarrow && knobs.statsInEmit && std::min(cap, bound(last.numPairs, 4096)) != 0u;
+            finishInNarrow = skippedPartition && knobs.finishInNarrow && std::min(cap, bound(last.numPairs, 4096)) != 0u;
             if (!finishInNarrow)
             L.launch(k_pair_finish, dim3(1), dim3(256), 0, st, shards.p, sc, spec ? std::min(cap, bound(last.numPairs, 4096)) : 0xFFFFFFFFu, nc, nblk, attempt == 0 ? axisPartials.p : nullptr, blockBounds.p, attempt == 0 ? gridNext : nullptr, cellCapNext,
-                     skippedPartition ? 0u : 1u, spec && knobs.statsInEmit ? 0u : 1u /* speculative: an extra workgroup of k_emit_manifolds does the statistics, off the critical path */);
+                     skippedPartition ? 0u : 1u, spec ? 0u : 1u /* speculative: an extra workgroup of k_narrow_clip does the statistics, off the critical path */);
             if (spec) { pairBound = std::min(cap, bound(last.numPairs, 4096)); break; }
             int rc = readScalars(); if (rc != MI_OK) return rc;
             pairBound = hs.numPairs + hs.numHmContacts;   // the terrain contacts are appended to the pair list after the narrow phase
@@ -457,7 +454,7 @@ enqueue_section:
         }
         L.launch(k_narrow, dim3(narrowBlocks), dim3(B), 0, st, pairBound, queueRegion, sc, pairKeys.p, pairKeysS.p, wShape.p, hset, npPacked.p, npNormal.p, npPoints.p, boxQueue.p,
                  reinterpret_cast<ulonglong2*>(tab[tabCur ^ 1].p), histCap, finishInNarrow ? shards.p : nullptr, pairBound, shards.p);
-        const bool statsInClip = spec && statsGridNext != nullptr && knobs.statsInEmit;   // (a synchronous step: k_pair_finish did it)
+        const bool statsInClip = spec && statsGridNext != nullptr;   // (a synchronous step: k_pair_finish did it)
         L.launch(k_narrow_clip, dim3(kBoxQueues * (queueRegion / B) + (statsInClip ? 1u : 0u)), dim3(B), 0, st, queueRegion, sc, pairKeys.p, pairKeysS.p, wShape.p, boxQueue.p, npPacked.p, npNormal.p, npPoints.p, shards.p,
                  statsInClip ? shards.p : nullptr, sc, nc, statsBlocks, axisPartials.p, blockBounds.p, statsGridNext, statsCellCap, blockSkip && prepared ? shard.cbLive.p : nullptr);
         // (a GJK-only kernel feeding a queue of hits to an EPA kernel was measured: no gain — the GJK half already needs ~250 VGPRs)
@@ -476,19 +473,18 @@ enqueue_section:
             const HmOut hmOut{sc, pairBound, pairKeys.p, pairKeysS.p, npPacked.p, npNormal.p, npPoints.p};
             L.launch(k_hm_contacts<true, false>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
             L.launch(k_hm_contacts<true, true>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
-            if (hmStash.p && pairBound) L.launch(k_hm_write_stashed, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);   // (sized for all pairs: the terrain contacts are among them)
+            L.launch(k_hm_write_stashed, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);   // (sized for all pairs: the terrain contacts are among them)
             L.launch(k_hm_finish, dim3(1), dim3(1), 0, st, sc, pairBound);
         }
         HIP_TRY(scanPairs.run(L, reinterpret_cast<unsigned long long*>(npPacked.p), reinterpret_cast<unsigned long long*>(npScan.p), pairBound, st));
         if (eventsEnabled) HIP_TRY(manIsNew.ensure(pairBound));
-        const bool statsInEmit = false;   // (the statistics workgroup moved to k_narrow_clip, above)
 #ifdef MI_DBG_KNOCKOUT
         // development (tools/gpu_knockout.sh): k_emit_manifolds a first time with parts removed (g_dbgKnock bits 8-12) and its read-modify-write targets (per-body colour
         // masks, the next history table, round-0 proposals, round flags) redirected to scratch; everything else it writes the real launch below writes again.
         if (((knobs.knockout >> 8) & 0xFFu) && !L.dry && tabValid) {
             static DBuf<unsigned long long> kUsed, kTop; static DBuf<HistSlot> kTab; static DBuf<uint32_t> kFlags; static hipEvent_t k0 = nullptr, k1 = nullptr;
             if (!k0) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); }
-            if (knockPendingEmit) { HIP_TRY(hipEventSynchronize(k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess && stepEvents) { knockMsSum += ms; ++knockLaunches; } knockPendingEmit = false; }
+            if (knockPendingEmit) { HIP_TRY(hipEventSynchronize(k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess && timingLevel >= 2u) { knockMsSum += ms; ++knockLaunches; } knockPendingEmit = false; }
             HIP_TRY(kUsed.ensure(bodyUsed.cap)); HIP_TRY(kTop.ensure(bodyTop.cap)); HIP_TRY(kTab.ensure(tab[tabCur ^ 1].cap)); HIP_TRY(kFlags.ensure(64));
             HIP_TRY(hipMemsetAsync(kUsed.p, 0, kUsed.cap * 8, st)); HIP_TRY(hipMemsetAsync(kTab.p, 0, kTab.cap * sizeof(HistSlot), st)); HIP_TRY(hipMemsetAsync(kTop.p, 0, kTop.cap * 8, st));
             static uint32_t word, zero = 0u; word = ((knobs.knockout >> 8) & 0xFFu) >= 0x80u ? 0u : (knobs.knockout & 0xFF00u);   // (0x8000: nothing removed = the harness itself)
@@ -497,20 +493,18 @@ enqueue_section:
             hipLaunchKernelGGL(k_emit_manifolds, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, nb, pairKeys.p, pairKeysS.p, npPacked.p, npScan.p, cEmit.p,
                                manPair.p, manBodies.p, manInfo.p, colWork.p, color.p, tab[tabCur].p, tabMask[tabCur], kUsed.p, eventsEnabled ? manIsNew.p : nullptr, sc,
                                heightmap ? make_float2(hmParams.restitution, hmParams.friction) : make_float2(0.f, 0.f), kTab.p, tabMask[tabCur ^ 1], manKept.p, histHint[hintOf[tabCur]].p, histHint[hintOf[tabCur ^ 1]].p /* (a fresh insertion may raise a hint: harmless, they only ever grow) */,
-                               (const Shards*)nullptr, statsBlocks, axisPartials.p, blockBounds.p, statsGridNext, statsCellCap, (const uint8_t*)nullptr, seamOn ? seamId.p : nullptr,
-                               round0InEmit ? kTop.p + (nb + 1) : nullptr, kFlags.p);
+                               seamOn ? seamId.p : nullptr, round0InEmit ? kTop.p + (nb + 1) : nullptr, kFlags.p);
             (void)hipEventRecord(k1, st);
             HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &zero, sizeof(zero), 0, hipMemcpyHostToDevice, st));
             knockPendingEmit = true;
         }
 #endif
-        L.launch(k_emit_manifolds, dim3(divUp(pairBound, B) + (statsInEmit ? 1u : 0u)), dim3(B), 0, st, nc, nb, pairKeys.p, pairKeysS.p, npPacked.p, npScan.p, cEmit.p,
+        L.launch(k_emit_manifolds, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, nb, pairKeys.p, pairKeysS.p, npPacked.p, npScan.p, cEmit.p,
                                                         manPair.p, manBodies.p, manInfo.p, colWork.p, color.p,
                                                         tabValid ? tab[tabCur].p : nullptr, tabMask[tabCur], bodyUsed.p, eventsEnabled ? manIsNew.p : nullptr, sc,
                                                         heightmap ? make_float2(hmParams.restitution, hmParams.friction) : make_float2(0.f, 0.f),
                                                         tab[tabCur ^ 1].p, tabMask[tabCur ^ 1], manKept.p, tabValid ? histHint[hintOf[tabCur]].p : nullptr, histHint[hintOf[tabCur ^ 1]].p,
-                                                        statsInEmit ? shards.p : nullptr, statsBlocks, axisPartials.p, blockBounds.p, statsGridNext, statsCellCap, blockSkip && prepared ? shard.cbLive.p : nullptr, seamOn ? seamId.p : nullptr,
-                                                        round0InEmit ? bodyTop.p + (nb + 1) : nullptr, roundFlagsPtr());
+                                                        seamOn ? seamId.p : nullptr, round0InEmit ? bodyTop.p + (nb + 1) : nullptr, roundFlagsPtr());
     }
     // ---------------------------------------------------------------------------------------------- triggers / force fields
     std::vector<mi_event> triggerEvents;
@@ -546,20 +540,20 @@ enqueue_section:
     bool shardCounted = false;   // sharded world: this rank's manifolds / contacts are counted inside k_manifold_keys when that runs, else by k_shard_count
     const bool xcdSingle = xcdSingleFor(nmBound);
     const bool xcdPlan = xcdPlanFor(nmBound);
-    const uint32_t colorMargin = knobs.colorMargin;   // extra rounds enqueued beyond the previous step's count
     // converged rounds exit at once, but every enqueued round costs its launch slot (~4.6 us): a scene that replays its steps as graphs wants the same
     // launches step after step (a multiple of 4), a large one exactly what the previous step needed plus the margin
-    // ... or, with the colouring tail (k_bin_hist runs whatever rounds are missing: colorTail in kernels.hpp), what the previous step needed + 1 (MI_COLOR_TAIL_MARGIN): the tail's rounds are slow (a device-wide barrier with cache write-back each), it is there for the
+    // ... or, with the colouring tail (k_bin_hist runs whatever rounds are missing: colorTail in kernels.hpp), what the previous step needed + 1: the tail's rounds are slow (a device-wide barrier with cache write-back each), it is there for the
     // step that outgrows its predecessor by more, not for every other step
+    constexpr uint32_t kColorMargin = 3, kColorTailMargin = 1;   // extra rounds enqueued beyond the previous step's count, without / with the tail
     if (spec && colorTailHold) --colorTailHold;
     const bool colorTailOn = spec && knobs.colorTail && !colorTailHold;   // (colorTailHold: the tail's device-wide barrier timed out recently — a margin of enqueued rounds instead, like the other fault paths)
     if (graphStep && colorTailOn) {   // a scene that replays its steps as graphs: the same launches step after step — the count only moves when the need outgrows it or falls 2 below
-        const uint32_t need = std::min<uint32_t>(96u, last.colorRounds + knobs.colorTailMargin);
+        const uint32_t need = std::min<uint32_t>(96u, last.colorRounds + kColorTailMargin);
         if (need > colorBatchSticky || need + 2u < colorBatchSticky) colorBatchSticky = need;
     }
-    uint32_t colorBatch = !spec ? 20u : graphStep ? (colorTailOn ? colorBatchSticky : std::min<uint32_t>(96u, (last.colorRounds + std::max(colorMargin, last.colorRounds / 4u) + 3u) & ~3u))
-                                      : colorTailOn ? std::min<uint32_t>(96u, last.colorRounds + knobs.colorTailMargin)
-                                                  : std::min<uint32_t>(96u, last.colorRounds + std::max(colorMargin, last.colorRounds / 4u));
+    uint32_t colorBatch = !spec ? 20u : graphStep ? (colorTailOn ? colorBatchSticky : std::min<uint32_t>(96u, (last.colorRounds + std::max(kColorMargin, last.colorRounds / 4u) + 3u) & ~3u))
+                                      : colorTailOn ? std::min<uint32_t>(96u, last.colorRounds + kColorTailMargin)
+                                                  : std::min<uint32_t>(96u, last.colorRounds + std::max(kColorMargin, last.colorRounds / 4u));
     if (colorTailOn && knobs.colorRoundsMax) colorBatch = std::min(colorBatch, knobs.colorRoundsMax);
     if (nmBound) {
         tilesCap = divUp(nmBound, 64) + kSchedBins + 8; ctCap = divUp(conBound, 64) + 4 * kSchedBins + 8;
@@ -581,8 +575,7 @@ enqueue_section:
                 L.launch(k_manifold_place, dim3(divUp(nmBound, kKeyItems)), dim3(256), 0, st, nmBound, sc, sortKeys[0].p, sortVals[0].p, keyCount.p, sortVals[1].p);
             }
         }
-        const bool xcdNoSort = knobs.xcdNoSort;   // development: manifold order as emitted
-        const uint32_t* perm = xcdPlan && !xcdSingle && !xcdNoSort ? sortVals[1].p : nullptr;
+        const uint32_t* perm = xcdPlan && !xcdSingle ? sortVals[1].p : nullptr;
         unsigned long long* top[2] = {bodyTop.p, bodyTop.p + (nb + 1)};
         if (debugOrderPending) { int rc = applyDebugOrder(); if (rc != MI_OK) return rc; }   // (synchronous step: hs holds this step's counts) every manifold -> the sequential colour
         uint32_t round = round0InEmit ? 1u : 0u;
@@ -647,11 +640,10 @@ enqueue_section:
     // ---------------------------------------------------------------------------------------------- constraints
     const uint32_t tilesLaunch = spec ? tilesCap : totalTiles;   // sync mode knows the exact tile count (mirrorSchedule)
     const bool useFlow = flowSolver && !launchFallbackSteps && (!debugOrderPending || debugOrderLevelled) && (spec || bins[kSchedBins - 1].count == 0 || !nmBound);   // the overflow colour needs the sequential kernel
-    const bool fuseEnabled = knobs.fuseJoints;
-    const bool fused = useFlow && fuseEnabled && joints.allInIslands() && !exactSeamStep;   // joints of all sweeps inside the dataflow launch
+    const bool fused = useFlow && joints.allInIslands() && !exactSeamStep;   // joints of all sweeps inside the dataflow launch
     // slots (tiles) one persistent workgroup must hold: exact in a synchronous step, from the previous step's lists (+ slack) in a speculative one
     auto persistSlots = [&](uint32_t tiles, bool xcd, bool speculative) -> uint32_t {
-        if (!xcd) return divUp(tiles, xcdOnly ? persistWaves / 8u : persistWaves);
+        if (!xcd) return divUp(tiles, persistWaves);
         uint32_t longest = 0;
         if (speculative) longest = (haveXcdEstimate && lastXcdSingle == xcdSingle) ? lastXcdMax + lastXcdMax / 8u + 16u : xcdSingle ? tiles + 16u : divUp(tiles, 8) + 64u;
         else for (uint32_t x = 0; x < 8u; ++x) { uint32_t n = 0; for (uint32_t bn = 0; bn < kSchedBins; ++bn) n += tileOwnerCount(x, divUp(bins[bn].count, 64), bn, xcdSingle ? 1u : 0u); longest = std::max(longest, n); }
@@ -698,7 +690,7 @@ enqueue_section:
                 while (profEvents.size() < e + 2) { hipEvent_t ev_; HIP_TRY(hipEventCreate(&ev_)); profEvents.push_back(ev_); }
                 (void)hipEventRecord(profEvents[e], st);
             }
-            L.launch(k_solve_flow_islands, dim3((uint32_t)(per * perLaunch)), dim3(64), flowLds, st, it, perLaunch, joints.numIslands, joints.dIslands, joints.dSteps, joints.dIslandBodies, iu, ia, bv, bodyUsed.p,
+            L.launch(k_solve_flow_islands, dim3((uint32_t)(per * perLaunch)), dim3(64), 0, st, it, perLaunch, joints.numIslands, joints.dIslands, joints.dSteps, joints.dIslandBodies, iu, ia, bv, bodyUsed.p,
                                                                                    tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, sc, islandPriv, iters);
             if (profileSolve) { (void)hipEventRecord(profEvents[2 * (size_t)profLaunches + 1], st); ++profLaunches; }
         }
@@ -717,9 +709,9 @@ enqueue_section:
         }
         const bool impLds = persistImpLds && maxSlots * (4u * 512u + 24u) <= 38u * 1024u;   // beyond that the impulses travel as granules in `imp` (no size limit)
         const uint32_t ldsMeta = maxSlots * (64u * 40u + 4u * 512u + 24u) + 16u, ldsImp = maxSlots * (4u * 512u + 24u) + 16u, ldsDesc = maxSlots * 24u + 16u;
-#define MI_PERSIST_ARGS iters, maxSlots, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, gVel.p, sc, xcdOnly, xcdTiles.p, xcdListCap, bodyOwner.p, gVelL.p, slotMeta.p, imp.p, xcdFault, knobs.persistResident ? 1u : 0u
+#define MI_PERSIST_ARGS iters, maxSlots, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, gVel.p, sc, xcdTiles.p, xcdListCap, bodyOwner.p, gVelL.p, slotMeta.p, imp.p, xcdFault, knobs.persistResident ? 1u : 0u
         // the solve stage IS this launch: its timing events ride on the dispatch (when this path is not taken they are recorded below)
-        hipEvent_t e6 = attached && (stepEventsMode || stageEvents) ? ev[6] : nullptr, e7 = attached && (stepEventsMode || stageEvents) ? ev[7] : nullptr;
+        hipEvent_t e6 = attached && timingLevel ? ev[6] : nullptr, e7 = attached && timingLevel ? ev[7] : nullptr;
         solveAttached = attached;
 #define MI_PERSIST_LAUNCH(A, B_, C_, LDS) do { if (attached) hipExtLaunchKernelGGL((k_contact_solve_persist<A, B_, C_>), dim3(persistWaves), dim3(64), LDS, st, e6, e7, 0, MI_PERSIST_ARGS); \
                                               else L.launch(k_contact_solve_persist<A, B_, C_>, dim3(persistWaves), dim3(64), LDS, st, MI_PERSIST_ARGS); } while (0)
@@ -729,7 +721,7 @@ enqueue_section:
         if ((knobs.knockout & 0xFFu) && usedXcd && metaLds && impLds && !L.dry) {
             static DBuf<float4> kv, kvl; static hipEvent_t k0 = nullptr, k1 = nullptr;
             if (!k0) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); kv.flags = gVel.flags; }
-            if (knockPending) { HIP_TRY(hipEventSynchronize(k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess && stepEvents) { knockMsSum += ms; ++knockLaunches; } knockPending = false; }   // (counted while the caller times steps: mi_world_set_stage_timing)
+            if (knockPending) { HIP_TRY(hipEventSynchronize(k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess && timingLevel >= 2u) { knockMsSum += ms; ++knockLaunches; } knockPending = false; }   // (counted while the caller times steps: mi_world_set_stage_timing)
             HIP_TRY(kv.ensure(gVel.cap)); HIP_TRY(kvl.ensure(gVelL.cap));
             HIP_TRY(hipMemcpyAsync(kv.p, gVel.p, gVel.cap * sizeof(float4), hipMemcpyDeviceToDevice, st));
             HIP_TRY(hipMemcpyAsync(kvl.p, gVelL.p, gVelL.cap * sizeof(float4), hipMemcpyDeviceToDevice, st));
@@ -741,7 +733,7 @@ enqueue_section:
 #endif
             (void)hipEventRecord(k0, st);
             hipLaunchKernelGGL((k_contact_solve_persist<true, true, true>), dim3(persistWaves), dim3(64), ldsMeta, st,
-                               iters, maxSlots, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, kv.p, sc, xcdOnly, xcdTiles.p, xcdListCap, bodyOwner.p, kvl.p, slotMeta.p, imp.p, 0u, knobs.persistResident ? 1u : 0u);
+                               iters, maxSlots, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, kv.p, sc, xcdTiles.p, xcdListCap, bodyOwner.p, kvl.p, slotMeta.p, imp.p, 0u, knobs.persistResident ? 1u : 0u);
             (void)hipEventRecord(k1, st);
             HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &zero, sizeof(zero), 0, hipMemcpyHostToDevice, st));
 #ifdef MI_DBG_TIMELINE
@@ -774,7 +766,7 @@ enqueue_section:
                 while (profEvents.size() < e + 2) { hipEvent_t ev_; HIP_TRY(hipEventCreate(&ev_)); profEvents.push_back(ev_); }
                 (void)hipEventRecord(profEvents[e], st);
             }
-            L.launch(k_contact_solve_flow, dim3(tilesLaunch * perLaunch), dim3(64), flowLds, st, it, perLaunch, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p, sc);
+            L.launch(k_contact_solve_flow, dim3(tilesLaunch * perLaunch), dim3(64), 0, st, it, perLaunch, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p, sc);
             if (profileSolve) { (void)hipEventRecord(profEvents[2 * (size_t)profLaunches + 1], st); ++profLaunches; }
             if (exactSeamStep) { int rcx = shardSweepExchange(it); if (rcx != MI_OK) return rcx; }   // exact seam: the owners' velocities of the shared bodies replace the ghost copies
         }
@@ -792,7 +784,7 @@ enqueue_section:
             uint32_t acc = 0;
             for (uint32_t k = 0; k < 4; ++k) { cl.tileStart[k] = bins[4 * c + k].tileStart; cl.ctStart[k] = bins[4 * c + k].ctStart; mainContacts += (uint64_t)bins[4 * c + k].count * (k + 1); }
             for (uint32_t i = 0; i < 4; ++i) { acc += divUp(bins[4 * c + (3 - i)].count, 64); cl.blockEnd[i] = acc; }
-            cl.numBlocks = acc; cl.swizzle = xcdSwizzle ? 1u : 0u;
+            cl.numBlocks = acc;
         }
         solveLaunches = iters * (tailStart + (tailStart < tailEnd ? 1u : 0u));
         for (uint32_t it = 0; it < iters; ++it) {
@@ -801,16 +793,15 @@ enqueue_section:
             for (uint32_t c = 0; c < tailStart; ++c) {
                 const ColorLaunch& cl = launches[c];
                 if (!cl.numBlocks) continue;
-                uint32_t grid_ = cl.swizzle ? divUp(cl.numBlocks, 8) * 8 : cl.numBlocks;
                 if (profileSolve) {
                     size_t e = 2 * (size_t)profLaunches;
                     while (profEvents.size() < e + 2) { hipEvent_t ev_; HIP_TRY(hipEventCreate(&ev_)); profEvents.push_back(ev_); }
                     (void)hipEventRecord(profEvents[e], st);
-                    L.launch(k_contact_solve, dim3(grid_), dim3(64), 0, st, cl, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
+                    L.launch(k_contact_solve, dim3(cl.numBlocks), dim3(64), 0, st, cl, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
                     (void)hipEventRecord(profEvents[e + 1], st);
                     ++profLaunches;
                 } else {
-                    L.launch(k_contact_solve, dim3(grid_), dim3(64), 0, st, cl, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
+                    L.launch(k_contact_solve, dim3(cl.numBlocks), dim3(64), 0, st, cl, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
                 }
             }
             if (tailStart < tailEnd) L.launch(k_contact_solve_tail, dim3(1), dim3(256), 0, st, binInfo.p, tailStart, tailEnd, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
@@ -823,8 +814,8 @@ enqueue_section:
     if (attached && !solveAttached) (void)hipEventRecord(ev[7], st);
 #define MI_VEL_ARGS nb, dt, gPos.p, gVel.p, bCogInvMass.p, bRot.p, bPosN.p, bRotN.p, bLinVelN.p, bAngVelN.p, bForceN.p, bTorqueN.p, gVelL.p, usedXcd ? bodyOwner.p : nullptr, bodyUsed.p, bodyTop.p, \
                     shard.enabled ? shard.active.p : nullptr, bPos.p, bLinVel.p, bAngVel.p, bForce.p, bTorque.p, shard.activePrev.p, shards.p, sc
-    if (attached && timeStepEnds && !blockSkip) hipExtLaunchKernelGGL(k_integrate_velocities<false>, dim3(divUp(nb + 1, B)), dim3(B), 0, st, nullptr, ev[8], 0, MI_VEL_ARGS, nullptr);
-    else if (attached && timeStepEnds) hipExtLaunchKernelGGL(k_integrate_velocities<true>, dim3(bodyGrid(divUp(nb + 1, B))), dim3(B), 0, st, nullptr, ev[8], 0, MI_VEL_ARGS, shard.blockLive.p);
+    if (attached && timesEnds(timingLevel) && !blockSkip) hipExtLaunchKernelGGL(k_integrate_velocities<false>, dim3(divUp(nb + 1, B)), dim3(B), 0, st, nullptr, ev[8], 0, MI_VEL_ARGS, nullptr);
+    else if (attached && timesEnds(timingLevel)) hipExtLaunchKernelGGL(k_integrate_velocities<true>, dim3(bodyGrid(divUp(nb + 1, B))), dim3(B), 0, st, nullptr, ev[8], 0, MI_VEL_ARGS, shard.blockLive.p);
     else if (blockSkip) L.launch(k_integrate_velocities<true>, dim3(bodyGrid(divUp(nb + 1, B))), dim3(B), 0, st, MI_VEL_ARGS, shard.blockLive.p);
     else L.launch(k_integrate_velocities<false>, dim3(divUp(nb + 1, B)), dim3(B), 0, st, MI_VEL_ARGS, nullptr);
 #undef MI_VEL_ARGS
@@ -838,7 +829,7 @@ enqueue_section:
         // step-ahead: the next step's k_bp_prepare, on the state this step has just written (the "N" set, current once the step is valid), the grid this step prepared and the
         // axis it chose (read from the device: StepScalars::axisNext survives the reset inside k_publish_readback), into the other set of world-shape / AABB rows
         if (knobs.stepAhead && spec && pass == PASS_PLAIN && spinReadback && fuseResetStep && !shard.enabled && nc && gridValid && knobs.fuseWorld && !graphStep && !debugSync &&
-            !timeStepEnds && !stageEvents && !debugOrderPending && !heightmap && !usesInteractions) {
+            !timesEnds(timingLevel) && !debugOrderPending && !heightmap && !usesInteractions) {
             HIP_TRY(wShapeAlt.ensure(wShape.cap)); HIP_TRY(aabbMinAlt.ensure(aabbMin.cap)); HIP_TRY(aabbMaxAlt.ensure(aabbMax.cap));
             hipLaunchKernelGGL(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, aabbMinAlt.p, aabbMaxAlt.p, grid.p + (gridCur ^ 1u), axisPartials.p, shards.p, sc, largeList.p, isLarge.p,
                                blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p, (const uint8_t*)nullptr, (const uint8_t*)nullptr, 1u,
@@ -862,7 +853,7 @@ enqueue_section:
         if (hit) {
             hit->lastUse = ++graphUseClock; ++graphHits;
             if (hipGraphLaunch(hit->exec, st) != hipSuccess) { (void)hipGetLastError(); graphsEnabled = false; dropStepGraphs(); pass = PASS_PLAIN; goto enqueue_section; }
-        } else if (!graphNoCapture && (sig == graphLastSig || sig == graphPrevSig)) {      // seen within the last two steps as well: capture it
+        } else if (sig == graphLastSig || sig == graphPrevSig) {      // seen within the last two steps as well: capture it
             if (stepGraphs.size() >= kMaxStepGraphs) { HIP_TRY(hipStreamSynchronize(st)); dropStepGraphs(); }   // a long-lived scene keeps changing shape: start over (all at once, with the stream idle)
             graphPrevSig = graphLastSig; graphLastSig = sig;
             if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); graphsEnabled = false; pass = PASS_PLAIN; }
@@ -1018,15 +1009,6 @@ enqueue_section:
     for (int k = 0; k < 3; ++k) shard.owned[k] = hs.shardOwned[k];
     if (seamMode()) { seamLast[0] = hs.seamStats[0]; seamLast[1] = hs.seamStats[1]; seamViolations += hs.seamStats[2]; }
     shard.flagsSwapPending = shard.enabled; shard.stepOpen = false; shard.flagsOfAStep = shard.enabled;
-    const bool xcdStats = knobs.xcdStats;   // development: how many bodies stayed XCD-local
-    if (xcdStats && usedXcd && ((totalSteps % 50u) == 0u || knobs.xcdNoSort)) {
-        std::vector<unsigned long long> own(nb);
-        HIP_TRY(hipMemcpy(own.data(), bodyOwner.p, (size_t)nb * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        size_t loc = 0, shared = 0; for (unsigned long long o : own) { int c = __builtin_popcountll(o); loc += c == 1; shared += c > 1; }
-        std::fprintf(stderr, "[mi_physics] step %llu: XCD-local bodies %zu, shared %zu, lists", (unsigned long long)totalSteps, loc, shared);
-        for (int x = 0; x < 8; ++x) std::fprintf(stderr, " %u", hs.xcdCount[x]);
-        std::fprintf(stderr, "\n");
-    }
     haveXcdEstimate = usedXcd; lastXcdSingle = usedXcdSingle;
     if (usedXcd) { uint32_t m = 0; for (int x = 0; x < 8; ++x) m = std::max(m, hs.xcdCount[x]); lastXcdMax = sticky(m, lastXcdMax, 16); }
     if (hs.tailRounds) { ++tailSteps; tailRoundsSum += hs.tailRounds; }
@@ -1044,11 +1026,9 @@ enqueue_section:
     counts.num_colors = manifoldsLast ? numColorsUsed : 0u /* (a step without manifolds builds no schedule: the mirrored one is an earlier step's) */; counts.sorting_axis = hs.axisCur; counts.reserved = solveLaunches;
     // the step's device times: read from its events LATER (finishTimes), the next step records into the other set
     finishTimes();   // (normally done already, at the start of this step)
-    timesPending = stepEventsMode == 2 || stageEvents; timesPendingSet = evSet; timesPendingStages = stageEvents; timesPendingEnds = timeStepEnds; timesPendingUpdates = (uint64_t)counts.num_contacts * iters;
+    timesPending = timingLevel != 0u; timesPendingSet = evSet; timesPendingLevel = timingLevel; timesPendingUpdates = (uint64_t)counts.num_contacts * iters;
     if (!timesPending) { times = mi_stage_times{}; ++timesSteps; contactUpdatesSum += timesPendingUpdates; }   // timing off: no stale times, and the step / contact-update counts still add up
     evSet ^= 1; ev = evSets[evSet];
-    const bool eagerTimes = knobs.eagerTimes;   // development: read them right here, as before
-    if (eagerTimes) finishTimes();
     return MI_OK;
 }
 // (the host gets here after the published read-back of the step the events belong to — but the HIP 7.0 runtime now and then still reports an event
@@ -1058,12 +1038,12 @@ void mi_world::finishTimes() {
     timesPending = false;
     hipEvent_t* e = evSets[timesPendingSet];
     auto el = [&](int a, int b) { return elapsedMs(e[a], e[b]); };
-    if (timesPendingStages) {
+    if (timesStages(timesPendingLevel)) {
         times.world_colliders = el(0, 1); times.broadphase = el(1, 2); times.narrowphase = el(2, 3); times.integrate_forces = el(3, 4);
         times.schedule = el(4, 5); times.init_constraints = el(5, 6);
     } else { times.world_colliders = times.broadphase = times.narrowphase = times.integrate_forces = times.schedule = times.init_constraints = 0.f; }
     times.solve = el(6, 7);
-    if (timesPendingEnds) { times.integrate_velocities = el(7, 8); times.total = el(0, 8); } else times.integrate_velocities = times.total = 0.f;   // (level 3: the step's ends were not timed)
+    if (timesEnds(timesPendingLevel)) { times.integrate_velocities = el(7, 8); times.total = el(0, 8); } else times.integrate_velocities = times.total = 0.f;   // (level 3: the step's ends were not timed)
     { float* a = &timesSum.world_colliders; const float* b = &times.world_colliders; for (int i = 0; i < 9; ++i) a[i] += b[i]; ++timesSteps;
       contactUpdatesSum += timesPendingUpdates; }
 }

@@ -200,5 +200,5 @@ def test_every_environment_variable_is_read_in_one_place():
     used = set()
     for f in list((root / "tests").glob("*.py")) + list((root / "tools").glob("*.py")) + list((root / "tools").glob("*.sh")) + [root / "bench.py", root / "__graft_entry__.py"]:
         used |= set(re.findall(r'\b(MI_[A-Z0-9_]+)\b', f.read_text()))
-    used = {u for u in used if not u.startswith(("MI_ERR", "MI_OK", "MI_EVENT", "MI_CONSTRAINT", "MI_OBJECT", "MI_API", "MI_SEAM", "MI_SHAPE", "MI_COLLIDER", "MI_DBG_TIMELINE", "MI_CLIP", "MI_SHARD_RECORD", "MI_LEARNING_API"))}
+    used = {u for u in used if not u.startswith(("MI_ERR", "MI_OK", "MI_EVENT", "MI_CONSTRAINT", "MI_OBJECT", "MI_API", "MI_SEAM", "MI_SHAPE", "MI_COLLIDER", "MI_DBG_TIMELINE", "MI_SHARD_RECORD", "MI_LEARNING_API"))}
     assert used <= known, f"unknown knobs: {sorted(used - known)}"

@@ -481,7 +481,7 @@ def test_gpu_other_contact_solvers_match_oracle(mi_lib, oracle_mod, monkeypatch,
     assert kind is None or g.solver_kind() == kind   # (MI_ASYNC=0: every step synchronous, whatever solver the exact sizes select)
     if kind is None: assert g.step_mode_stats()[1] == 0
     assert g.step_mode_stats()[2] <= 2, "the partitioned solver must not keep falling back"
-    # timing is opt-in: nothing by default; level 2 = the whole step and the solve stage; level 1 = every stage
+    # timing is opt-in: nothing by default; level 2 = the whole step and the solve stage; level 1 = every stage; level 3 = the solve stage alone
     t = g.stage_times()
     assert t["total"] == 0 and t["solve"] == 0
     g.set_stage_timing(2)
@@ -492,6 +492,10 @@ def test_gpu_other_contact_solvers_match_oracle(mi_lib, oracle_mod, monkeypatch,
     g.step_fixed(s, sc.dt, 1); o.step_fixed(s, sc.dt, 1)
     t = g.stage_times()
     assert t["broadphase"] > 0 and t["narrowphase"] > 0 and abs(t["total"] - sum(v for k, v in t.items() if k != "total")) < 0.2 * t["total"]
+    g.set_stage_timing(3)
+    g.step_fixed(s, sc.dt, 1); o.step_fixed(s, sc.dt, 1)
+    t = g.stage_times()
+    assert t["solve"] > 0 and t["total"] == 0 and t["broadphase"] == 0
     assert g.physics_transforms()[0].tobytes() == o.physics_transforms()[0].tobytes()
 
 
