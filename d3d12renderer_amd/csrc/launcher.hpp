@@ -7,6 +7,8 @@
 //               rate (~5 us per launch against kernels of 2-5 us), not by the device.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+#include <cassert>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -71,6 +73,15 @@ struct Launcher {
             note(hipGetLastError());
             if (traceEach) note(hipStreamSynchronize(st));   // (MI_DEBUG_SYNC: a memory fault ends the process inside this wait — the line above names the launch)
         }
+    }
+    // `timed`: the launch carries timing events on its own dispatch (hipExtLaunchKernelGGL; either event, or both, may be null: it stays that runtime call); otherwise
+    // it is launch().  A graph cannot hold that form and a signature has no place for it: plain passes with hashing off only.
+    template <class... KArgs, class... Args>
+    void launchTimed(bool timed, hipEvent_t start, hipEvent_t stop, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args&&... args) {
+        if (!timed) { launch(kernel, grid, block, lds, st, std::forward<Args>(args)...); return; }
+        assert(!dry && !hashing);
+        std::tuple<std::decay_t<KArgs>...> t(static_cast<std::decay_t<KArgs>>(std::forward<Args>(args))...);
+        std::apply([&](auto&... a) { hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, st, start, stop, 0, a...); }, t);
     }
     bool traceEach = false; uint32_t traceOrdinal = 0;
     hipError_t memsetAsync(void* p, int v, size_t n, hipStream_t st) {

@@ -64,6 +64,7 @@ struct DBuf {
         p = np; cap = ncap;
         return hipSuccess;
     }
+    void swap(DBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(flags, o.flags); }
 };
 
 // One scan site: the record arrays, ticket counter and generation of k_exclusive_scan (kernels.hpp).  Nothing is reset between
@@ -144,6 +145,7 @@ template <> inline void sigMix<HeightmapParams>(Launcher& L, const HeightmapPara
 }
 }
 
+struct StepAttempt;   // world_step.inc
 struct mi_world {
     int device = 0;
     Knobs knobs;   // the environment, read once at creation (knobs.hpp)
@@ -320,10 +322,16 @@ struct mi_world {
     int uploadHeightmap();
     bool eventsEnabled = false; DBuf<uint8_t> manIsNew; DBuf<DeviceEvent> devEvents; std::vector<mi_event> pendingEvents;
     DBuf<float4> rows, slotNormal; DBuf<float4> imp; DBuf<float2> slotMass; DBuf<uint4> slotMeta; DBuf<uint2> tileDesc;
-    bool usedFlow = false, skippedPartition = false, havePartitionFlag = false, lastPartitioned = false;
+    bool usedFlow = false, havePartitionFlag = false, lastPartitioned = false;
     bool usedFused = false;
 #if defined(MI_DBG_KNOCKOUT) || defined(MI_DBG_TIMELINE)
-    bool knockPending = false, knockPendingEmit = false, knockPendingBp = false; double knockMsSum = 0.0; uint32_t knockLaunches = 0; unsigned long long* dbgTimelineBuf = nullptr;   // development builds only (world_step.inc)
+    // development builds only (world_step.inc): the three knock-out sites with their scratch buffers, the persistent solver's timeline
+    struct KnockSite { hipEvent_t k0 = nullptr, k1 = nullptr; bool pending = false; uint32_t word = 0; } knockBp, knockEmit, knockSolve;
+    double knockMsSum = 0.0; uint32_t knockLaunches = 0, knockZero = 0; unsigned long long* dbgTimelineBuf = nullptr; unsigned long long* dbgTimelineKnock = nullptr;
+    DBuf<uint64_t> knockPairs; DBuf<unsigned char> knockSc, knockSh; DBuf<unsigned long long> knockUsed, knockTop; DBuf<HistSlot> knockTab; DBuf<uint32_t> knockFlags; DBuf<float4> knockVel, knockVelL;
+    int dbgKnockWait(KnockSite& s); template <class F> int dbgKnockLaunch(KnockSite& s, uint32_t word, F&& launch);
+    int dbgKnockBroad(uint32_t bpc, uint32_t cap, GridParams* gridUse); int dbgKnockEmit(const StepAttempt& a); int dbgKnockSolve(const StepAttempt& a, uint32_t ldsMeta);
+    int dbgTimelineDump();
 #endif
     bool persistSolver = true, persistMetaLds = true, persistImpLds = true, usedPersist = false; uint32_t persistWaves = 1024;   // one resident workgroup per SIMD owns its tiles through all sweeps (k_contact_solve_persist)
     uint32_t flowFallbacks = 0;
@@ -364,7 +372,19 @@ struct mi_world {
     int upload();
     int download();
     int stepInternal(const mi_step_settings& s, float dt);
+    // one attempt at a step (world_step.inc): plan, enqueue (once per pass: signature / capture / plain), wait, validate, commit
     int runStep(const mi_step_settings& s, float dt, bool speculative);
+    int planStep(StepAttempt& a); int enqueueStep(StepAttempt& a); int submitPass(StepAttempt& a, bool& again);
+    int stagePrepare(StepAttempt& a); int stageBroad(StepAttempt& a); int stageNarrow(StepAttempt& a); int stageInteractions(StepAttempt& a); int stageForces(StepAttempt& a);
+    int stageSchedule(StepAttempt& a); int stageConstraintInit(StepAttempt& a); int stageSolve(StepAttempt& a); int stageIntegrate(StepAttempt& a); int stagePublish(StepAttempt& a);
+    int solveFused(StepAttempt& a); int solvePersistent(StepAttempt& a); int solveFlow(StepAttempt& a); int solvePerColour(StepAttempt& a);
+    int awaitReadback(); int validateStep(StepAttempt& a); int collectEvents(StepAttempt& a); void commitStep(const StepAttempt& a);
+    void mark(const StepAttempt& a, int id); int readScalars(); int profileBegin(); void profileEnd(); int orderSequentialBin();
+    ForcesArgs forcesArgs(const StepAttempt& a); KeysArgs keysArgs(uint32_t nm);
+    uint32_t colorBatchFor(const StepAttempt& a, bool colorTailOn); uint32_t persistSlots(const StepAttempt& a);
+    bool exactSeamStep() const { return shard.enabled && shard.exact; }   // every sweep ends in an exchange with the neighbours: one launch per sweep (the generic dataflow path), nothing persistent
+    bool emitsRound0() const { return knobs.round0InEmit && !debugOrderPending; }   // colouring round 0 inside k_emit_manifolds (the caller's order re-colours everything by itself)
+    bool xcdAble() const; bool xcdSingleFor(uint32_t nm) const; bool xcdPlanFor(uint32_t nm) const;
     // Every enqueue of a step goes through L (launcher.hpp).  Steps of a small scene are replayed as ONE HIP graph when their
     // signature (every launch, pointer, size and scalar) equals that of a captured step: ~35 launches of 2-5 us kernels are bound by
     // the host's launch rate otherwise.

@@ -205,358 +205,474 @@ int mi_world::interactionsDevice(uint32_t interPairBound) {
     return MI_OK;
 }
 
-int mi_world::runStep(const mi_step_settings& settings, float dt, bool spec) {
-    const uint32_t nb = (uint32_t)bodies.size(), nc = (uint32_t)colliders.size();
-    const uint32_t B = 256;
-    StepScalars* sc = scalarsPtr();
-    hipStream_t st = stream;
-    int evi = 0;
-    const bool debugSync = knobs.debugSync;   // development: find the stage a device fault comes from
-    L.traceEach = debugSync; L.traceOrdinal = 0;
-    // The step (events 0 / 8) and the solve stage (6 / 7) are always timed.  A recorded event is a barrier packet of its own (~6 us of
-    // idle device per event: 24 us per step); where the stage is ONE kernel the events ride on that kernel's dispatch instead
-    // (hipExtLaunchKernelGGL start / stop events): no packet, no gap.  `attached` = this step's 0 / 6 / 7 / 8 are attached ones.
-    bool attached = !debugSync;   // (set per pass below: a graph cannot hold the attached form, it gets recorded events)
-    // Timing is opt-in (mi_world_set_stage_timing): even ATTACHED events are not free — the start / stop events riding on the solver's dispatch cost ~11 us of idle
-    // device per step (the kernels before / after wait for the signals), the step's two ~1.5 us: 12 us of a 1.0 ms step for numbers nobody asked for.
-    auto mark = [&]() {
-        const int id = evi++;
-        if (debugSync && !L.dry) { std::fprintf(stderr, "[mi_physics] step %llu: waiting for the stage ending at mark %d\n", (unsigned long long)totalSteps, id); std::fflush(stderr);   // (a memory fault ends the process inside the wait: the last line names the stage)
-            hipError_t e = hipStreamSynchronize(st); if (e != hipSuccess) std::fprintf(stderr, "[mi_physics] step %llu (%s): stage ending at mark %d: %s\n", (unsigned long long)totalSteps, spec ? "speculative" : "synchronous", id, hipGetErrorString(e)); }
-        if (!timingLevel) return;
-        if (attached && (id == 0 || id == 6 || id == 7 || id == 8)) return;
-        if (!timesEnds(timingLevel) && (id == 0 || id == 8)) return;   // level 3: the solve stage alone (the step's own start / stop events cost two more gaps)
-        if (!timesStages(timingLevel) && id != 0 && id != 6 && id != 7 && id != 8) return;   // levels 2 and 3: no stage boundaries
-        L.eventRecord(ev[id], st);
-    };
-    auto bound = [](uint32_t last, uint32_t slack) { return last + last / 8u + slack; };
-    auto readScalars = [&]() -> int { HIP_TRY(hipMemcpyAsync(&hs, sc, sizeof(StepScalars), hipMemcpyDeviceToHost, st)); HIP_TRY(hipStreamSynchronize(st)); return MI_OK; };
+// The nine event slots of a step (ev[]): the boundaries of mi_stage_times' stages, in the order they are passed.
+enum StepEvent { EV_STEP_BEGIN, EV_PREPARED, EV_BROAD, EV_NARROW, EV_FORCES, EV_SCHEDULE, EV_SOLVE_BEGIN, EV_SOLVE_END, EV_STEP_END };
+static bool isStepEnd(int id) { return id == EV_STEP_BEGIN || id == EV_STEP_END; }
+static bool isSolveEnd(int id) { return id == EV_SOLVE_BEGIN || id == EV_SOLVE_END; }
+// Passes over enqueueStep (launcher.hpp): a speculative step of a small scene first runs it DRY (signature only); a known
+// signature is replayed from its captured graph, one seen in the previous step as well is captured now, anything else runs plainly.
+enum StepPass { PASS_PLAIN, PASS_DRY, PASS_CAPTURE };
 
-    // Passes over the enqueue section below (launcher.hpp): a speculative step of a small scene first runs it DRY (signature only); a known
-    // signature is replayed from its captured graph, one seen in the previous step as well is captured now, anything else runs plainly.
-    const bool debugSyncG = debugSync;
+// What one attempt at a step (one runStep call) knows: decided by planStep once, or by an enqueue stage for the stages behind it (every pass runs every stage and
+// finds the same values).  Plain data on runStep's stack.  No device pointer is kept here: buffers are (re)allocated on the way through a step, every launch reads x.p itself.
+struct StepAttempt {
+    mi_step_settings settings; float dt; bool spec; uint32_t nb, nc;
+    // planStep
+    bool graphStep, fuseResetStep, skipReset, useAhead;
+    int pass; bool attached;   // attached: this pass's EV_STEP_BEGIN / SOLVE_BEGIN / SOLVE_END / STEP_END ride on kernel dispatches (a graph cannot hold that form, it gets recorded events)
+    // stagePrepare
+    bool blockSkip, seamOn, prepared;
+    // stageBroad
+    uint32_t pairBound;       // upper bound of this step's collision pairs that launches / scans are sized for
+    bool skippedPartition, finishInNarrow;  // finishInNarrow: k_narrow derives the pair list's final counts itself (no k_pair_finish launch)
+    GridParams* statsGridNext; uint32_t statsCellCap, statsBlocks;   // (speculative steps: pairFinishStats runs beside k_narrow_clip)
+    // stageInteractions
+    uint32_t interPairBound; std::vector<mi_event> triggerEvents;
+    // stageForces
+    bool keysWithForces;
+    // stageSchedule
+    uint32_t nmBound, conBound, tilesCap, ctCap, eventCap, xcdListCap;
+    bool xcdSingle, xcdPlan;
+    bool shardCounted;   // sharded world: this rank's manifolds / contacts are counted inside k_manifold_keys when that runs, else by k_shard_count
+    // stageConstraintInit
+    uint32_t tilesLaunch, persistMaxSlots; bool useFlow, fused, persistPlan; IslandPrivate islandPriv;
+    // stageSolve
+    bool solveAttached; uint64_t mainContacts;
+};
+static uint32_t specBound(uint32_t last, uint32_t slack) { return last + last / 8u + slack; }
+// sharded world: the per-body / per-collider passes run a fixed number of workgroups that stride over the blocks of 256 and skip those with nothing simulated in them
+static uint32_t bodyGrid(const StepAttempt& a, uint32_t blocks) { return a.blockSkip ? std::min(blocks, kShardGrid) : blocks; }
+
+int mi_world::readScalars() { HIP_TRY(hipMemcpyAsync(&hs, scalarsPtr(), sizeof(StepScalars), hipMemcpyDeviceToHost, stream)); HIP_TRY(hipStreamSynchronize(stream)); return MI_OK; }
+// The step (EV_STEP_BEGIN / EV_STEP_END) and the solve stage (EV_SOLVE_BEGIN / EV_SOLVE_END) are always timed.  A recorded event is a barrier packet of its own (~6 us of
+// idle device per event: 24 us per step); where the stage is ONE kernel the events ride on that kernel's dispatch instead
+// (Launcher::launchTimed: start / stop events): no packet, no gap.  `a.attached` = this pass's four are attached ones.
+// Timing is opt-in (mi_world_set_stage_timing): even ATTACHED events are not free — the start / stop events riding on the solver's dispatch cost ~11 us of idle
+// device per step (the kernels before / after wait for the signals), the step's two ~1.5 us: 12 us of a 1.0 ms step for numbers nobody asked for.
+void mi_world::mark(const StepAttempt& a, int id) {
+    if (knobs.debugSync && !L.dry) { std::fprintf(stderr, "[mi_physics] step %llu: waiting for the stage ending at mark %d\n", (unsigned long long)totalSteps, id); std::fflush(stderr);   // (a memory fault ends the process inside the wait: the last line names the stage)
+        hipError_t e = hipStreamSynchronize(stream); if (e != hipSuccess) std::fprintf(stderr, "[mi_physics] step %llu (%s): stage ending at mark %d: %s\n", (unsigned long long)totalSteps, a.spec ? "speculative" : "synchronous", id, hipGetErrorString(e)); }
+    if (!timingLevel) return;
+    if (a.attached && (isStepEnd(id) || isSolveEnd(id))) return;
+    if (!timesEnds(timingLevel) && isStepEnd(id)) return;   // level 3: the solve stage alone (the step's own start / stop events cost two more gaps)
+    if (!timesStages(timingLevel) && !isStepEnd(id) && !isSolveEnd(id)) return;   // levels 2 and 3: no stage boundaries
+    L.eventRecord(ev[id], stream);
+}
+// XCD partitioning pays once the pile is big enough to keep eight L2s busy; it needs the persistent kernel (no joints)
+bool mi_world::xcdAble() const { return flowSolver && persistSolver && persistXcd && joints.count() == 0 && (persistWaves & 7u) == 0u && !debugOrderPending && !exactSeamStep(); }
+// small piles: the 128 waves of ONE XCD run the whole solve, every body hand-over goes through that XCD's L2 (tileOwner(..., single))
+bool mi_world::xcdSingleFor(uint32_t nm) const { return xcdAble() && persistXcdSingle && nm && nm < xcdMinManifolds && divUp(divUp(nm, 64) + kSchedBins + 8, persistWaves / 8u) <= 16u; }
+bool mi_world::xcdPlanFor(uint32_t nm) const { return xcdAble() && (nm >= xcdMinManifolds || xcdSingleFor(nm)); }
+// per-launch HIP events around the solver's launches (mi_world_step_profiled): a pair per launch, created as needed
+int mi_world::profileBegin() {
+    if (!profileSolve) return MI_OK;
+    const size_t e = 2 * (size_t)profLaunches;
+    while (profEvents.size() < e + 2) { hipEvent_t ev_; HIP_TRY(hipEventCreate(&ev_)); profEvents.push_back(ev_); }
+    (void)hipEventRecord(profEvents[e], stream);
+    return MI_OK;
+}
+void mi_world::profileEnd() { if (profileSolve) { (void)hipEventRecord(profEvents[2 * (size_t)profLaunches + 1], stream); ++profLaunches; } }
+
+int mi_world::runStep(const mi_step_settings& settings, float dt, bool spec) {
+    StepAttempt a{};
+    a.settings = settings; a.dt = dt; a.spec = spec; a.nb = (uint32_t)bodies.size(); a.nc = (uint32_t)colliders.size();
+    L.traceEach = knobs.debugSync; L.traceOrdinal = 0;   // development: find the stage a device fault comes from
+    int rc = planStep(a); if (rc != MI_OK) return rc;
+    for (bool again = true; again;) {
+        rc = enqueueStep(a); if (rc != MI_OK) return rc;
+        rc = submitPass(a, again); if (rc != MI_OK) return rc;
+    }
+    if (poseArm.armed) {   // the poses of the state this step is producing, enqueued behind it (a step that turns out void produces them again)
+        ++pose.produced_ahead; poseArm.done = false;
+        int rcp = posesProduce(poseArm.t, true, true); if (rcp != MI_OK) return rcp;
+        poseArm.done = true;
+    }
+    rc = awaitReadback(); if (rc != MI_OK) return rc;
+    rc = validateStep(a); if (rc != MI_OK) return rc;   // (STEP_RETRY among them)
+    rc = collectEvents(a); if (rc != MI_OK) return rc;
+    commitStep(a);
+    return MI_OK;
+}
+
+// What is decided once per attempt, before any pass: whether the step goes through the graph passes, whether the reset rides in the publish kernel, and whether
+// what ran ahead of this step is adopted.
+int mi_world::planStep(StepAttempt& a) {
+    const uint32_t nb = a.nb, nc = a.nc;
+    const bool debugSync = knobs.debugSync;
     constexpr uint32_t kGraphMaxColliders = 32768;   // larger scenes are not launch-bound (MI_GRAPH=all replays them too)
-    const bool graphStep = spec && graphsEnabled && !profileSolve && !xcdFaultTest && !flowFaultTest && !debugSyncG && !launchFallbackSteps &&
-                           (graphsForAll || nc <= kGraphMaxColliders) && readbackSeqDev.p;
-    enum { PASS_PLAIN, PASS_DRY, PASS_CAPTURE };
-    int pass = graphStep ? PASS_DRY : PASS_PLAIN;
+    a.graphStep = a.spec && graphsEnabled && !profileSolve && !xcdFaultTest && !flowFaultTest && !debugSync && !launchFallbackSteps &&
+                  (graphsForAll || nc <= kGraphMaxColliders) && readbackSeqDev.p;
+    a.pass = a.graphStep ? PASS_DRY : PASS_PLAIN;
     // k_reset_scalars' work rides at the end of k_publish_readback (`scalarsClean`: the previous attempt's publish has done it): the step then starts with k_bp_prepare, whose 27 us
     // give the host time to get the next launches out — the 4 us launch and the ~8 us gap behind it are gone.  Not for worlds whose host side looks at the device words again after
     // the read-back (events: the "every collision ended" pass), nor where another kernel would have to carry the step's start event.  (A sharded world's exchange runs
     // behind the reset: k_shard_pack counts its records from zero, and nothing of the next step minds the counts it leaves.)
-    const bool fuseResetStep = knobs.fuseReset && spinReadback && readbackSeqDev.p && !eventsEnabled && !seamMode() && nc && gridValid && knobs.fuseWorld && !debugSync;
-    bool skipReset = fuseResetStep && scalarsClean;
+    a.fuseResetStep = knobs.fuseReset && spinReadback && readbackSeqDev.p && !eventsEnabled && !seamMode() && nc && gridValid && knobs.fuseWorld && !debugSync;
+    a.skipReset = a.fuseResetStep && scalarsClean;
     scalarsClean = false;
     // step-ahead (world.hip): the previous speculative step has already run this step's k_bp_prepare on the state it produced.  Adopted only if this step would launch exactly that
     // kernel on exactly those inputs; otherwise what it counted is cleared (cell histogram here, the scalars / counter shards by k_reset_scalars) and the step starts as usual.
-    const bool aheadFits = ahead.pending && !ahead.stale && spec && pass == PASS_PLAIN && skipReset && !shard.enabled && nc && gridValid && knobs.fuseWorld && !heightmap && !usesInteractions &&
+    const bool aheadFits = ahead.pending && !ahead.stale && a.spec && a.pass == PASS_PLAIN && a.skipReset && !shard.enabled && nc && gridValid && knobs.fuseWorld && !heightmap && !usesInteractions &&
                            ahead.nc == nc && ahead.nb == nb && ahead.gridIdx == gridCur && ahead.axis == sapAxis && ahead.pos == bPos.p && ahead.rot == bRot.p && ahead.shape == cShape.p &&
                            !timesEnds(timingLevel) && !debugSync && !debugOrderPending;
     if (ahead.pending && !aheadFits) {
-        skipReset = false;
-        if (cellCount.p) HIP_TRY(hipMemsetAsync(cellCount.p, 0, cellCount.cap * sizeof(uint32_t), st));   // (16 MB; this path is rare: an outside write, a void step, another step mode)
+        a.skipReset = false;
+        if (cellCount.p) HIP_TRY(hipMemsetAsync(cellCount.p, 0, cellCount.cap * sizeof(uint32_t), stream));   // (16 MB; this path is rare: an outside write, a void step, another step mode)
     }
-    const bool useAhead = ahead.pending && aheadFits;
+    a.useAhead = ahead.pending && aheadFits;
     ahead.pending = false; ahead.stale = false;
-    if (useAhead) { std::swap(wShape.p, wShapeAlt.p); std::swap(wShape.cap, wShapeAlt.cap); std::swap(aabbMin.p, aabbMinAlt.p); std::swap(aabbMin.cap, aabbMinAlt.cap); std::swap(aabbMax.p, aabbMaxAlt.p); std::swap(aabbMax.cap, aabbMaxAlt.cap); ++aheadUsed; }
-enqueue_section:
-    evi = 0; skippedPartition = false;
+    if (a.useAhead) { wShape.swap(wShapeAlt); aabbMin.swap(aabbMinAlt); aabbMax.swap(aabbMaxAlt); ++aheadUsed; }
+    return MI_OK;
+}
+
+// Everything a step puts on the stream, in stage order; every pass runs exactly this.
+int mi_world::enqueueStep(StepAttempt& a) {
     L.trace = graphDebug;
-    L.begin(pass == PASS_DRY, pass != PASS_PLAIN);
-    attached = !debugSync && pass == PASS_PLAIN;
-    mark();  // 0
-    if (skipReset) {}   // (the step's start event rides on k_bp_prepare below)
-    else if (attached && timesEnds(timingLevel)) hipExtLaunchKernelGGL(k_reset_scalars, dim3(1), dim3(128), 0, st, ev[0], nullptr, 0, sc, shards.p, roundFlagsPtr(), keyCount.p);
-    else L.launch(k_reset_scalars, dim3(1), dim3(128), 0, st, sc, shards.p, roundFlagsPtr(), keyCount.p);
-    // sharded world: the per-body / per-collider passes run a fixed number of workgroups that stride over the blocks of 256 and skip those with nothing simulated in them
-    const bool blockSkip = shard.enabled && nb && knobs.shardBlockSkip;
-    auto bodyGrid = [&](uint32_t blocks) { return blockSkip ? std::min(blocks, kShardGrid) : blocks; };
+    L.begin(a.pass == PASS_DRY, a.pass != PASS_PLAIN);
+    a.attached = !knobs.debugSync && a.pass == PASS_PLAIN;
+    mark(a, EV_STEP_BEGIN);
+    int rc = stagePrepare(a); if (rc != MI_OK) return rc;
+    mark(a, EV_PREPARED);
+    rc = stageBroad(a); if (rc != MI_OK) return rc;
+    if (a.pass == PASS_PLAIN) finishTimes();   // the previous step's event times, now that this step's first kernels keep the device busy
+    mark(a, EV_BROAD);
+    rc = stageNarrow(a); if (rc != MI_OK) return rc;
+    rc = stageInteractions(a); if (rc != MI_OK) return rc;
+    mark(a, EV_NARROW);
+    rc = stageForces(a); if (rc != MI_OK) return rc;
+    mark(a, EV_FORCES);
+    rc = stageSchedule(a); if (rc != MI_OK) return rc;
+    mark(a, EV_SCHEDULE);
+    rc = stageConstraintInit(a); if (rc != MI_OK) return rc;
+    mark(a, EV_SOLVE_BEGIN);
+    rc = stageSolve(a); if (rc != MI_OK) return rc;
+    mark(a, EV_SOLVE_END);
+    if (a.attached && !a.solveAttached) (void)hipEventRecord(ev[EV_SOLVE_END], stream);
+    rc = stageIntegrate(a); if (rc != MI_OK) return rc;
+    mark(a, EV_STEP_END);
+    return stagePublish(a);
+}
+
+// What becomes of the pass just enqueued.  A signature pass: replay the captured graph of that signature, or capture (signature seen within the last two steps), or
+// run plainly; a capture pass: instantiate and launch.  `again`: enqueueStep is to run once more, as a.pass.
+int mi_world::submitPass(StepAttempt& a, bool& again) {
+    hipStream_t st = stream;
+    again = false;
+    auto plainAgain = [&]() { a.pass = PASS_PLAIN; again = true; };
+    if (a.pass == PASS_DRY) {
+        const uint64_t sig = L.h ^ ((uint64_t)L.ops << 48);
+        StepGraph* hit = nullptr;
+        for (StepGraph& g : stepGraphs) if (g.sig == sig && g.exec) { hit = &g; break; }
+        if (graphDebug) {
+            if (!hit && !graphPrevOps2.empty()) {   // compare with the step before the previous one (same buffer parity)
+                size_t k = 0; while (k < graphPrevOps2.size() && k < L.opHashes.size() && graphPrevOps2[k] == L.opHashes[k]) ++k;
+                std::fprintf(stderr, "[mi_physics] step %llu: graph signature differs from that of two steps ago at operation %zu of %zu (then %zu)\n", (unsigned long long)totalSteps, k, L.opHashes.size(), graphPrevOps2.size());
+            }
+            graphPrevOps2 = graphPrevOps; graphPrevOps = L.opHashes;
+        }
+        if (hit) {
+            hit->lastUse = ++graphUseClock; ++graphHits;
+            if (hipGraphLaunch(hit->exec, st) != hipSuccess) { (void)hipGetLastError(); graphsEnabled = false; dropStepGraphs(); plainAgain(); }
+        } else if (sig == graphLastSig || sig == graphPrevSig) {      // seen within the last two steps as well: capture it
+            if (stepGraphs.size() >= kMaxStepGraphs) { HIP_TRY(hipStreamSynchronize(st)); dropStepGraphs(); }   // a long-lived scene keeps changing shape: start over (all at once, with the stream idle)
+            graphPrevSig = graphLastSig; graphLastSig = sig;
+            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); graphsEnabled = false; plainAgain(); }
+            else { a.pass = PASS_CAPTURE; again = true; }
+        } else { graphPrevSig = graphLastSig; graphLastSig = sig; ++graphPlain; plainAgain(); }
+    } else if (a.pass == PASS_CAPTURE) {
+        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+        bool ok = hipStreamEndCapture(st, &graph) == hipSuccess && graph && L.firstError == hipSuccess;
+        if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+        if (graph) (void)hipGraphDestroy(graph);
+        if (ok) ok = hipGraphLaunch(exec, st) == hipSuccess;
+        if (!ok) {   // this runtime cannot hold the step in a graph: plain launches from now on (nothing has been enqueued yet)
+            (void)hipGetLastError();
+            if (exec) (void)hipGraphExecDestroy(exec);
+            graphsEnabled = false; dropStepGraphs(); plainAgain();
+            return MI_OK;
+        }
+        stepGraphs.push_back(StepGraph{graphLastSig, exec, ++graphUseClock}); ++graphCaptures;
+    }
+    return MI_OK;
+}
+
+// Reset of the step's scalars, shard / seam classification, world-space colliders (with the grid pass in the same kernel where a grid is ready), terrain contact counts.
+int mi_world::stagePrepare(StepAttempt& a) {
+    const uint32_t nb = a.nb, nc = a.nc, B = 256;
+    StepScalars* sc = scalarsPtr(); hipStream_t st = stream;
+    const bool startTimed = a.attached && timesEnds(timingLevel);   // the step's first kernel carries the start event
+    if (!a.skipReset) L.launchTimed(startTimed, ev[EV_STEP_BEGIN], nullptr, k_reset_scalars, dim3(1), dim3(128), 0, st, sc, shards.p, roundFlagsPtr(), keyCount.p);   // (else the start event rides on k_bp_prepare below)
+    a.blockSkip = shard.enabled && nb && knobs.shardBlockSkip;
     if (shard.enabled && nb) {
         HIP_TRY(shard.activePrev.ensure(std::max(nb, 1u)));
-        if (shard.flagsSwapPending) { std::swap(shard.active.p, shard.activePrev.p); std::swap(shard.active.cap, shard.activePrev.cap); shard.flagsSwapPending = false; }   // (not on the synchronous re-run of a step)
+        if (shard.flagsSwapPending) { shard.active.swap(shard.activePrev); shard.flagsSwapPending = false; }   // (not on the synchronous re-run of a step)
         const uint32_t bodyBlocks = divUp(nb, B), colliderBlocks = divUp(std::max(nc, 1u), B);
         HIP_TRY(shard.blockStamp.ensure(bodyBlocks)); HIP_TRY(shard.blockLive.ensure(bodyBlocks)); HIP_TRY(shard.cbLive.ensure(colliderBlocks));
         if (!shard.stepHost) { HIP_TRY(hipHostMalloc((void**)&shard.stepHost, sizeof(uint32_t))); HIP_TRY(shard.stepDev.ensure(4)); }
         *shard.stepHost = (uint32_t)totalSteps;     // (read by the copy below when it EXECUTES — pinned memory —, also when a replayed step graph executes it: written in the signature pass too)
         HIP_TRY(L.memcpyAsync(shard.stepDev.p, shard.stepHost, sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        if (blockSkip && (!shard.prevValid || shard.blocksAll)) {   // every block is recent (and counts as live) for this step: it classifies them all and finds out
+        if (a.blockSkip && (!shard.prevValid || shard.blocksAll)) {   // every block is recent (and counts as live) for this step: it classifies them all and finds out
             L.launch(k_fill_u32_from, dim3(divUp(bodyBlocks, B)), dim3(B), 0, st, shard.blockStamp.p, shard.stepDev.p, bodyBlocks);
             HIP_TRY(L.memsetAsync(shard.blockLive.p, 1, bodyBlocks, st)); HIP_TRY(L.memsetAsync(shard.cbLive.p, 1, colliderBlocks, st));
             if (!L.dry) shard.blocksAll = false;
         }
         if (!shard.prevValid) { HIP_TRY(L.memsetAsync(shard.activePrev.p, 1, nb, st)); if (!L.dry) shard.prevValid = true; }   // after an upload / an outside write: every body is copied once
-        L.launch(k_shard_classify, dim3(bodyGrid(bodyBlocks)), dim3(B), 0, st, nb, shard.sp, bPos.p, bRot.p, bCogInvMass.p, shard.active.p, shards.p, shard.root.p, shard.known.p,
-                 shard.activePrev.p, blockSkip ? shard.blockStamp.p : nullptr, shard.blockLive.p, shard.stepDev.p);
+        L.launch(k_shard_classify, dim3(bodyGrid(a, bodyBlocks)), dim3(B), 0, st, nb, shard.sp, bPos.p, bRot.p, bCogInvMass.p, shard.active.p, shards.p, shard.root.p, shard.known.p,
+                 shard.activePrev.p, a.blockSkip ? shard.blockStamp.p : nullptr, shard.blockLive.p, shard.stepDev.p);
     }
-    const bool seamOn = seamMode() && nb;
-    if (seamOn) {   // exact seam: which tile border every body is shared across (decides the class of its manifolds)
+    a.seamOn = seamMode() && nb;
+    if (a.seamOn) {   // exact seam: which tile border every body is shared across (decides the class of its manifolds)
         HIP_TRY(seamId.ensure(nb));
         if (shard.enabled) L.launch(k_seam_classify_shard, dim3(divUp(nb, B)), dim3(B), 0, st, nb, shard.sp, bPos.p, bRot.p, bCogInvMass.p, shard.root.p, shard.active.p, seamId.p);
         else L.launch(k_seam_classify_tiling, dim3(divUp(nb, B)), dim3(B), 0, st, nb, seamTiling.dBx.p, (uint32_t)seamTiling.bx.size(), seamTiling.dBz.p, (uint32_t)seamTiling.bz.size(), seamTiling.margin,
                       bPos.p, bRot.p, bCogInvMass.p, shard.root.p, seamId.p);
     }
-    if (shard.enabled && shard.exact && nb) {   // ... and the bodies whose velocities go to each neighbour after every sweep
+    if (exactSeamStep() && nb) {   // ... and the bodies whose velocities go to each neighbour after every sweep
         HIP_TRY(shard.sweepCount.ensure(8));
         HIP_TRY(L.memsetAsync(shard.sweepCount.p, 0, 8 * sizeof(uint32_t), st));
         SweepLists lists{}; for (uint32_t k = 0; k < shard.sp.numPeers; ++k) { HIP_TRY(shard.sweepList[k].ensure(shard.capacity)); lists.p[k] = shard.sweepList[k].p; }
         L.launch(k_seam_sweep_list, dim3(divUp(nb, B)), dim3(B), 0, st, nb, shard.sp, shard.active.p, bPos.p, bRot.p, bCogInvMass.p, shard.root.p, lists, shard.capacity, shard.sweepCount.p);
     }
+    a.prepared = false;
+    if (!nc) return MI_OK;
     // with a grid prepared by the previous step the world colliders are computed INSIDE k_bp_prepare (one launch, one pass over the AABB rows less)
-    const bool fuseWorldEnabled = knobs.fuseWorld;
-    const bool fuseWorld = nc && gridValid && fuseWorldEnabled;
-    bool prepared = false;
-    if (nc) {
-        if (fuseWorld) {   // (the cell histogram is all zero here: cleared once at upload, and every scan clears the cells it has read)
-#define MI_PREPARE_ARGS nc, aabbMin.p, aabbMax.p, grid.p + gridCur, axisPartials.p, shards.p, sc, largeList.p, isLarge.p, blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p, \
-                     shard.enabled ? shard.activePrev.p : nullptr, shard.enabled ? shard.active.p : nullptr, shard.enabled && shard.desc.rank != 0u ? 0u : 1u, \
-                     nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPos.p, bRot.p, hullAabb.p, wShape.p, aabbMin.p, aabbMax.p, sapAxis, shard.enabled ? shard.axisDev.p : nullptr, \
-                     blockSkip ? cbRange.p : nullptr, blockSkip ? shard.blockLive.p : nullptr, blockSkip ? shard.cbLive.p : nullptr
-            if (useAhead) {}   // (the previous step ran it: step-ahead)
-            else if (skipReset && attached && timesEnds(timingLevel) && !blockSkip) hipExtLaunchKernelGGL(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, ev[0], nullptr, 0, MI_PREPARE_ARGS);   // first kernel of the step: it carries the start event
-            else if (skipReset && attached && timesEnds(timingLevel)) hipExtLaunchKernelGGL(k_bp_prepare<true>, dim3(bodyGrid(divUp(nc, 256))), dim3(256), 0, st, ev[0], nullptr, 0, MI_PREPARE_ARGS);   // (sharded: k_shard_classify before it is not in the step's time)
-            else if (blockSkip) L.launch(k_bp_prepare<true>, dim3(bodyGrid(divUp(nc, 256))), dim3(256), 0, st, MI_PREPARE_ARGS);
-            else L.launch(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, MI_PREPARE_ARGS);
-#undef MI_PREPARE_ARGS
-            prepared = true;
-        } else
+    if (gridValid && knobs.fuseWorld) {   // (the cell histogram is all zero here: cleared once at upload, and every scan clears the cells it has read)
+        // Not launched if the previous step ran it (step-ahead).  Behind a skipped reset it is the first kernel of the step and carries the start event (sharded: k_shard_classify before it is not in the step's time).
+        if (!a.useAhead)
+            L.launchTimed(a.skipReset && startTimed, ev[EV_STEP_BEGIN], nullptr, a.blockSkip ? k_bp_prepare<true> : k_bp_prepare<false>, dim3(bodyGrid(a, divUp(nc, 256))), dim3(256), 0, st,
+                          nc, aabbMin.p, aabbMax.p, grid.p + gridCur, axisPartials.p, shards.p, sc, largeList.p, isLarge.p, blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p,
+                          shard.enabled ? shard.activePrev.p : nullptr, shard.enabled ? shard.active.p : nullptr, shard.enabled && shard.desc.rank != 0u ? 0u : 1u,
+                          nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPos.p, bRot.p, hullAabb.p, wShape.p, aabbMin.p, aabbMax.p, sapAxis, shard.enabled ? shard.axisDev.p : nullptr,
+                          a.blockSkip ? cbRange.p : nullptr, a.blockSkip ? shard.blockLive.p : nullptr, a.blockSkip ? shard.cbLive.p : nullptr);
+        a.prepared = true;
+    } else
         L.launch(k_world_colliders, dim3(divUp(nc, B)), dim3(B), 0, st, nc, nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPos.p, bRot.p, hullAabb.p,
-                                                     wShape.p, aabbMin.p, aabbMax.p, sc, sapAxis, shard.enabled ? shard.active.p : nullptr, shard.activePrev.p, shard.enabled ? shard.axisDev.p : nullptr);
-        if (heightmap) {   // terrain contacts per collider, their offsets and totals (they join the pair list after the collider-pair narrow phase)
-            const HullSet hmHulls{hullVerts.p, hullRanges.p};
-            L.launch(k_hm_lowest, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmSlow.p, hmHulls);
-            L.launch(k_hm_contacts<false, false>, dim3(divUp(nc, 4)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, nullptr, HmOut{}, hmHulls, hmStash.p);
-            L.launch(k_hm_contacts<false, true>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, nullptr, HmOut{}, hmHulls, hmStash.p);   // (the colliders the first pass flagged: a cell window beyond 64 cells)
-            HIP_TRY(scanTerrain.run(L, hmPacked.p, hmScan.p, nc, st));
-            L.launch(k_hm_totals, dim3(1), dim3(1), 0, st, nc, hmPacked.p, hmScan.p, sc);
-        }
+                 wShape.p, aabbMin.p, aabbMax.p, sc, sapAxis, shard.enabled ? shard.active.p : nullptr, shard.activePrev.p, shard.enabled ? shard.axisDev.p : nullptr);
+    if (heightmap) {   // terrain contacts per collider, their offsets and totals (they join the pair list after the collider-pair narrow phase)
+        const HullSet hmHulls{hullVerts.p, hullRanges.p};
+        L.launch(k_hm_lowest, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmSlow.p, hmHulls);
+        L.launch(k_hm_contacts<false, false>, dim3(divUp(nc, 4)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, nullptr, HmOut{}, hmHulls, hmStash.p);
+        L.launch(k_hm_contacts<false, true>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, nullptr, HmOut{}, hmHulls, hmStash.p);   // (the colliders the first pass flagged: a cell window beyond 64 cells)
+        HIP_TRY(scanTerrain.run(L, hmPacked.p, hmScan.p, nc, st));
+        L.launch(k_hm_totals, dim3(1), dim3(1), 0, st, nc, hmPacked.p, hmScan.p, sc);
     }
-    mark();  // 1
-    // ---------------------------------------------------------------------------------------------- broad phase
-    uint32_t pairBound = 0;   // upper bound of this step's collision pairs that launches / scans are sized for
-    auto forcesArgs = [&]() {   // (evaluated where it is launched: buffers may still be (re)allocated on the way there)
-        return ForcesArgs{bPos.p, bRot.p, bCogInvMass.p, bInvI.p, bParams.p, bLinVel.p, bAngVel.p, usesInteractions ? bForceStep.p : bForce.p, bTorque.p,
-                          gPos.p, gInvI.p, gVel.p, gVelL.p, bodyOwner.p, shard.enabled ? shard.active.p : nullptr, blockSkip ? shard.blockLive.p : nullptr, nb, dt, {globalForce.x, globalForce.y, globalForce.z}, 0u};
-    };
-    const bool round0InEmit = knobs.round0InEmit && !debugOrderPending;   // colouring round 0 inside k_emit_manifolds (the caller's order re-colours everything by itself)
-    // XCD partitioning pays once the pile is big enough to keep eight L2s busy; it needs the persistent kernel (no joints)
-    const bool exactSeamStep = shard.enabled && shard.exact;   // every sweep ends in an exchange with the neighbours: one launch per sweep (the generic dataflow path), nothing persistent
-    const bool xcdAble = flowSolver && persistSolver && persistXcd && joints.count() == 0 && (persistWaves & 7u) == 0u && !debugOrderPending && !exactSeamStep;
-    // small piles: the 128 waves of ONE XCD run the whole solve, every body hand-over goes through that XCD's L2 (tileOwner(..., single))
-    auto xcdSingleFor = [&](uint32_t nm) { return xcdAble && persistXcdSingle && nm && nm < xcdMinManifolds && divUp(divUp(nm, 64) + kSchedBins + 8, persistWaves / 8u) <= 16u; };
-    auto xcdPlanFor = [&](uint32_t nm) { return xcdAble && (nm >= xcdMinManifolds || xcdSingleFor(nm)); };
-    bool finishInNarrow = false;  // k_narrow derives the pair list's final counts itself (no k_pair_finish launch)
-    GridParams* statsGridNext = nullptr; uint32_t statsCellCap = 0, statsBlocks = 0;   // (speculative steps: pairFinishStats runs beside k_narrow_clip)
-    if (nc) {
-        uint32_t nblk = divUp(nc, 256);
-        // the cell table (histogram + scan) covers cellCap cells; k_bp_grid_setup enlarges the cells if the grid would need more
-        const uint32_t cellCapNext = std::min<uint32_t>(kMaxCells, std::max<uint32_t>(1u << 16, 4u * nc));
-        const uint32_t cellCap = gridValid ? (lastCellCap = std::min<uint32_t>(kMaxCells, (lastCellCap > gridNextCells && lastCellCap - gridNextCells <= 8192u) ? lastCellCap : ((gridNextCells + 1u + 4095u) & ~4095u))) : spec ? std::min<uint32_t>(kMaxCells, std::max<uint32_t>(1u << 16, 2u * last.numCells)) : kMaxCells;
-        GridParams* gridUse = grid.p + gridCur; GridParams* gridNext = grid.p + (gridCur ^ 1u);
-        statsGridNext = gridNext; statsCellCap = cellCapNext; statsBlocks = nblk;
-        if (prepared) {}   // k_bp_prepare ran with the world colliders
-        else if (gridValid) {
-            // the grid prepared at the end of the previous step (k_pair_finish): one fused kernel instead of five launches; the cell histogram
-            // is all zero here (cleared once at upload, and every scan clears the cells it has read)
-            L.launch(k_bp_prepare<false>, dim3(nblk), dim3(256), 0, st, nc, aabbMin.p, aabbMax.p, gridUse, axisPartials.p, shards.p, sc, largeList.p, isLarge.p, blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p, shard.enabled ? shard.activePrev.p : nullptr, shard.enabled ? shard.active.p : nullptr, shard.enabled && shard.desc.rank != 0u ? 0u : 1u,
-                     nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr, nullptr);
-        } else {
-            L.launch(k_axis_partials, dim3(nblk), dim3(256), 0, st, nc, aabbMin.p, aabbMax.p, axisPartials.p, shards.p, shard.enabled ? shard.active.p : nullptr, shard.enabled && shard.desc.rank != 0u ? 0u : 1u);
-            L.launch(k_bp_threshold, dim3(1), dim3(256), 0, st, nc, shards.p, sc);
-            L.launch(k_bp_classify, dim3(divUp(nc, B)), dim3(B), 0, st, nc, aabbMin.p, aabbMax.p, sc, largeList.p, isLarge.p, blockBounds.p);
-            L.launch(k_bp_grid_setup, dim3(1), dim3(256), 0, st, nc, nblk, cellCap, blockBounds.p, sc, gridUse);
-            L.launch(k_bp_cell_ids, dim3(divUp(nc, B)), dim3(B), 0, st, nc, aabbMin.p, aabbMax.p, isLarge.p, gridUse, cellKeys.p, cellRanks.p, cellCount.p);
-        }
-        HIP_TRY(scanCells.run(L, cellCount.p, cellLower.p, cellCap, st, true));
-        if (blockSkip && prepared) L.launch(k_bp_scatter_sorted<true>, dim3(bodyGrid(divUp(nc, B))), dim3(B), 0, st, nc, cellKeys.p, cellRanks.p, cellLower.p, aabbMin.p, aabbMax.p, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, shard.cbLive.p);
-        else L.launch(k_bp_scatter_sorted<false>, dim3(divUp(nc, B)), dim3(B), 0, st, nc, cellKeys.p, cellRanks.p, cellLower.p, aabbMin.p, aabbMax.p, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, nullptr);
-        if (pairKeys.cap == 0) { HIP_TRY(pairKeys.ensure(std::max<size_t>(1u << 16, 8 * (size_t)nc))); }
-        if (spec) { HIP_TRY(pairKeys.ensure(bound(last.numPairs, 4096))); }
-        if (usesInteractions && interKeys.cap == 0) HIP_TRY(interKeys.ensure(4096));
-        if (usesInteractions && spec) HIP_TRY(interKeys.ensure(bound(last.numInterPairs, 1024)));
-        for (int attempt = 0; attempt < 3; ++attempt) {
-            uint32_t cap = (uint32_t)std::min<size_t>(pairKeys.cap, 0x7FFFFFFFu);
-            const InterSink inter{usesInteractions ? interKeys.p : nullptr, (uint32_t)interKeys.cap, &sc->numInterPairs};
-            // sized for the small (grid) colliders expected — in a sharded world most colliders are dead and in no list; more than expected: the workgroups loop
-            const uint32_t smallBound = spec ? std::min(nc, bound(last.numSmall, 4096)) : nc;
-            const uint32_t bpc = (divUp(smallBound, kGridChunks * 256u) + 7u) & ~7u;   // a multiple of 8 (XCD-contiguous block order in k_bp_pairs_grid)
-            const uint32_t largeGx = std::min(divUp(smallBound + 1024u, B), 4096u), largeGy = std::min(16u, std::max(1u, divUp(spec ? last.numLarge + last.numLarge / 4u : 1024u, 64u)));
+    return MI_OK;
+}
+
+// Broad phase: cell table, sorted colliders, the pair pass (redone with a larger list while a synchronous step overflows it), the pair list's final counts and the next step's grid.
+int mi_world::stageBroad(StepAttempt& a) {
+    const uint32_t nb = a.nb, nc = a.nc, B = 256;
+    StepScalars* sc = scalarsPtr(); hipStream_t st = stream;
+    const bool spec = a.spec;
+    a.pairBound = 0; a.skippedPartition = false; a.finishInNarrow = false;
+    a.statsGridNext = nullptr; a.statsCellCap = 0; a.statsBlocks = 0;
+    if (!nc) return MI_OK;
+    uint32_t nblk = divUp(nc, 256);
+    // the cell table (histogram + scan) covers cellCap cells; k_bp_grid_setup enlarges the cells if the grid would need more
+    const uint32_t cellCapNext = std::min<uint32_t>(kMaxCells, std::max<uint32_t>(1u << 16, 4u * nc));
+    const uint32_t cellCap = gridValid ? (lastCellCap = std::min<uint32_t>(kMaxCells, (lastCellCap > gridNextCells && lastCellCap - gridNextCells <= 8192u) ? lastCellCap : ((gridNextCells + 1u + 4095u) & ~4095u))) : spec ? std::min<uint32_t>(kMaxCells, std::max<uint32_t>(1u << 16, 2u * last.numCells)) : kMaxCells;
+    GridParams* gridUse = grid.p + gridCur; GridParams* gridNext = grid.p + (gridCur ^ 1u);
+    a.statsGridNext = gridNext; a.statsCellCap = cellCapNext; a.statsBlocks = nblk;
+    if (a.prepared) {}   // k_bp_prepare ran with the world colliders
+    else if (gridValid) {
+        // the grid prepared at the end of the previous step (k_pair_finish): one fused kernel instead of five launches; the cell histogram
+        // is all zero here (cleared once at upload, and every scan clears the cells it has read)
+        L.launch(k_bp_prepare<false>, dim3(nblk), dim3(256), 0, st, nc, aabbMin.p, aabbMax.p, gridUse, axisPartials.p, shards.p, sc, largeList.p, isLarge.p, blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p, shard.enabled ? shard.activePrev.p : nullptr, shard.enabled ? shard.active.p : nullptr, shard.enabled && shard.desc.rank != 0u ? 0u : 1u,
+                 nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr, nullptr);
+    } else {
+        L.launch(k_axis_partials, dim3(nblk), dim3(256), 0, st, nc, aabbMin.p, aabbMax.p, axisPartials.p, shards.p, shard.enabled ? shard.active.p : nullptr, shard.enabled && shard.desc.rank != 0u ? 0u : 1u);
+        L.launch(k_bp_threshold, dim3(1), dim3(256), 0, st, nc, shards.p, sc);
+        L.launch(k_bp_classify, dim3(divUp(nc, B)), dim3(B), 0, st, nc, aabbMin.p, aabbMax.p, sc, largeList.p, isLarge.p, blockBounds.p);
+        L.launch(k_bp_grid_setup, dim3(1), dim3(256), 0, st, nc, nblk, cellCap, blockBounds.p, sc, gridUse);
+        L.launch(k_bp_cell_ids, dim3(divUp(nc, B)), dim3(B), 0, st, nc, aabbMin.p, aabbMax.p, isLarge.p, gridUse, cellKeys.p, cellRanks.p, cellCount.p);
+    }
+    HIP_TRY(scanCells.run(L, cellCount.p, cellLower.p, cellCap, st, true));
+    const bool skipBlocks = a.blockSkip && a.prepared;   // (the dead blocks' flags come from k_bp_prepare)
+    L.launch(skipBlocks ? k_bp_scatter_sorted<true> : k_bp_scatter_sorted<false>, dim3(skipBlocks ? bodyGrid(a, divUp(nc, B)) : divUp(nc, B)), dim3(B), 0, st,
+             nc, cellKeys.p, cellRanks.p, cellLower.p, aabbMin.p, aabbMax.p, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, skipBlocks ? shard.cbLive.p : nullptr);
+    if (pairKeys.cap == 0) { HIP_TRY(pairKeys.ensure(std::max<size_t>(1u << 16, 8 * (size_t)nc))); }
+    if (spec) { HIP_TRY(pairKeys.ensure(specBound(last.numPairs, 4096))); }
+    if (usesInteractions && interKeys.cap == 0) HIP_TRY(interKeys.ensure(4096));
+    if (usesInteractions && spec) HIP_TRY(interKeys.ensure(specBound(last.numInterPairs, 1024)));
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        uint32_t cap = (uint32_t)std::min<size_t>(pairKeys.cap, 0x7FFFFFFFu);
+        const InterSink inter{usesInteractions ? interKeys.p : nullptr, (uint32_t)interKeys.cap, &sc->numInterPairs};
+        // sized for the small (grid) colliders expected — in a sharded world most colliders are dead and in no list; more than expected: the workgroups loop
+        const uint32_t smallBound = spec ? std::min(nc, specBound(last.numSmall, 4096)) : nc;
+        const uint32_t bpc = (divUp(smallBound, kGridChunks * 256u) + 7u) & ~7u;   // a multiple of 8 (XCD-contiguous block order in k_bp_pairs_grid)
+        const uint32_t largeGx = std::min(divUp(smallBound + 1024u, B), 4096u), largeGy = std::min(16u, std::max(1u, divUp(spec ? last.numLarge + last.numLarge / 4u : 1024u, 64u)));
 #ifdef MI_DBG_KNOCKOUT
-            // development (tools/gpu_knockout.sh): the grid part of the pair pass a first time, on a scratch pair list and scratch counters, with parts removed (g_dbgKnock bits 16-18)
-            if ((knobs.knockout >> 16) && !L.dry && attempt == 0) {
-                static DBuf<uint64_t> kPairs; static DBuf<unsigned char> kSc, kSh; static hipEvent_t k0 = nullptr, k1 = nullptr;
-                if (!k0) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); }
-                if (knockPendingBp) { HIP_TRY(hipEventSynchronize(k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess && timingLevel >= 2u) { knockMsSum += ms; ++knockLaunches; } knockPendingBp = false; }
-                HIP_TRY(kPairs.ensure(pairKeys.cap)); HIP_TRY(kSc.ensure(sizeof(StepScalars))); HIP_TRY(kSh.ensure(sizeof(Shards)));
-                HIP_TRY(hipMemcpyAsync(kSc.p, sc, sizeof(StepScalars), hipMemcpyDeviceToDevice, st)); HIP_TRY(hipMemsetAsync(kSh.p, 0, sizeof(Shards), st));
-                static uint32_t word, zero = 0u; word = (knobs.knockout >> 16) >= 0x80u ? 0u : (knobs.knockout & 0xFF0000u);   // (0x800000: nothing removed)
-                HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &word, sizeof(word), 0, hipMemcpyHostToDevice, st));
-                (void)hipEventRecord(k0, st);
-                hipLaunchKernelGGL(k_bp_pairs_grid, dim3(5u * bpc), dim3(B), 0, st, nc, bpc, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, kPairs.p, cap, reinterpret_cast<StepScalars*>(kSc.p), reinterpret_cast<Shards*>(kSh.p), InterSink{nullptr, 0u, nullptr});
-                (void)hipEventRecord(k1, st);
-                HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &zero, sizeof(zero), 0, hipMemcpyHostToDevice, st));
-                knockPendingBp = true;
-            }
+        if (attempt == 0) { int rck = dbgKnockBroad(bpc, cap, gridUse); if (rck != MI_OK) return rck; }
 #endif
-            if (knobs.fuseLarge) {   // both passes in one launch, the large one in its first workgroups (k_bp_pairs)
-                const uint32_t largeBlocks = (largeGx * largeGy + 7u) & ~7u;
-                L.launch(k_bp_pairs, dim3(largeBlocks + 5u * bpc), dim3(B), 0, st, largeBlocks, largeGx, largeGy, nc, bpc, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, largeList.p, aabbMin.p, aabbMax.p, pairKeys.p, cap, sc, shards.p, inter);
-            } else {
-                L.launch(k_bp_pairs_grid, dim3(5u * bpc), dim3(B), 0, st, nc, bpc, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, pairKeys.p, cap, sc, shards.p, inter);
-                L.launch(k_bp_pairs_large, dim3(largeGx, largeGy), dim3(B), 0, st, nc, largeList.p, aabbMin.p, aabbMax.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, pairKeys.p, cap, sc, shards.p, inter);
-            }
-            // (a box pile: nearly every pair is of one type and k_pair_finish decides against partitioning — k_pair_partition then does nothing but cost its
-            // launch slot: a speculative step whose predecessor was not partitioned leaves it out; if this step wants it after all, k_pair_finish voids the step)
-            skippedPartition = spec && havePartitionFlag && !lastPartitioned;
-            // (and without k_pair_partition nothing needs the list's final counts before k_narrow: its workgroups derive them themselves — one launch less)
-            finishInNarrow = skippedPartition && knobs.finishInNarrow && std::min(cap, bound(last.numPairs, 4096)) != 0u;
-            if (!finishInNarrow)
-            L.launch(k_pair_finish, dim3(1), dim3(256), 0, st, shards.p, sc, spec ? std::min(cap, bound(last.numPairs, 4096)) : 0xFFFFFFFFu, nc, nblk, attempt == 0 ? axisPartials.p : nullptr, blockBounds.p, attempt == 0 ? gridNext : nullptr, cellCapNext,
-                     skippedPartition ? 0u : 1u, spec ? 0u : 1u /* speculative: an extra workgroup of k_narrow_clip does the statistics, off the critical path */);
-            if (spec) { pairBound = std::min(cap, bound(last.numPairs, 4096)); break; }
-            int rc = readScalars(); if (rc != MI_OK) return rc;
-            pairBound = hs.numPairs + hs.numHmContacts;   // the terrain contacts are appended to the pair list after the narrow phase
-            if (pairBound <= cap && hs.numInterPairs <= interKeys.cap) { if (debugOrderPending) { int rco = orientPairsLikeDebugOrder(); if (rco != MI_OK) return rco; } break; }
-            if (attempt == 2) return fail(MI_ERR_DEVICE, "pair pass did not settle");
-            if (pairBound > cap) HIP_TRY(pairKeys.ensure((size_t)pairBound + pairBound / 4));   // overflow: grow and redo the pair pass
-            if (hs.numInterPairs > interKeys.cap) HIP_TRY(interKeys.ensure((size_t)hs.numInterPairs + hs.numInterPairs / 4));
-            L.launch(k_reset_pair_counters, dim3(1), dim3(32), 0, st, sc, shards.p);
+        if (knobs.fuseLarge) {   // both passes in one launch, the large one in its first workgroups (k_bp_pairs)
+            const uint32_t largeBlocks = (largeGx * largeGy + 7u) & ~7u;
+            L.launch(k_bp_pairs, dim3(largeBlocks + 5u * bpc), dim3(B), 0, st, largeBlocks, largeGx, largeGy, nc, bpc, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, largeList.p, aabbMin.p, aabbMax.p, pairKeys.p, cap, sc, shards.p, inter);
+        } else {
+            L.launch(k_bp_pairs_grid, dim3(5u * bpc), dim3(B), 0, st, nc, bpc, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, pairKeys.p, cap, sc, shards.p, inter);
+            L.launch(k_bp_pairs_large, dim3(largeGx, largeGy), dim3(B), 0, st, nc, largeList.p, aabbMin.p, aabbMax.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, pairKeys.p, cap, sc, shards.p, inter);
+        }
+        // (a box pile: nearly every pair is of one type and k_pair_finish decides against partitioning — k_pair_partition then does nothing but cost its
+        // launch slot: a speculative step whose predecessor was not partitioned leaves it out; if this step wants it after all, k_pair_finish voids the step)
+        a.skippedPartition = spec && havePartitionFlag && !lastPartitioned;
+        // (and without k_pair_partition nothing needs the list's final counts before k_narrow: its workgroups derive them themselves — one launch less)
+        a.finishInNarrow = a.skippedPartition && knobs.finishInNarrow && std::min(cap, specBound(last.numPairs, 4096)) != 0u;
+        if (!a.finishInNarrow)
+        L.launch(k_pair_finish, dim3(1), dim3(256), 0, st, shards.p, sc, spec ? std::min(cap, specBound(last.numPairs, 4096)) : 0xFFFFFFFFu, nc, nblk, attempt == 0 ? axisPartials.p : nullptr, blockBounds.p, attempt == 0 ? gridNext : nullptr, cellCapNext,
+                 a.skippedPartition ? 0u : 1u, spec ? 0u : 1u /* speculative: an extra workgroup of k_narrow_clip does the statistics, off the critical path */);
+        if (spec) { a.pairBound = std::min(cap, specBound(last.numPairs, 4096)); break; }
+        int rc = readScalars(); if (rc != MI_OK) return rc;
+        a.pairBound = hs.numPairs + hs.numHmContacts;   // the terrain contacts are appended to the pair list after the narrow phase
+        if (a.pairBound <= cap && hs.numInterPairs <= interKeys.cap) { if (debugOrderPending) { int rco = orientPairsLikeDebugOrder(); if (rco != MI_OK) return rco; } break; }
+        if (attempt == 2) return fail(MI_ERR_DEVICE, "pair pass did not settle");
+        if (a.pairBound > cap) HIP_TRY(pairKeys.ensure((size_t)a.pairBound + a.pairBound / 4));   // overflow: grow and redo the pair pass
+        if (hs.numInterPairs > interKeys.cap) HIP_TRY(interKeys.ensure((size_t)hs.numInterPairs + hs.numInterPairs / 4));
+        L.launch(k_reset_pair_counters, dim3(1), dim3(32), 0, st, sc, shards.p);
+    }
+    return MI_OK;
+}
+
+// Narrow phase: contacts per pair (boxes / spheres directly and through the clip queues, GJK / EPA, terrain), their scan, and the manifolds with the colours they keep.
+int mi_world::stageNarrow(StepAttempt& a) {
+    const uint32_t nb = a.nb, nc = a.nc, B = 256, pairBound = a.pairBound;
+    StepScalars* sc = scalarsPtr(); hipStream_t st = stream;
+    const bool spec = a.spec;
+    if (!pairBound) return MI_OK;
+    HIP_TRY(pairKeysS.ensure(pairKeys.cap));
+    if (!a.skippedPartition) L.launch(k_pair_partition, dim3(divUp(pairBound, 1024)), dim3(256), 0, st, pairKeys.p, pairKeysS.p, sc);
+    HIP_TRY(npPacked.ensure(pairBound)); HIP_TRY(npScan.ensure(pairBound)); HIP_TRY(npNormal.ensure(pairBound)); HIP_TRY(npPoints.ensure(4 * (size_t)pairBound));
+    HIP_TRY(manPair.ensure(pairBound)); HIP_TRY(manBodies.ensure(pairBound)); HIP_TRY(manInfo.ensure(pairBound));
+    HIP_TRY(colWork.ensure(pairBound)); HIP_TRY(color.ensure(pairBound));
+    // bodyUsed is all zero here (k_integrate_velocities of the previous step / upload cleared it); k_emit_manifolds seeds it with the kept colours
+    HullSet hset{hullVerts.p, hullRanges.p};
+    const uint32_t narrowBlocks = divUp(pairBound, B);
+    const uint32_t queueRegion = divUp(narrowBlocks, kBoxQueues) * B;   // a queue can hold every pair of the workgroups that feed it
+    HIP_TRY(boxQueue.ensure((size_t)kBoxQueues * queueRegion));
+    uint32_t histCap = 1024;
+    {   // the NEXT step's colour history: sized here, cleared by k_narrow on the side (k_emit_manifolds already enters the manifolds that keep their colour)
+        const uint32_t histBound = spec ? std::min(pairBound, specBound(last.numManifolds, 1024)) : pairBound;
+        const int nt = tabCur ^ 1;
+        while (histCap < 2u * histBound) histCap <<= 1;
+        HIP_TRY(tab[nt].ensure(histCap)); HIP_TRY(manKept.ensure(pairBound));
+        tabMask[nt] = histCap - 1u;
+        // probe hints: the next table goes on with the previous table's array while the size stays (kept entries keep their slots, hence their displacements); a table
+        // of another size — or the first one — starts on the other array, zeroed
+        if (tabValid && tabMask[nt] == tabMask[tabCur] && histHint[hintOf[tabCur]].cap >= histCap) hintOf[nt] = hintOf[tabCur];
+        else {
+            hintOf[nt] = tabValid ? hintOf[tabCur] ^ 1 : 0;
+            HIP_TRY(histHint[hintOf[nt]].ensure(histCap));
+            HIP_TRY(L.memsetAsync(histHint[hintOf[nt]].p, 0, (size_t)histCap * sizeof(uint32_t), st));
         }
     }
-    if (pass == PASS_PLAIN) finishTimes();   // the previous step's event times, now that this step's first kernels keep the device busy
-    mark();  // 2
-    // ---------------------------------------------------------------------------------------------- narrow phase
-    if (pairBound) {
-        HIP_TRY(pairKeysS.ensure(pairKeys.cap));
-        if (!skippedPartition) L.launch(k_pair_partition, dim3(divUp(pairBound, 1024)), dim3(256), 0, st, pairKeys.p, pairKeysS.p, sc);
-        HIP_TRY(npPacked.ensure(pairBound)); HIP_TRY(npScan.ensure(pairBound)); HIP_TRY(npNormal.ensure(pairBound)); HIP_TRY(npPoints.ensure(4 * (size_t)pairBound));
-        HIP_TRY(manPair.ensure(pairBound)); HIP_TRY(manBodies.ensure(pairBound)); HIP_TRY(manInfo.ensure(pairBound));
-        HIP_TRY(colWork.ensure(pairBound)); HIP_TRY(color.ensure(pairBound));
-        // bodyUsed is all zero here (k_integrate_velocities of the previous step / upload cleared it); k_emit_manifolds seeds it with the kept colours
-        HullSet hset{hullVerts.p, hullRanges.p};
-        const uint32_t narrowBlocks = divUp(pairBound, B);
-        const uint32_t queueRegion = divUp(narrowBlocks, kBoxQueues) * B;   // a queue can hold every pair of the workgroups that feed it
-        HIP_TRY(boxQueue.ensure((size_t)kBoxQueues * queueRegion));
-        uint32_t histCap = 1024;
-        {   // the NEXT step's colour history: sized here, cleared by k_narrow on the side (k_emit_manifolds already enters the manifolds that keep their colour)
-            const uint32_t histBound = spec ? std::min(pairBound, bound(last.numManifolds, 1024)) : pairBound;
-            const int nt = tabCur ^ 1;
-            while (histCap < 2u * histBound) histCap <<= 1;
-            HIP_TRY(tab[nt].ensure(histCap)); HIP_TRY(manKept.ensure(pairBound));
-            tabMask[nt] = histCap - 1u;
-            // probe hints: the next table goes on with the previous table's array while the size stays (kept entries keep their slots, hence their displacements); a table
-            // of another size — or the first one — starts on the other array, zeroed
-            if (tabValid && tabMask[nt] == tabMask[tabCur] && histHint[hintOf[tabCur]].cap >= histCap) hintOf[nt] = hintOf[tabCur];
-            else {
-                hintOf[nt] = tabValid ? hintOf[tabCur] ^ 1 : 0;
-                HIP_TRY(histHint[hintOf[nt]].ensure(histCap));
-                HIP_TRY(L.memsetAsync(histHint[hintOf[nt]].p, 0, (size_t)histCap * sizeof(uint32_t), st));
-            }
-        }
-        L.launch(k_narrow, dim3(narrowBlocks), dim3(B), 0, st, pairBound, queueRegion, sc, pairKeys.p, pairKeysS.p, wShape.p, hset, npPacked.p, npNormal.p, npPoints.p, boxQueue.p,
-                 reinterpret_cast<ulonglong2*>(tab[tabCur ^ 1].p), histCap, finishInNarrow ? shards.p : nullptr, pairBound, shards.p);
-        const bool statsInClip = spec && statsGridNext != nullptr;   // (a synchronous step: k_pair_finish did it)
-        L.launch(k_narrow_clip, dim3(kBoxQueues * (queueRegion / B) + (statsInClip ? 1u : 0u)), dim3(B), 0, st, queueRegion, sc, pairKeys.p, pairKeysS.p, wShape.p, boxQueue.p, npPacked.p, npNormal.p, npPoints.p, shards.p,
-                 statsInClip ? shards.p : nullptr, sc, nc, statsBlocks, axisPartials.p, blockBounds.p, statsGridNext, statsCellCap, blockSkip && prepared ? shard.cbLive.p : nullptr);
-        // (a GJK-only kernel feeding a queue of hits to an EPA kernel was measured: no gain — the GJK half already needs ~250 VGPRs)
-        if (usesGjk) {
-            HIP_TRY(epaQueue.ensure(pairBound)); HIP_TRY(epaSimplex.ensure((size_t)pairBound * kEpaSimplexRows));
-            // few GJK pairs (vehicles on hull tiles, a handful of capsules): one WAVE per pair for GJK as well; many: GJK by lanes, EPA by waves
-            const int gjkWaveMode = knobs.gjkWave;   // 0 / 1 force a variant (tests, tuning)
-            const bool gjkWave = gjkWaveMode >= 0 ? gjkWaveMode != 0 : (spec ? last.gjkSpan <= gjkWaveMaxPairs : false);
-            if (gjkWave) L.launch(k_narrow_gjk_wave, dim3(std::min(pairBound, 16384u)), dim3(64), 0, st, sc, pairKeys.p, pairKeysS.p, wShape.p, hset, npPacked.p, npNormal.p, npPoints.p);
-            else {
+    L.launch(k_narrow, dim3(narrowBlocks), dim3(B), 0, st, pairBound, queueRegion, sc, pairKeys.p, pairKeysS.p, wShape.p, hset, npPacked.p, npNormal.p, npPoints.p, boxQueue.p,
+             reinterpret_cast<ulonglong2*>(tab[tabCur ^ 1].p), histCap, a.finishInNarrow ? shards.p : nullptr, pairBound, shards.p);
+    const bool statsInClip = spec && a.statsGridNext != nullptr;   // (a synchronous step: k_pair_finish did it)
+    L.launch(k_narrow_clip, dim3(kBoxQueues * (queueRegion / B) + (statsInClip ? 1u : 0u)), dim3(B), 0, st, queueRegion, sc, pairKeys.p, pairKeysS.p, wShape.p, boxQueue.p, npPacked.p, npNormal.p, npPoints.p, shards.p,
+             statsInClip ? shards.p : nullptr, sc, nc, a.statsBlocks, axisPartials.p, blockBounds.p, a.statsGridNext, a.statsCellCap, a.blockSkip && a.prepared ? shard.cbLive.p : nullptr);
+    // (a GJK-only kernel feeding a queue of hits to an EPA kernel was measured: no gain — the GJK half already needs ~250 VGPRs)
+    if (usesGjk) {
+        HIP_TRY(epaQueue.ensure(pairBound)); HIP_TRY(epaSimplex.ensure((size_t)pairBound * kEpaSimplexRows));
+        // few GJK pairs (vehicles on hull tiles, a handful of capsules): one WAVE per pair for GJK as well; many: GJK by lanes, EPA by waves
+        const int gjkWaveMode = knobs.gjkWave;   // 0 / 1 force a variant (tests, tuning)
+        const bool gjkWave = gjkWaveMode >= 0 ? gjkWaveMode != 0 : (spec ? last.gjkSpan <= gjkWaveMaxPairs : false);
+        if (gjkWave) L.launch(k_narrow_gjk_wave, dim3(std::min(pairBound, 16384u)), dim3(64), 0, st, sc, pairKeys.p, pairKeysS.p, wShape.p, hset, npPacked.p, npNormal.p, npPoints.p);
+        else {
             L.launch(k_narrow_gjk, dim3(divUp(pairBound, 64)), dim3(64), 0, st, sc, pairKeys.p, pairKeysS.p, wShape.p, hset, npPacked.p, npNormal.p, npPoints.p, epaQueue.p, epaSimplex.p, pairBound);
             L.launch(k_narrow_epa, dim3(std::min(pairBound, 8192u)), dim3(64), 0, st, sc, pairKeys.p, pairKeysS.p, wShape.p, hset, epaQueue.p, epaSimplex.p, pairBound, npPacked.p, npNormal.p, npPoints.p);
-            }
         }
-        if (heightmap) {
-            const HmOut hmOut{sc, pairBound, pairKeys.p, pairKeysS.p, npPacked.p, npNormal.p, npPoints.p};
-            L.launch(k_hm_contacts<true, false>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
-            L.launch(k_hm_contacts<true, true>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
-            L.launch(k_hm_write_stashed, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);   // (sized for all pairs: the terrain contacts are among them)
-            L.launch(k_hm_finish, dim3(1), dim3(1), 0, st, sc, pairBound);
-        }
-        HIP_TRY(scanPairs.run(L, reinterpret_cast<unsigned long long*>(npPacked.p), reinterpret_cast<unsigned long long*>(npScan.p), pairBound, st));
-        if (eventsEnabled) HIP_TRY(manIsNew.ensure(pairBound));
-#ifdef MI_DBG_KNOCKOUT
-        // development (tools/gpu_knockout.sh): k_emit_manifolds a first time with parts removed (g_dbgKnock bits 8-12) and its read-modify-write targets (per-body colour
-        // masks, the next history table, round-0 proposals, round flags) redirected to scratch; everything else it writes the real launch below writes again.
-        if (((knobs.knockout >> 8) & 0xFFu) && !L.dry && tabValid) {
-            static DBuf<unsigned long long> kUsed, kTop; static DBuf<HistSlot> kTab; static DBuf<uint32_t> kFlags; static hipEvent_t k0 = nullptr, k1 = nullptr;
-            if (!k0) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); }
-            if (knockPendingEmit) { HIP_TRY(hipEventSynchronize(k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess && timingLevel >= 2u) { knockMsSum += ms; ++knockLaunches; } knockPendingEmit = false; }
-            HIP_TRY(kUsed.ensure(bodyUsed.cap)); HIP_TRY(kTop.ensure(bodyTop.cap)); HIP_TRY(kTab.ensure(tab[tabCur ^ 1].cap)); HIP_TRY(kFlags.ensure(64));
-            HIP_TRY(hipMemsetAsync(kUsed.p, 0, kUsed.cap * 8, st)); HIP_TRY(hipMemsetAsync(kTab.p, 0, kTab.cap * sizeof(HistSlot), st)); HIP_TRY(hipMemsetAsync(kTop.p, 0, kTop.cap * 8, st));
-            static uint32_t word, zero = 0u; word = ((knobs.knockout >> 8) & 0xFFu) >= 0x80u ? 0u : (knobs.knockout & 0xFF00u);   // (0x8000: nothing removed = the harness itself)
-            HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &word, sizeof(word), 0, hipMemcpyHostToDevice, st));
-            (void)hipEventRecord(k0, st);
-            hipLaunchKernelGGL(k_emit_manifolds, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, nb, pairKeys.p, pairKeysS.p, npPacked.p, npScan.p, cEmit.p,
-                               manPair.p, manBodies.p, manInfo.p, colWork.p, color.p, tab[tabCur].p, tabMask[tabCur], kUsed.p, eventsEnabled ? manIsNew.p : nullptr, sc,
-                               heightmap ? make_float2(hmParams.restitution, hmParams.friction) : make_float2(0.f, 0.f), kTab.p, tabMask[tabCur ^ 1], manKept.p, histHint[hintOf[tabCur]].p, histHint[hintOf[tabCur ^ 1]].p /* (a fresh insertion may raise a hint: harmless, they only ever grow) */,
-                               seamOn ? seamId.p : nullptr, round0InEmit ? kTop.p + (nb + 1) : nullptr, kFlags.p);
-            (void)hipEventRecord(k1, st);
-            HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &zero, sizeof(zero), 0, hipMemcpyHostToDevice, st));
-            knockPendingEmit = true;
-        }
-#endif
-        L.launch(k_emit_manifolds, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, nb, pairKeys.p, pairKeysS.p, npPacked.p, npScan.p, cEmit.p,
-                                                        manPair.p, manBodies.p, manInfo.p, colWork.p, color.p,
-                                                        tabValid ? tab[tabCur].p : nullptr, tabMask[tabCur], bodyUsed.p, eventsEnabled ? manIsNew.p : nullptr, sc,
-                                                        heightmap ? make_float2(hmParams.restitution, hmParams.friction) : make_float2(0.f, 0.f),
-                                                        tab[tabCur ^ 1].p, tabMask[tabCur ^ 1], manKept.p, tabValid ? histHint[hintOf[tabCur]].p : nullptr, histHint[hintOf[tabCur ^ 1]].p,
-                                                        seamOn ? seamId.p : nullptr, round0InEmit ? bodyTop.p + (nb + 1) : nullptr, roundFlagsPtr());
     }
-    // ---------------------------------------------------------------------------------------------- triggers / force fields
-    std::vector<mi_event> triggerEvents;
-    uint32_t interPairBound = 0;
-    if (usesInteractions && spec) {
-        interPairBound = (uint32_t)std::min<size_t>(interKeys.cap, bound(last.numInterPairs, 1024));
-        HIP_TRY(interList.ensure(bound(last.numInteractions, 1024))); HIP_TRY(interSorted.ensure(interList.cap));
-        int rc = interactionsDevice(interPairBound); if (rc != MI_OK) return rc;
-    } else if (usesInteractions) { int rc = interactions(triggerEvents); if (rc != MI_OK) return rc; }
-    mark();  // 3
+    if (heightmap) {
+        const HmOut hmOut{sc, pairBound, pairKeys.p, pairKeysS.p, npPacked.p, npNormal.p, npPoints.p};
+        L.launch(k_hm_contacts<true, false>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
+        L.launch(k_hm_contacts<true, true>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
+        L.launch(k_hm_write_stashed, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);   // (sized for all pairs: the terrain contacts are among them)
+        L.launch(k_hm_finish, dim3(1), dim3(1), 0, st, sc, pairBound);
+    }
+    HIP_TRY(scanPairs.run(L, reinterpret_cast<unsigned long long*>(npPacked.p), reinterpret_cast<unsigned long long*>(npScan.p), pairBound, st));
+    if (eventsEnabled) HIP_TRY(manIsNew.ensure(pairBound));
+    const bool round0InEmit = emitsRound0();
+#ifdef MI_DBG_KNOCKOUT
+    { int rck = dbgKnockEmit(a); if (rck != MI_OK) return rck; }
+#endif
+    L.launch(k_emit_manifolds, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, nb, pairKeys.p, pairKeysS.p, npPacked.p, npScan.p, cEmit.p,
+                                                    manPair.p, manBodies.p, manInfo.p, colWork.p, color.p,
+                                                    tabValid ? tab[tabCur].p : nullptr, tabMask[tabCur], bodyUsed.p, eventsEnabled ? manIsNew.p : nullptr, sc,
+                                                    heightmap ? make_float2(hmParams.restitution, hmParams.friction) : make_float2(0.f, 0.f),
+                                                    tab[tabCur ^ 1].p, tabMask[tabCur ^ 1], manKept.p, tabValid ? histHint[hintOf[tabCur]].p : nullptr, histHint[hintOf[tabCur ^ 1]].p,
+                                                    a.seamOn ? seamId.p : nullptr, round0InEmit ? bodyTop.p + (nb + 1) : nullptr, roundFlagsPtr());
+    return MI_OK;
+}
+
+// Triggers / force fields: a speculative step orders and applies them on the device; a synchronous one brings the (few) interactions to the host.
+int mi_world::stageInteractions(StepAttempt& a) {
+    a.interPairBound = 0; a.triggerEvents.clear();
+    if (usesInteractions && a.spec) {
+        a.interPairBound = (uint32_t)std::min<size_t>(interKeys.cap, specBound(last.numInterPairs, 1024));
+        HIP_TRY(interList.ensure(specBound(last.numInteractions, 1024))); HIP_TRY(interSorted.ensure(interList.cap));
+        return interactionsDevice(a.interPairBound);
+    }
+    return usesInteractions ? interactions(a.triggerEvents) : MI_OK;
+}
+
+// Gravity, damping and the external forces into the solver's body arrays (+ the manifolds' spatial keys for the XCD-partitioned layout, in the same launch).
+int mi_world::stageForces(StepAttempt& a) {
+    const uint32_t nb = a.nb, B = 256;
+    hipStream_t st = stream;
     // (speculative step of a pile that gets the XCD-partitioned layout: the spatial keys of the manifolds ride in the same launch — k_forces_keys)
-    const uint32_t specNmBound = spec && pairBound ? std::min(pairBound, bound(last.numManifolds, 1024)) : 0u;
-    const bool keysWithForces = knobs.fuseKeys && specNmBound && xcdPlanFor(specNmBound) && !xcdSingleFor(specNmBound);
-    auto keysArgs = [&](uint32_t nm) {
-        return KeysArgs{nm, nb, sc, grid.p + gridCur, manBodies.p, bPos.p, bCogInvMass.p, sortKeys[0].p, sortVals[0].p, keyCount.p, shard.enabled ? shard.active.p : nullptr, manInfo.p, shards.p};
-    };
-    if (keysWithForces) {
+    const uint32_t specNmBound = a.spec && a.pairBound ? std::min(a.pairBound, specBound(last.numManifolds, 1024)) : 0u;
+    a.keysWithForces = knobs.fuseKeys && specNmBound && xcdPlanFor(specNmBound) && !xcdSingleFor(specNmBound);
+    const dim3 bodyBlocks(bodyGrid(a, divUp(nb + 1, B)));
+    if (a.keysWithForces) {
         HIP_TRY(sortKeys[0].ensure(specNmBound)); HIP_TRY(sortVals[0].ensure(specNmBound));
         const uint32_t keyBlocks = divUp(specNmBound, kKeyItems);
-        if (blockSkip) L.launch(k_forces_keys<true>, dim3(keyBlocks + bodyGrid(divUp(nb + 1, B))), dim3(B), 0, st, keyBlocks, forcesArgs(), keysArgs(specNmBound));
-        else L.launch(k_forces_keys<false>, dim3(keyBlocks + divUp(nb + 1, B)), dim3(B), 0, st, keyBlocks, forcesArgs(), keysArgs(specNmBound));
-    } else
-    if (blockSkip) L.launch(k_integrate_forces<true>, dim3(bodyGrid(divUp(nb + 1, B))), dim3(B), 0, st, forcesArgs());
-    else L.launch(k_integrate_forces<false>, dim3(divUp(nb + 1, B)), dim3(B), 0, st, forcesArgs());
-    mark();  // 4
-    // ---------------------------------------------------------------------------------------------- schedule
-    uint32_t nmBound = 0, conBound = 0;
-    if (pairBound) {
-        if (spec) { nmBound = std::min(pairBound, bound(last.numManifolds, 1024)); conBound = bound(last.numContacts, 4096); }
-        else { int rc = readScalars(); if (rc != MI_OK) return rc; nmBound = hs.numManifolds; conBound = hs.numContacts; }
-    }
-    uint32_t tilesCap = 0, ctCap = 0, eventCap = 0, xcdListCap = 0;
-    bool shardCounted = false;   // sharded world: this rank's manifolds / contacts are counted inside k_manifold_keys when that runs, else by k_shard_count
-    const bool xcdSingle = xcdSingleFor(nmBound);
-    const bool xcdPlan = xcdPlanFor(nmBound);
-    // converged rounds exit at once, but every enqueued round costs its launch slot (~4.6 us): a scene that replays its steps as graphs wants the same
-    // launches step after step (a multiple of 4), a large one exactly what the previous step needed plus the margin
-    // ... or, with the colouring tail (k_bin_hist runs whatever rounds are missing: colorTail in kernels.hpp), what the previous step needed + 1: the tail's rounds are slow (a device-wide barrier with cache write-back each), it is there for the
-    // step that outgrows its predecessor by more, not for every other step
+        L.launch(a.blockSkip ? k_forces_keys<true> : k_forces_keys<false>, dim3(keyBlocks + bodyBlocks.x), dim3(B), 0, st, keyBlocks, forcesArgs(a), keysArgs(specNmBound));
+    } else L.launch(a.blockSkip ? k_integrate_forces<true> : k_integrate_forces<false>, bodyBlocks, dim3(B), 0, st, forcesArgs(a));
+    return MI_OK;
+}
+// (evaluated where it is launched: buffers may still be (re)allocated on the way there)
+ForcesArgs mi_world::forcesArgs(const StepAttempt& a) {
+    return ForcesArgs{bPos.p, bRot.p, bCogInvMass.p, bInvI.p, bParams.p, bLinVel.p, bAngVel.p, usesInteractions ? bForceStep.p : bForce.p, bTorque.p,
+                      gPos.p, gInvI.p, gVel.p, gVelL.p, bodyOwner.p, shard.enabled ? shard.active.p : nullptr, a.blockSkip ? shard.blockLive.p : nullptr, a.nb, a.dt, {globalForce.x, globalForce.y, globalForce.z}, 0u};
+}
+KeysArgs mi_world::keysArgs(uint32_t nm) {
+    return KeysArgs{nm, (uint32_t)bodies.size(), scalarsPtr(), grid.p + gridCur, manBodies.p, bPos.p, bCogInvMass.p, sortKeys[0].p, sortVals[0].p, keyCount.p, shard.enabled ? shard.active.p : nullptr, manInfo.p, shards.p};
+}
+
+// Colouring rounds a step enqueues before k_bin_hist.
+// Converged rounds exit at once, but every enqueued round costs its launch slot (~4.6 us): a scene that replays its steps as graphs wants the same
+// launches step after step (a multiple of 4), a large one exactly what the previous step needed plus the margin
+// ... or, with the colouring tail (k_bin_hist runs whatever rounds are missing: colorTail in kernels.hpp), what the previous step needed + 1: the tail's rounds are slow (a device-wide barrier with cache write-back each), it is there for the
+// step that outgrows its predecessor by more, not for every other step
+uint32_t mi_world::colorBatchFor(const StepAttempt& a, bool colorTailOn) {
     constexpr uint32_t kColorMargin = 3, kColorTailMargin = 1;   // extra rounds enqueued beyond the previous step's count, without / with the tail
-    if (spec && colorTailHold) --colorTailHold;
-    const bool colorTailOn = spec && knobs.colorTail && !colorTailHold;   // (colorTailHold: the tail's device-wide barrier timed out recently — a margin of enqueued rounds instead, like the other fault paths)
-    if (graphStep && colorTailOn) {   // a scene that replays its steps as graphs: the same launches step after step — the count only moves when the need outgrows it or falls 2 below
+    if (a.graphStep && colorTailOn) {   // a scene that replays its steps as graphs: the same launches step after step — the count only moves when the need outgrows it or falls 2 below
         const uint32_t need = std::min<uint32_t>(96u, last.colorRounds + kColorTailMargin);
         if (need > colorBatchSticky || need + 2u < colorBatchSticky) colorBatchSticky = need;
     }
-    uint32_t colorBatch = !spec ? 20u : graphStep ? (colorTailOn ? colorBatchSticky : std::min<uint32_t>(96u, (last.colorRounds + std::max(kColorMargin, last.colorRounds / 4u) + 3u) & ~3u))
-                                      : colorTailOn ? std::min<uint32_t>(96u, last.colorRounds + kColorTailMargin)
-                                                  : std::min<uint32_t>(96u, last.colorRounds + std::max(kColorMargin, last.colorRounds / 4u));
+    uint32_t colorBatch = !a.spec ? 20u : a.graphStep ? (colorTailOn ? colorBatchSticky : std::min<uint32_t>(96u, (last.colorRounds + std::max(kColorMargin, last.colorRounds / 4u) + 3u) & ~3u))
+                                        : colorTailOn ? std::min<uint32_t>(96u, last.colorRounds + kColorTailMargin)
+                                                      : std::min<uint32_t>(96u, last.colorRounds + std::max(kColorMargin, last.colorRounds / 4u));
     if (colorTailOn && knobs.colorRoundsMax) colorBatch = std::min(colorBatch, knobs.colorRoundsMax);
+    return colorBatch;
+}
+
+// Schedule: bounds of the manifolds / contacts, spatial placement for the XCD layout, graph colouring, colour bins -> tiles, the next step's colour history, collision events.
+int mi_world::stageSchedule(StepAttempt& a) {
+    const uint32_t nb = a.nb, nc = a.nc, B = 256, pairBound = a.pairBound;
+    StepScalars* sc = scalarsPtr(); hipStream_t st = stream;
+    const bool spec = a.spec, seamOn = a.seamOn, round0InEmit = emitsRound0();
+    uint32_t nmBound = 0, conBound = 0;
+    if (pairBound) {
+        if (spec) { nmBound = std::min(pairBound, specBound(last.numManifolds, 1024)); conBound = specBound(last.numContacts, 4096); }
+        else { int rc = readScalars(); if (rc != MI_OK) return rc; nmBound = hs.numManifolds; conBound = hs.numContacts; }
+    }
+    a.nmBound = nmBound; a.conBound = conBound;
+    a.tilesCap = a.ctCap = a.eventCap = a.xcdListCap = 0; a.shardCounted = false;
+    const bool xcdSingle = a.xcdSingle = xcdSingleFor(nmBound), xcdPlan = a.xcdPlan = xcdPlanFor(nmBound);
+    if (spec && colorTailHold) --colorTailHold;
+    const bool colorTailOn = spec && knobs.colorTail && !colorTailHold;   // (colorTailHold: the tail's device-wide barrier timed out recently — a margin of enqueued rounds instead, like the other fault paths)
+    uint32_t colorBatch = colorBatchFor(a, colorTailOn);
     if (nmBound) {
-        tilesCap = divUp(nmBound, 64) + kSchedBins + 8; ctCap = divUp(conBound, 64) + 4 * kSchedBins + 8;
+        uint32_t tilesCap = divUp(nmBound, 64) + kSchedBins + 8, ctCap = divUp(conBound, 64) + 4 * kSchedBins + 8, xcdListCap = 0;
         // the sequential (overflow) bin's tiles take 4 contact-tiles each whatever their contact counts.  A synchronous step must hold whatever the colouring puts there — in the
         // caller's order that is EVERY manifold, and a heap of bodies spawned into one another fills it with one-contact manifolds (tools/gpu_fuzz.py: MI_ERR_CAPACITY out of a
         // synchronous step) —; a speculative step with anything in that bin is void anyway and sized for none.
@@ -570,11 +686,12 @@ enqueue_section:
             HIP_TRY(sortKeys[0].ensure(nmBound)); for (int k = 0; k < 2; ++k) HIP_TRY(sortVals[k].ensure(nmBound));
             HIP_TRY(xcdTiles.ensure((size_t)8 * xcdListCap)); HIP_TRY(xcdInfo.ensure((size_t)8 * xcdListCap));
             if (!xcdSingle) {   // (one XCD: nothing to keep apart, the emission order will do)
-                if (!keysWithForces) L.launch(k_manifold_keys, dim3(divUp(nmBound, kKeyItems)), dim3(256), 0, st, keysArgs(nmBound));
-                shardCounted = shard.enabled;
+                if (!a.keysWithForces) L.launch(k_manifold_keys, dim3(divUp(nmBound, kKeyItems)), dim3(256), 0, st, keysArgs(nmBound));
+                a.shardCounted = shard.enabled;
                 L.launch(k_manifold_place, dim3(divUp(nmBound, kKeyItems)), dim3(256), 0, st, nmBound, sc, sortKeys[0].p, sortVals[0].p, keyCount.p, sortVals[1].p);
             }
         }
+        a.tilesCap = tilesCap; a.ctCap = ctCap; a.xcdListCap = xcdListCap;
         const uint32_t* perm = xcdPlan && !xcdSingle ? sortVals[1].p : nullptr;
         unsigned long long* top[2] = {bodyTop.p, bodyTop.p + (nb + 1)};
         if (debugOrderPending) { int rc = applyDebugOrder(); if (rc != MI_OK) return rc; }   // (synchronous step: hs holds this step's counts) every manifold -> the sequential colour
@@ -604,57 +721,66 @@ enqueue_section:
         // the kept manifolds' old colours: together no valid colouring); the next free step colours them afresh, as the oracle does
         if (debugOrderPending) L.launch(k_history_overflow, dim3(divUp(tabMask[tabCur ^ 1] + 1u, B)), dim3(B), 0, st, tab[tabCur ^ 1].p, tabMask[tabCur ^ 1]);
         if (seamOn) L.launch(k_seam_stats, dim3(divUp(nmBound, B)), dim3(B), 0, st, sc, colWork.p, color.p, shard.enabled ? shard.active.p : nullptr);
-        {   // colour history for the next step, into the OTHER table (it becomes current only if this step turns out valid)
-            const int nt = tabCur ^ 1;   // sized and cleared before k_emit_manifolds (narrow phase stage)
-            if (eventsEnabled) {   // begins: manifolds not in the previous table; ends: previous pairs not in this step's table
-                eventCap = nmBound + (tabValid ? last.numManifolds : 0u) + 1024u;
-                HIP_TRY(devEvents.ensure(eventCap));
-                L.launch(k_events_begin, dim3(divUp(nmBound, B)), dim3(B), 0, st, nc, eventCap, sc, manIsNew.p, manPair.p, manBodies.p, manInfo.p, pairKeys.p, pairKeysS.p,
-                                                               npNormal.p, npPoints.p, gPos.p, gVel.p, devEvents.p);
-                if (tabValid) L.launch(k_events_end, dim3(divUp(tabMask[tabCur] + 1u, B)), dim3(B), 0, st, eventCap, sc, tab[tabCur].p, tabMask[tabCur], tab[nt].p, tabMask[nt], devEvents.p, histHint[hintOf[nt]].p);
-            }
+        if (eventsEnabled) {   // begins: manifolds not in the previous table; ends: previous pairs not in this step's table
+            const int nt = tabCur ^ 1;   // colour history for the next step, the OTHER table (sized and cleared before k_emit_manifolds; it becomes current only if this step turns out valid)
+            const uint32_t eventCap = a.eventCap = nmBound + (tabValid ? last.numManifolds : 0u) + 1024u;
+            HIP_TRY(devEvents.ensure(eventCap));
+            L.launch(k_events_begin, dim3(divUp(nmBound, B)), dim3(B), 0, st, nc, eventCap, sc, manIsNew.p, manPair.p, manBodies.p, manInfo.p, pairKeys.p, pairKeysS.p,
+                                                           npNormal.p, npPoints.p, gPos.p, gVel.p, devEvents.p);
+            if (tabValid) L.launch(k_events_end, dim3(divUp(tabMask[tabCur] + 1u, B)), dim3(B), 0, st, eventCap, sc, tab[tabCur].p, tabMask[tabCur], tab[nt].p, tabMask[nt], devEvents.p, histHint[hintOf[nt]].p);
         }
-        if (!spec) {
-            mirrorSchedule();
-            const BinInfo& ob = bins[kSchedBins - 1];
-            if (debugOrderPending && debugOrderLevelled) {
-                if (ob.count) return fail(MI_ERR_DEVICE, "mi_debug_set_solve_dataflow: the levelled schedule put a manifold into the sequential bin");
-            } else
-            if (debugOrderPending) {   // the caller's order (applyDebugOrder left every manifold's rank in debugRank)
-                if (ob.count != hs.numManifolds) return fail(MI_ERR_DEVICE, "mi_debug_set_solve_order: schedule did not put every manifold into the sequential bin");
-                if (ob.count) {
-                    std::vector<uint32_t> ord(ob.count);
-                    for (uint32_t m = 0; m < ob.count; ++m) ord[debugRank[m]] = m;
-                    HIP_TRY(hipMemcpyAsync(order.p + ob.slotStart, ord.data(), ob.count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                    HIP_TRY(hipStreamSynchronize(st));
-                }
-            } else
-            if (ob.count > 1) {   // overflow colour: sequential solve in ascending pair-key order
-                HIP_TRY(L.memcpyAsync(orderTmp.p + ob.slotStart, order.p + ob.slotStart, ob.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-                L.launch(k_sort_overflow, dim3(1), dim3(256), 0, st, ob.slotStart, ob.count, manPair.p, hs.partitioned ? pairKeysS.p : pairKeys.p, orderTmp.p, order.p);
-            }
-        }
+        if (!spec) { int rc = orderSequentialBin(); if (rc != MI_OK) return rc; }
     }
     if (debugOrderPending && !nmBound && !debugOrder.empty()) return fail(MI_ERR_INVALID_ARGUMENT, "mi_debug_set_solve_order: the step found no contact manifold, the list holds " + std::to_string(debugOrder.size()));
-    mark();  // 5
-    // ---------------------------------------------------------------------------------------------- constraints
-    const uint32_t tilesLaunch = spec ? tilesCap : totalTiles;   // sync mode knows the exact tile count (mirrorSchedule)
-    const bool useFlow = flowSolver && !launchFallbackSteps && (!debugOrderPending || debugOrderLevelled) && (spec || bins[kSchedBins - 1].count == 0 || !nmBound);   // the overflow colour needs the sequential kernel
-    const bool fused = useFlow && joints.allInIslands() && !exactSeamStep;   // joints of all sweeps inside the dataflow launch
-    // slots (tiles) one persistent workgroup must hold: exact in a synchronous step, from the previous step's lists (+ slack) in a speculative one
-    auto persistSlots = [&](uint32_t tiles, bool xcd, bool speculative) -> uint32_t {
-        if (!xcd) return divUp(tiles, persistWaves);
-        uint32_t longest = 0;
-        if (speculative) longest = (haveXcdEstimate && lastXcdSingle == xcdSingle) ? lastXcdMax + lastXcdMax / 8u + 16u : xcdSingle ? tiles + 16u : divUp(tiles, 8) + 64u;
-        else for (uint32_t x = 0; x < 8u; ++x) { uint32_t n = 0; for (uint32_t bn = 0; bn < kSchedBins; ++bn) n += tileOwnerCount(x, divUp(bins[bn].count, 64), bn, xcdSingle ? 1u : 0u); longest = std::max(longest, n); }
-        return divUp(std::max(longest, 1u), persistWaves / 8u);
-    };
+    return MI_OK;
+}
+// Synchronous step, schedule known (hs): the host mirror of it, and the slot order of the sequential (overflow) bin.
+int mi_world::orderSequentialBin() {
+    hipStream_t st = stream;
+    mirrorSchedule();
+    const BinInfo& ob = bins[kSchedBins - 1];
+    if (debugOrderPending && debugOrderLevelled) {
+        if (ob.count) return fail(MI_ERR_DEVICE, "mi_debug_set_solve_dataflow: the levelled schedule put a manifold into the sequential bin");
+    } else
+    if (debugOrderPending) {   // the caller's order (applyDebugOrder left every manifold's rank in debugRank)
+        if (ob.count != hs.numManifolds) return fail(MI_ERR_DEVICE, "mi_debug_set_solve_order: schedule did not put every manifold into the sequential bin");
+        if (ob.count) {
+            std::vector<uint32_t> ord(ob.count);
+            for (uint32_t m = 0; m < ob.count; ++m) ord[debugRank[m]] = m;
+            HIP_TRY(hipMemcpyAsync(order.p + ob.slotStart, ord.data(), ob.count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+    } else
+    if (ob.count > 1) {   // overflow colour: sequential solve in ascending pair-key order
+        HIP_TRY(L.memcpyAsync(orderTmp.p + ob.slotStart, order.p + ob.slotStart, ob.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        L.launch(k_sort_overflow, dim3(1), dim3(256), 0, st, ob.slotStart, ob.count, manPair.p, hs.partitioned ? pairKeysS.p : pairKeys.p, orderTmp.p, order.p);
+    }
+    return MI_OK;
+}
+
+// slots (tiles) one persistent workgroup must hold: exact in a synchronous step, from the previous step's lists (+ slack) in a speculative one
+uint32_t mi_world::persistSlots(const StepAttempt& a) {
+    if (!a.xcdPlan) return divUp(a.tilesLaunch, persistWaves);
+    uint32_t longest = 0;
+    if (a.spec) longest = (haveXcdEstimate && lastXcdSingle == a.xcdSingle) ? lastXcdMax + lastXcdMax / 8u + 16u : a.xcdSingle ? a.tilesLaunch + 16u : divUp(a.tilesLaunch, 8) + 64u;
+    else for (uint32_t x = 0; x < 8u; ++x) { uint32_t n = 0; for (uint32_t bn = 0; bn < kSchedBins; ++bn) n += tileOwnerCount(x, divUp(bins[bn].count, 64), bn, a.xcdSingle ? 1u : 0u); longest = std::max(longest, n); }
+    return divUp(std::max(longest, 1u), persistWaves / 8u);
+}
+
+// Constraints: which solver this step gets, and the contact rows / slot data (k_contact_init) and joint rows it starts from.
+int mi_world::stageConstraintInit(StepAttempt& a) {
+    const uint32_t nb = a.nb, B = 256, nmBound = a.nmBound, tilesCap = a.tilesCap, ctCap = a.ctCap, xcdListCap = a.xcdListCap;
+    StepScalars* sc = scalarsPtr(); hipStream_t st = stream;
+    const bool xcdPlan = a.xcdPlan;
+    const uint32_t tilesLaunch = a.tilesLaunch = a.spec ? tilesCap : totalTiles;   // sync mode knows the exact tile count (mirrorSchedule)
+    a.useFlow = flowSolver && !launchFallbackSteps && (!debugOrderPending || debugOrderLevelled) && (a.spec || bins[kSchedBins - 1].count == 0 || !nmBound);   // the overflow colour needs the sequential kernel
+    const bool fused = a.fused = a.useFlow && joints.allInIslands() && !exactSeamStep();   // joints of all sweeps inside the dataflow launch
     // the persistent kernel keeps the accumulated impulses in LDS while they fit: k_contact_init then need not write the impulse granules
-    const bool persistPlan = !fused && useFlow && persistSolver && joints.count() == 0 && tilesLaunch && !exactSeamStep;
-    const uint32_t persistMaxSlots = persistPlan ? persistSlots(tilesLaunch, xcdPlan, spec) : 0u;
+    a.persistPlan = !fused && a.useFlow && persistSolver && joints.count() == 0 && tilesLaunch && !exactSeamStep();
+    a.persistMaxSlots = a.persistPlan ? persistSlots(a) : 0u;
     const bool privateIslands = fused && privateIslandsEnabled && !shard.enabled && joints.dBodyIsland && nmBound && tilesLaunch;
-    const IslandPrivate islandPriv = privateIslands ? joints.islandPrivate() : IslandPrivate{nullptr, nullptr, nullptr, nullptr, nullptr};
-    const bool impNeeded = !(persistPlan && persistImpLds && persistMaxSlots * (4u * 512u + 24u) <= 38u * 1024u);
+    const IslandPrivate islandPriv = a.islandPriv = privateIslands ? joints.islandPrivate() : IslandPrivate{nullptr, nullptr, nullptr, nullptr, nullptr};
+    const bool impNeeded = !(a.persistPlan && persistImpLds && a.persistMaxSlots * (4u * 512u + 24u) <= 38u * 1024u);
     if (nmBound) {
         HIP_TRY(slotMeta.ensure((size_t)tilesCap * 64)); HIP_TRY(slotNormal.ensure((size_t)tilesCap * 64)); HIP_TRY(slotMass.ensure((size_t)tilesCap * 64));
         HIP_TRY(rows.ensure((size_t)ctCap * kRows * 64)); HIP_TRY(imp.ensure((size_t)ctCap * 64));
@@ -663,222 +789,154 @@ enqueue_section:
             L.launch(k_island_classify, dim3(divUp(nmBound, B)), dim3(B), 0, st, sc, colWork.p, color.p, islandPriv);
         }
         if (tilesLaunch)
-            L.launch(k_contact_init, dim3(xcdPlan ? 8u * xcdListCap : tilesLaunch), dim3(64), 0, st, sc, nb, dt, xcdPlan ? xcdInfo.p : tileInfo.p, order.p, manPair.p, manBodies.p, manInfo.p, npNormal.p, npPoints.p,
+            L.launch(k_contact_init, dim3(xcdPlan ? 8u * xcdListCap : tilesLaunch), dim3(64), 0, st, sc, nb, a.dt, xcdPlan ? xcdInfo.p : tileInfo.p, order.p, manPair.p, manBodies.p, manInfo.p, npNormal.p, npPoints.p,
                                                       gPos.p, gInvI.p, xcdPlan ? gVelL.p : gVel.p /* same content here; the cached copy */, color.p, bodyUsed.p, fused ? joints.dBodyJ : nullptr, rows.p, impNeeded ? imp.p : nullptr, slotMeta.p, slotNormal.p, slotMass.p,
                                                       xcdPlan ? reinterpret_cast<uint8_t*>(bodyOwner.p) : nullptr, xcdListCap, xcdPlan ? 8u * xcdListCap : tilesCap, islandPriv);
     }
-    int rc = joints.initialize(*this, dt, st);   // (through L)
+    return joints.initialize(*this, a.dt, st);   // (through L)
+}
+
+// The solve stage: one of four solver paths (stepInternal's ladder walks down them), then a sharded world's counts.
+int mi_world::stageSolve(StepAttempt& a) {
+    const bool persist = !a.fused && a.persistPlan && a.persistMaxSlots * 24u <= 38u * 1024u;
+    a.solveAttached = false; a.mainContacts = 0;
+    if (a.attached && !persist) (void)hipEventRecord(ev[EV_SOLVE_BEGIN], stream);   // another solver path (several launches): classic recorded events
+    usedFlow = a.useFlow; usedPersist = false; usedFused = a.fused; usedXcd = false; usedXcdSingle = false;
+    int rc = a.fused ? solveFused(a) : persist ? solvePersistent(a) : a.useFlow ? solveFlow(a) : solvePerColour(a);
     if (rc != MI_OK) return rc;
-    mark();  // 6
-    bool solveAttached = false;
-    const bool willPersist = (!fused && persistPlan && persistMaxSlots * 24u <= 38u * 1024u);
-    if (attached && !willPersist) (void)hipEventRecord(ev[6], st);   // another solver path (several launches): classic recorded events
-    const uint32_t iters = settings.num_rigid_solver_iterations;
-    usedFlow = useFlow; usedPersist = false; usedFused = fused; usedXcd = false; usedXcdSingle = false;
-    uint64_t mainContacts = 0;
-    if (fused) {
-        // contacts and joint islands of every sweep in one launch (k_solve_flow_islands)
-        const uint64_t per = (uint64_t)joints.numIslands + tilesLaunch;
-        const uint32_t perLaunch = per * iters < 0x7FFFFFFFull ? iters : 1u;
-        solveLaunches = (iters + perLaunch - 1) / perLaunch;
-        BodyView bv{gPos.p, gInvI.p, gVel.p, bRot.p, bCogInvMass.p, shard.enabled ? shard.active.p : nullptr};
-        const IslandUpd iu{joints.distance.dUpd, joints.ball.dUpd, joints.fixed.dUpd, joints.hinge.dUpd, joints.cone.dUpd, joints.slider.dUpd};
-        const IslandAcc ia{joints.hinge.dAcc, joints.cone.dAcc, joints.slider.dAcc};
-        for (uint32_t it = 0; it < iters; it += perLaunch) {
-            if (profileSolve) {
-                size_t e = 2 * (size_t)profLaunches;
-                while (profEvents.size() < e + 2) { hipEvent_t ev_; HIP_TRY(hipEventCreate(&ev_)); profEvents.push_back(ev_); }
-                (void)hipEventRecord(profEvents[e], st);
-            }
-            L.launch(k_solve_flow_islands, dim3((uint32_t)(per * perLaunch)), dim3(64), 0, st, it, perLaunch, joints.numIslands, joints.dIslands, joints.dSteps, joints.dIslandBodies, iu, ia, bv, bodyUsed.p,
-                                                                                   tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, sc, islandPriv, iters);
-            if (profileSolve) { (void)hipEventRecord(profEvents[2 * (size_t)profLaunches + 1], st); ++profLaunches; }
-        }
-    } else if (persistPlan && persistMaxSlots * 24u <= 38u * 1024u) {
-        // persistent waves: one workgroup per SIMD owns its tiles through all sweeps, impulses (and, while they fit, the constant slot data) in LDS (k_contact_solve_persist)
-        const uint32_t maxSlots = persistMaxSlots;
-        const bool metaLds = persistMetaLds && maxSlots * (64u * 40u + 4u * 512u + 24u) <= 38u * 1024u;
-        usedXcd = xcdPlan; usedXcdSingle = xcdPlan && xcdSingle;
-        const uint32_t xcdFault = xcdFaultTest && usedXcd && !xcdFaultFired ? 1u : 0u;   // tests: one workgroup reports a placement mismatch once
-        if (xcdFault) xcdFaultFired = true;
-        solveLaunches = 1; usedPersist = true;
-        if (profileSolve) {
-            size_t e = 2 * (size_t)profLaunches;
-            while (profEvents.size() < e + 2) { hipEvent_t ev_; HIP_TRY(hipEventCreate(&ev_)); profEvents.push_back(ev_); }
-            (void)hipEventRecord(profEvents[e], st);
-        }
-        const bool impLds = persistImpLds && maxSlots * (4u * 512u + 24u) <= 38u * 1024u;   // beyond that the impulses travel as granules in `imp` (no size limit)
-        const uint32_t ldsMeta = maxSlots * (64u * 40u + 4u * 512u + 24u) + 16u, ldsImp = maxSlots * (4u * 512u + 24u) + 16u, ldsDesc = maxSlots * 24u + 16u;
-#define MI_PERSIST_ARGS iters, maxSlots, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, gVel.p, sc, xcdTiles.p, xcdListCap, bodyOwner.p, gVelL.p, slotMeta.p, imp.p, xcdFault, knobs.persistResident ? 1u : 0u
-        // the solve stage IS this launch: its timing events ride on the dispatch (when this path is not taken they are recorded below)
-        hipEvent_t e6 = attached && timingLevel ? ev[6] : nullptr, e7 = attached && timingLevel ? ev[7] : nullptr;
-        solveAttached = attached;
-#define MI_PERSIST_LAUNCH(A, B_, C_, LDS) do { if (attached) hipExtLaunchKernelGGL((k_contact_solve_persist<A, B_, C_>), dim3(persistWaves), dim3(64), LDS, st, e6, e7, 0, MI_PERSIST_ARGS); \
-                                              else L.launch(k_contact_solve_persist<A, B_, C_>, dim3(persistWaves), dim3(64), LDS, st, MI_PERSIST_ARGS); } while (0)
+    if (shard.enabled && a.pairBound && !a.shardCounted) L.launch(k_shard_count, dim3(divUp(a.nmBound ? a.nmBound : 1u, 256)), dim3(256), 0, stream, a.nb, manBodies.p, manInfo.p, bCogInvMass.p, shard.active.p, scalarsPtr(), shards.p);
+    return MI_OK;
+}
+// contacts and joint islands of every sweep in one launch (k_solve_flow_islands)
+int mi_world::solveFused(StepAttempt& a) {
+    const uint32_t iters = a.settings.num_rigid_solver_iterations;
+    const uint64_t per = (uint64_t)joints.numIslands + a.tilesLaunch;
+    const uint32_t perLaunch = per * iters < 0x7FFFFFFFull ? iters : 1u;
+    solveLaunches = (iters + perLaunch - 1) / perLaunch;
+    BodyView bv{gPos.p, gInvI.p, gVel.p, bRot.p, bCogInvMass.p, shard.enabled ? shard.active.p : nullptr};
+    const IslandUpd iu{joints.distance.dUpd, joints.ball.dUpd, joints.fixed.dUpd, joints.hinge.dUpd, joints.cone.dUpd, joints.slider.dUpd};
+    const IslandAcc ia{joints.hinge.dAcc, joints.cone.dAcc, joints.slider.dAcc};
+    for (uint32_t it = 0; it < iters; it += perLaunch) {
+        int rc = profileBegin(); if (rc != MI_OK) return rc;
+        L.launch(k_solve_flow_islands, dim3((uint32_t)(per * perLaunch)), dim3(64), 0, stream, it, perLaunch, joints.numIslands, joints.dIslands, joints.dSteps, joints.dIslandBodies, iu, ia, bv, bodyUsed.p,
+                                                                               tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, scalarsPtr(), a.islandPriv, iters);
+        profileEnd();
+    }
+    return MI_OK;
+}
+// persistent waves: one workgroup per SIMD owns its tiles through all sweeps, impulses (and, while they fit, the constant slot data) in LDS (k_contact_solve_persist)
+int mi_world::solvePersistent(StepAttempt& a) {
+    const uint32_t iters = a.settings.num_rigid_solver_iterations, maxSlots = a.persistMaxSlots;
+    const bool metaLds = persistMetaLds && maxSlots * (64u * 40u + 4u * 512u + 24u) <= 38u * 1024u;
+    usedXcd = a.xcdPlan; usedXcdSingle = a.xcdPlan && a.xcdSingle;
+    const uint32_t xcdFault = xcdFaultTest && usedXcd && !xcdFaultFired ? 1u : 0u;   // tests: one workgroup reports a placement mismatch once
+    if (xcdFault) xcdFaultFired = true;
+    solveLaunches = 1; usedPersist = true;
+    int rc = profileBegin(); if (rc != MI_OK) return rc;
+    const bool impLds = persistImpLds && maxSlots * (4u * 512u + 24u) <= 38u * 1024u;   // beyond that the impulses travel as granules in `imp` (no size limit)
+    const uint32_t ldsMeta = maxSlots * (64u * 40u + 4u * 512u + 24u) + 16u, ldsImp = maxSlots * (4u * 512u + 24u) + 16u, ldsDesc = maxSlots * 24u + 16u;
+    // the solve stage IS this launch: its timing events ride on the dispatch (when this path is not taken they are recorded in stageSolve / enqueueStep)
+    hipEvent_t e6 = a.attached && timingLevel ? ev[EV_SOLVE_BEGIN] : nullptr, e7 = a.attached && timingLevel ? ev[EV_SOLVE_END] : nullptr;
+    a.solveAttached = a.attached;
 #ifdef MI_DBG_KNOCKOUT
-        // development (tools/gpu_knockout.sh): the same launch FIRST on scratch copies of the velocity arrays with parts of the tile visit removed (g_dbgKnock, kernels.hpp);
-        // the real launch below starts from the untouched arrays and the step goes on from ITS results.  Device time of the knock-out launch -> knockMsSum / knockLaunches.
-        if ((knobs.knockout & 0xFFu) && usedXcd && metaLds && impLds && !L.dry) {
-            static DBuf<float4> kv, kvl; static hipEvent_t k0 = nullptr, k1 = nullptr;
-            if (!k0) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); kv.flags = gVel.flags; }
-            if (knockPending) { HIP_TRY(hipEventSynchronize(k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess && timingLevel >= 2u) { knockMsSum += ms; ++knockLaunches; } knockPending = false; }   // (counted while the caller times steps: mi_world_set_stage_timing)
-            HIP_TRY(kv.ensure(gVel.cap)); HIP_TRY(kvl.ensure(gVelL.cap));
-            HIP_TRY(hipMemcpyAsync(kv.p, gVel.p, gVel.cap * sizeof(float4), hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(kvl.p, gVelL.p, gVelL.cap * sizeof(float4), hipMemcpyDeviceToDevice, st));
-            static uint32_t word, zero = 0u; word = (knobs.knockout & 0xFFu) >= 8u ? 0u : (knobs.knockout & 0xFFu);   // (8: the unmodified kernel through the harness — what the harness itself costs)
-            HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &word, sizeof(word), 0, hipMemcpyHostToDevice, st));
-#ifdef MI_DBG_TIMELINE
-            static unsigned long long* tlKnock; tlKnock = dbgTimelineBuf ? dbgTimelineBuf + (size_t)persistWaves * 256 * 8 : nullptr;
-            if (dbgTimelineBuf) HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgTimeline), &tlKnock, sizeof(tlKnock), 0, hipMemcpyHostToDevice, st));
+    if (usedXcd && metaLds && impLds) { int rck = dbgKnockSolve(a, ldsMeta); if (rck != MI_OK) return rck; }
 #endif
-            (void)hipEventRecord(k0, st);
-            hipLaunchKernelGGL((k_contact_solve_persist<true, true, true>), dim3(persistWaves), dim3(64), ldsMeta, st,
-                               iters, maxSlots, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, kv.p, sc, xcdTiles.p, xcdListCap, bodyOwner.p, kvl.p, slotMeta.p, imp.p, 0u, knobs.persistResident ? 1u : 0u);
-            (void)hipEventRecord(k1, st);
-            HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &zero, sizeof(zero), 0, hipMemcpyHostToDevice, st));
-#ifdef MI_DBG_TIMELINE
-            if (dbgTimelineBuf) HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgTimeline), &dbgTimelineBuf, sizeof(dbgTimelineBuf), 0, hipMemcpyHostToDevice, st));
-#endif
-            knockPending = true;
-        }
-#endif
-        if (usedXcd) {
-            if (metaLds && impLds) MI_PERSIST_LAUNCH(true, true, true, ldsMeta);
-            else if (impLds) MI_PERSIST_LAUNCH(false, true, true, ldsImp);
-            else MI_PERSIST_LAUNCH(false, true, false, ldsDesc);
-        } else {
-            if (metaLds && impLds) MI_PERSIST_LAUNCH(true, false, true, ldsMeta);
-            else if (impLds) MI_PERSIST_LAUNCH(false, false, true, ldsImp);
-            else MI_PERSIST_LAUNCH(false, false, false, ldsDesc);
-        }
-#undef MI_PERSIST_LAUNCH
-#undef MI_PERSIST_ARGS
-        if (profileSolve) { (void)hipEventRecord(profEvents[2 * (size_t)profLaunches + 1], st); ++profLaunches; }
-    } else if (useFlow) {
-        // no joints between the sweeps -> all sweeps in one launch; otherwise one launch per sweep (joints run in between)
-        const uint32_t perLaunch = joints.count() == 0 && !exactSeamStep && (uint64_t)std::max(tilesLaunch, 1u) * iters < 0x7FFFFFFFull ? iters : 1u;
-        solveLaunches = tilesLaunch ? (iters + perLaunch - 1) / perLaunch : 0;
-        for (uint32_t it = 0; it < iters; it += perLaunch) {
-            if (perLaunch == 1) joints.solveIteration(*this, st);   // distance, ball, fixed, hinge, cone-twist, slider (constraints.cpp:3764-3769)
-            if (!tilesLaunch) { if (exactSeamStep) { int rcx = shardSweepExchange(it); if (rcx != MI_OK) return rcx; } continue; }
-            if (profileSolve) {
-                size_t e = 2 * (size_t)profLaunches;
-                while (profEvents.size() < e + 2) { hipEvent_t ev_; HIP_TRY(hipEventCreate(&ev_)); profEvents.push_back(ev_); }
-                (void)hipEventRecord(profEvents[e], st);
-            }
-            L.launch(k_contact_solve_flow, dim3(tilesLaunch * perLaunch), dim3(64), 0, st, it, perLaunch, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p, sc);
-            if (profileSolve) { (void)hipEventRecord(profEvents[2 * (size_t)profLaunches + 1], st); ++profLaunches; }
-            if (exactSeamStep) { int rcx = shardSweepExchange(it); if (rcx != MI_OK) return rcx; }   // exact seam: the owners' velocities of the shared bodies replace the ghost copies
-        }
-    } else {
-        // one launch per colour per sweep (MI_SOLVER=launch, or an overflow colour is present); synchronous mode only
-        auto colorCount = [&](uint32_t c) { return bins[4 * c].count + bins[4 * c + 1].count + bins[4 * c + 2].count + bins[4 * c + 3].count; };
-        // colours [tailStart, tailEnd) are small (<= 512 manifolds each, a suffix of the used colours): one launch for all of them
-        if (!nmBound) { numColorsUsed = 0; for (BinInfo& b : bins) b.count = 0; }   // no manifolds this step: the mirrored schedule is the previous step's
-        uint32_t tailEnd = std::min(numColorsUsed, kOverflowColor), tailStart = tailEnd;
-        while (tailStart > 0 && colorCount(tailStart - 1) <= 512u) --tailStart;
-        if (tailEnd - tailStart < 2) tailStart = tailEnd;
-        std::vector<ColorLaunch> launches(tailStart);
+    // <slot data in LDS, per-XCD tile lists, impulses in LDS>: the six instantiations that exist
+    const bool allLds = metaLds && impLds;
+    auto* solver = usedXcd ? (allLds ? k_contact_solve_persist<true, true, true> : impLds ? k_contact_solve_persist<false, true, true> : k_contact_solve_persist<false, true, false>)
+                           : (allLds ? k_contact_solve_persist<true, false, true> : impLds ? k_contact_solve_persist<false, false, true> : k_contact_solve_persist<false, false, false>);
+    L.launchTimed(a.attached, e6, e7, solver, dim3(persistWaves), dim3(64), allLds ? ldsMeta : impLds ? ldsImp : ldsDesc, stream,
+                  iters, maxSlots, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, gVel.p, scalarsPtr(), xcdTiles.p, a.xcdListCap, bodyOwner.p, gVelL.p, slotMeta.p, imp.p, xcdFault, knobs.persistResident ? 1u : 0u);
+    profileEnd();
+    return MI_OK;
+}
+// the dispatch-ordered dataflow kernel: no joints between the sweeps -> all sweeps in one launch; otherwise one launch per sweep (joints run in between)
+int mi_world::solveFlow(StepAttempt& a) {
+    const uint32_t iters = a.settings.num_rigid_solver_iterations, tilesLaunch = a.tilesLaunch;
+    hipStream_t st = stream;
+    const bool exactSeam = exactSeamStep();   // every sweep ends in an exchange with the neighbours: one launch per sweep
+    const uint32_t perLaunch = joints.count() == 0 && !exactSeam && (uint64_t)std::max(tilesLaunch, 1u) * iters < 0x7FFFFFFFull ? iters : 1u;
+    solveLaunches = tilesLaunch ? (iters + perLaunch - 1) / perLaunch : 0;
+    for (uint32_t it = 0; it < iters; it += perLaunch) {
+        if (perLaunch == 1) joints.solveIteration(*this, st);   // distance, ball, fixed, hinge, cone-twist, slider (constraints.cpp:3764-3769)
+        if (!tilesLaunch) { if (exactSeam) { int rcx = shardSweepExchange(it); if (rcx != MI_OK) return rcx; } continue; }
+        int rc = profileBegin(); if (rc != MI_OK) return rc;
+        L.launch(k_contact_solve_flow, dim3(tilesLaunch * perLaunch), dim3(64), 0, st, it, perLaunch, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p, scalarsPtr());
+        profileEnd();
+        if (exactSeam) { int rcx = shardSweepExchange(it); if (rcx != MI_OK) return rcx; }   // exact seam: the owners' velocities of the shared bodies replace the ghost copies
+    }
+    return MI_OK;
+}
+// one launch per colour per sweep (MI_SOLVER=launch, or an overflow colour is present); synchronous mode only
+int mi_world::solvePerColour(StepAttempt& a) {
+    const uint32_t iters = a.settings.num_rigid_solver_iterations;
+    hipStream_t st = stream;
+    auto colorCount = [&](uint32_t c) { return bins[4 * c].count + bins[4 * c + 1].count + bins[4 * c + 2].count + bins[4 * c + 3].count; };
+    // colours [tailStart, tailEnd) are small (<= 512 manifolds each, a suffix of the used colours): one launch for all of them
+    if (!a.nmBound) { numColorsUsed = 0; for (BinInfo& b : bins) b.count = 0; }   // no manifolds this step: the mirrored schedule is the previous step's
+    uint32_t tailEnd = std::min(numColorsUsed, kOverflowColor), tailStart = tailEnd;
+    while (tailStart > 0 && colorCount(tailStart - 1) <= 512u) --tailStart;
+    if (tailEnd - tailStart < 2) tailStart = tailEnd;
+    std::vector<ColorLaunch> launches(tailStart);
+    for (uint32_t c = 0; c < tailStart; ++c) {
+        ColorLaunch& cl = launches[c];
+        uint32_t acc = 0;
+        for (uint32_t k = 0; k < 4; ++k) { cl.tileStart[k] = bins[4 * c + k].tileStart; cl.ctStart[k] = bins[4 * c + k].ctStart; a.mainContacts += (uint64_t)bins[4 * c + k].count * (k + 1); }
+        for (uint32_t i = 0; i < 4; ++i) { acc += divUp(bins[4 * c + (3 - i)].count, 64); cl.blockEnd[i] = acc; }
+        cl.numBlocks = acc;
+    }
+    solveLaunches = iters * (tailStart + (tailStart < tailEnd ? 1u : 0u));
+    for (uint32_t it = 0; it < iters; ++it) {
+        if (debugOrderPending) { int rcj = joints.solveIterationReference(*this, st); if (rcj != MI_OK) return rcj; }
+        else joints.solveIteration(*this, st);
         for (uint32_t c = 0; c < tailStart; ++c) {
-            ColorLaunch& cl = launches[c];
-            uint32_t acc = 0;
-            for (uint32_t k = 0; k < 4; ++k) { cl.tileStart[k] = bins[4 * c + k].tileStart; cl.ctStart[k] = bins[4 * c + k].ctStart; mainContacts += (uint64_t)bins[4 * c + k].count * (k + 1); }
-            for (uint32_t i = 0; i < 4; ++i) { acc += divUp(bins[4 * c + (3 - i)].count, 64); cl.blockEnd[i] = acc; }
-            cl.numBlocks = acc;
+            const ColorLaunch& cl = launches[c];
+            if (!cl.numBlocks) continue;
+            int rc = profileBegin(); if (rc != MI_OK) return rc;
+            L.launch(k_contact_solve, dim3(cl.numBlocks), dim3(64), 0, st, cl, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
+            profileEnd();
         }
-        solveLaunches = iters * (tailStart + (tailStart < tailEnd ? 1u : 0u));
-        for (uint32_t it = 0; it < iters; ++it) {
-            if (debugOrderPending) { int rcj = joints.solveIterationReference(*this, st); if (rcj != MI_OK) return rcj; }
-            else joints.solveIteration(*this, st);
-            for (uint32_t c = 0; c < tailStart; ++c) {
-                const ColorLaunch& cl = launches[c];
-                if (!cl.numBlocks) continue;
-                if (profileSolve) {
-                    size_t e = 2 * (size_t)profLaunches;
-                    while (profEvents.size() < e + 2) { hipEvent_t ev_; HIP_TRY(hipEventCreate(&ev_)); profEvents.push_back(ev_); }
-                    (void)hipEventRecord(profEvents[e], st);
-                    L.launch(k_contact_solve, dim3(cl.numBlocks), dim3(64), 0, st, cl, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
-                    (void)hipEventRecord(profEvents[e + 1], st);
-                    ++profLaunches;
-                } else {
-                    L.launch(k_contact_solve, dim3(cl.numBlocks), dim3(64), 0, st, cl, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
-                }
-            }
-            if (tailStart < tailEnd) L.launch(k_contact_solve_tail, dim3(1), dim3(256), 0, st, binInfo.p, tailStart, tailEnd, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
-            if (bins[kSchedBins - 1].count) L.launch(k_contact_solve_serial, dim3(1), dim3(64), 0, st, bins[kSchedBins - 1], slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
-            if (exactSeamStep) { int rcx = shardSweepExchange(it); if (rcx != MI_OK) return rcx; }
-        }
+        if (tailStart < tailEnd) L.launch(k_contact_solve_tail, dim3(1), dim3(256), 0, st, binInfo.p, tailStart, tailEnd, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
+        if (bins[kSchedBins - 1].count) L.launch(k_contact_solve_serial, dim3(1), dim3(64), 0, st, bins[kSchedBins - 1], slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p);
+        if (exactSeamStep()) { int rcx = shardSweepExchange(it); if (rcx != MI_OK) return rcx; }
     }
-    if (shard.enabled && pairBound && !shardCounted) L.launch(k_shard_count, dim3(divUp(nmBound ? nmBound : 1u, B)), dim3(B), 0, st, nb, manBodies.p, manInfo.p, bCogInvMass.p, shard.active.p, sc, shards.p);
-    mark();  // 7
-    if (attached && !solveAttached) (void)hipEventRecord(ev[7], st);
-#define MI_VEL_ARGS nb, dt, gPos.p, gVel.p, bCogInvMass.p, bRot.p, bPosN.p, bRotN.p, bLinVelN.p, bAngVelN.p, bForceN.p, bTorqueN.p, gVelL.p, usedXcd ? bodyOwner.p : nullptr, bodyUsed.p, bodyTop.p, \
-                    shard.enabled ? shard.active.p : nullptr, bPos.p, bLinVel.p, bAngVel.p, bForce.p, bTorque.p, shard.activePrev.p, shards.p, sc
-    if (attached && timesEnds(timingLevel) && !blockSkip) hipExtLaunchKernelGGL(k_integrate_velocities<false>, dim3(divUp(nb + 1, B)), dim3(B), 0, st, nullptr, ev[8], 0, MI_VEL_ARGS, nullptr);
-    else if (attached && timesEnds(timingLevel)) hipExtLaunchKernelGGL(k_integrate_velocities<true>, dim3(bodyGrid(divUp(nb + 1, B))), dim3(B), 0, st, nullptr, ev[8], 0, MI_VEL_ARGS, shard.blockLive.p);
-    else if (blockSkip) L.launch(k_integrate_velocities<true>, dim3(bodyGrid(divUp(nb + 1, B))), dim3(B), 0, st, MI_VEL_ARGS, shard.blockLive.p);
-    else L.launch(k_integrate_velocities<false>, dim3(divUp(nb + 1, B)), dim3(B), 0, st, MI_VEL_ARGS, nullptr);
-#undef MI_VEL_ARGS
-    mark();  // 8
-    // ---------------------------------------------------------------------------------------------- end of step: the one read-back
-    {
-        const uint32_t words = (uint32_t)(offsetof(Readback, seq) / 4u);
-        if (spinReadback) L.launch(k_publish_readback, dim3(1), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(sc), words, reinterpret_cast<uint32_t*>(hsPinned), words, readbackSeqDev.p,
-                                   fuseResetStep ? sc : nullptr, shards.p, roundFlagsPtr(), keyCount.p);
-        else HIP_TRY(L.memcpyAsync(hsPinned, sc, offsetof(Readback, seq), hipMemcpyDeviceToHost, st));   // scalars + round flags are contiguous
-        // step-ahead: the next step's k_bp_prepare, on the state this step has just written (the "N" set, current once the step is valid), the grid this step prepared and the
-        // axis it chose (read from the device: StepScalars::axisNext survives the reset inside k_publish_readback), into the other set of world-shape / AABB rows
-        if (knobs.stepAhead && spec && pass == PASS_PLAIN && spinReadback && fuseResetStep && !shard.enabled && nc && gridValid && knobs.fuseWorld && !graphStep && !debugSync &&
-            !timesEnds(timingLevel) && !debugOrderPending && !heightmap && !usesInteractions) {
-            HIP_TRY(wShapeAlt.ensure(wShape.cap)); HIP_TRY(aabbMinAlt.ensure(aabbMin.cap)); HIP_TRY(aabbMaxAlt.ensure(aabbMax.cap));
-            hipLaunchKernelGGL(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, aabbMinAlt.p, aabbMaxAlt.p, grid.p + (gridCur ^ 1u), axisPartials.p, shards.p, sc, largeList.p, isLarge.p,
-                               blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p, (const uint8_t*)nullptr, (const uint8_t*)nullptr, 1u,
-                               nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPosN.p, bRotN.p, hullAabb.p, wShapeAlt.p, aabbMinAlt.p, aabbMaxAlt.p, sapAxis, &sc->axisNext,
-                               (const uint2*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr);
-            ++aheadEnqueued;
-            ahead.pending = true; ahead.stale = true /* until this step is known to be valid */; ahead.nc = nc; ahead.nb = nb; ahead.gridIdx = gridCur ^ 1u; ahead.pos = bPosN.p; ahead.rot = bRotN.p; ahead.shape = cShape.p; ahead.axis = 0xFFFFFFFFu;
-        }
+    return MI_OK;
+}
+
+// Velocities -> the new body state (the "N" set; nothing persistent is written before this kernel).  Last kernel of the step's time: it carries the stop event.
+int mi_world::stageIntegrate(StepAttempt& a) {
+    const uint32_t nb = a.nb, B = 256;
+    L.launchTimed(a.attached && timesEnds(timingLevel), nullptr, ev[EV_STEP_END], a.blockSkip ? k_integrate_velocities<true> : k_integrate_velocities<false>, dim3(bodyGrid(a, divUp(nb + 1, B))), dim3(B), 0, stream,
+                  nb, a.dt, gPos.p, gVel.p, bCogInvMass.p, bRot.p, bPosN.p, bRotN.p, bLinVelN.p, bAngVelN.p, bForceN.p, bTorqueN.p, gVelL.p, usedXcd ? bodyOwner.p : nullptr, bodyUsed.p, bodyTop.p,
+                  shard.enabled ? shard.active.p : nullptr, bPos.p, bLinVel.p, bAngVel.p, bForce.p, bTorque.p, shard.activePrev.p, shards.p, scalarsPtr(), a.blockSkip ? shard.blockLive.p : nullptr);
+    return MI_OK;
+}
+
+// End of step: the one read-back (and, behind it, the next step's first kernel: step-ahead).
+int mi_world::stagePublish(StepAttempt& a) {
+    const uint32_t nb = a.nb, nc = a.nc;
+    StepScalars* sc = scalarsPtr(); hipStream_t st = stream;
+    const uint32_t words = (uint32_t)(offsetof(Readback, seq) / 4u);
+    if (spinReadback) L.launch(k_publish_readback, dim3(1), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(sc), words, reinterpret_cast<uint32_t*>(hsPinned), words, readbackSeqDev.p,
+                               a.fuseResetStep ? sc : nullptr, shards.p, roundFlagsPtr(), keyCount.p);
+    else HIP_TRY(L.memcpyAsync(hsPinned, sc, offsetof(Readback, seq), hipMemcpyDeviceToHost, st));   // scalars + round flags are contiguous
+    // step-ahead: the next step's k_bp_prepare, on the state this step has just written (the "N" set, current once the step is valid), the grid this step prepared and the
+    // axis it chose (read from the device: StepScalars::axisNext survives the reset inside k_publish_readback), into the other set of world-shape / AABB rows
+    if (knobs.stepAhead && a.spec && a.pass == PASS_PLAIN && spinReadback && a.fuseResetStep && !shard.enabled && nc && gridValid && knobs.fuseWorld && !a.graphStep && !knobs.debugSync &&
+        !timesEnds(timingLevel) && !debugOrderPending && !heightmap && !usesInteractions) {
+        HIP_TRY(wShapeAlt.ensure(wShape.cap)); HIP_TRY(aabbMinAlt.ensure(aabbMin.cap)); HIP_TRY(aabbMaxAlt.ensure(aabbMax.cap));
+        hipLaunchKernelGGL(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, aabbMinAlt.p, aabbMaxAlt.p, grid.p + (gridCur ^ 1u), axisPartials.p, shards.p, sc, largeList.p, isLarge.p,
+                           blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p, (const uint8_t*)nullptr, (const uint8_t*)nullptr, 1u,
+                           nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPosN.p, bRotN.p, hullAabb.p, wShapeAlt.p, aabbMinAlt.p, aabbMaxAlt.p, sapAxis, &sc->axisNext,
+                           (const uint2*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr);
+        ++aheadEnqueued;
+        ahead.pending = true; ahead.stale = true /* until this step is known to be valid */; ahead.nc = nc; ahead.nb = nb; ahead.gridIdx = gridCur ^ 1u; ahead.pos = bPosN.p; ahead.rot = bRotN.p; ahead.shape = cShape.p; ahead.axis = 0xFFFFFFFFu;
     }
-    if (pass == PASS_DRY) {
-        const uint64_t sig = L.h ^ ((uint64_t)L.ops << 48);
-        StepGraph* hit = nullptr;
-        for (StepGraph& g : stepGraphs) if (g.sig == sig && g.exec) { hit = &g; break; }
-        if (graphDebug) {
-            if (!hit && !graphPrevOps2.empty()) {   // compare with the step before the previous one (same buffer parity)
-                size_t k = 0; while (k < graphPrevOps2.size() && k < L.opHashes.size() && graphPrevOps2[k] == L.opHashes[k]) ++k;
-                std::fprintf(stderr, "[mi_physics] step %llu: graph signature differs from that of two steps ago at operation %zu of %zu (then %zu)\n", (unsigned long long)totalSteps, k, L.opHashes.size(), graphPrevOps2.size());
-            }
-            graphPrevOps2 = graphPrevOps; graphPrevOps = L.opHashes;
-        }
-        if (hit) {
-            hit->lastUse = ++graphUseClock; ++graphHits;
-            if (hipGraphLaunch(hit->exec, st) != hipSuccess) { (void)hipGetLastError(); graphsEnabled = false; dropStepGraphs(); pass = PASS_PLAIN; goto enqueue_section; }
-        } else if (sig == graphLastSig || sig == graphPrevSig) {      // seen within the last two steps as well: capture it
-            if (stepGraphs.size() >= kMaxStepGraphs) { HIP_TRY(hipStreamSynchronize(st)); dropStepGraphs(); }   // a long-lived scene keeps changing shape: start over (all at once, with the stream idle)
-            graphPrevSig = graphLastSig; graphLastSig = sig;
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); graphsEnabled = false; pass = PASS_PLAIN; }
-            else pass = PASS_CAPTURE;
-            goto enqueue_section;
-        } else { graphPrevSig = graphLastSig; graphLastSig = sig; ++graphPlain; pass = PASS_PLAIN; goto enqueue_section; }
-    } else if (pass == PASS_CAPTURE) {
-        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-        bool ok = hipStreamEndCapture(st, &graph) == hipSuccess && graph && L.firstError == hipSuccess;
-        if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-        if (graph) (void)hipGraphDestroy(graph);
-        if (ok) ok = hipGraphLaunch(exec, st) == hipSuccess;
-        if (!ok) {   // this runtime cannot hold the step in a graph: plain launches from now on (nothing has been enqueued yet)
-            (void)hipGetLastError();
-            if (exec) (void)hipGraphExecDestroy(exec);
-            graphsEnabled = false; dropStepGraphs(); pass = PASS_PLAIN; goto enqueue_section;
-        }
-        const uint64_t sig = graphLastSig;
-        stepGraphs.push_back(StepGraph{sig, exec, ++graphUseClock}); ++graphCaptures;
-    }
-    if (poseArm.armed) {   // the poses of the state this step is producing, enqueued behind it (a step that turns out void produces them again)
-        ++pose.produced_ahead; poseArm.done = false;
-        int rcp = posesProduce(poseArm.t, true, true); if (rcp != MI_OK) return rcp;
-        poseArm.done = true;
-    }
+    return MI_OK;
+}
+
+// The host's one wait per step: for the sequence number k_publish_readback writes behind the scalars (or for the stream, on the copy path).
+int mi_world::awaitReadback() {
     if (spinReadback) {
         const uint32_t seq = readbackSeq + 1u ? readbackSeq + 1u : 1u;   // never 0; the device counts the same way (k_publish_readback)
         readbackSeq = seq;
@@ -888,46 +946,39 @@ enqueue_section:
         while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
             __builtin_ia32_pause();
             if ((++spins & 0xFFFu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-                HIP_TRY(hipStreamSynchronize(st));   // a long step, a device fault or a lost store: let the runtime report it
+                HIP_TRY(hipStreamSynchronize(stream));   // a long step, a device fault or a lost store: let the runtime report it
                 if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) return fail(MI_ERR_DEVICE, "end-of-step read-back did not arrive");
                 break;
             }
         }
     } else {
-        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(stream));
     }
     hs = hsPinned->sc;
-    const uint32_t* flagsHost = hsPinned->flags;
     HIP_TRY(hipGetLastError());
-    scalarsClean = fuseResetStep;   // (the publish kernel of THIS attempt cleared the device words for whatever runs next: the next step, or this one again)
-    if (spec) {
+    return MI_OK;
+}
+
+// Was the attempt valid?  MI_OK, an error, or STEP_RETRY with whatever the next attempt must know already set (nothing persistent has been written: stepInternal
+// runs the same step again, synchronously, one rung further down its ladder).
+int mi_world::validateStep(StepAttempt& a) {
+    scalarsClean = a.fuseResetStep;   // (the publish kernel of THIS attempt cleared the device words for whatever runs next: the next step, or this one again)
+    if (a.spec) {
         const uint32_t ovfCount = hs.binStart[kColorBins] - hs.binStart[kSchedBins - 1];
-        const bool valid = hs.numPairs <= pairBound && hs.numManifolds <= nmBound && hs.specOverflow == 0 && hs.colorPending == 0 && ovfCount == 0 &&
-                           (!usesInteractions || (hs.numInterPairs <= interPairBound && hs.numInteractions <= interList.cap && hs.numInteractions <= 32768u));
+        const bool valid = hs.numPairs <= a.pairBound && hs.numManifolds <= a.nmBound && hs.specOverflow == 0 && hs.colorPending == 0 && ovfCount == 0 &&
+                           (!usesInteractions || (hs.numInterPairs <= a.interPairBound && hs.numInteractions <= interList.cap && hs.numInteractions <= 32768u));
         if (hs.tailRounds == kTailTimedOut) colorTailHold = 256u;
         if (!valid) return STEP_RETRY;   // nothing persistent was modified: run the same step synchronously (what ran ahead of the next step stays marked stale)
         mirrorSchedule();
     }
 #ifdef MI_DBG_TIMELINE
-    if (usedPersist && !knobs.timelineOut.empty()) {   // development: per-visit wall-clock stamps of the persistent solver, dumped after step MI_DBG_TIMELINE_STEP
-        const size_t words = (size_t)persistWaves * 256 * 8;      // (second half: the stamps of the knock-out launch of a -DMI_DBG_KNOCKOUT build)
-        if (dbgTimelineBuf && totalSteps == (unsigned long long)knobs.timelineStep) {
-            std::vector<unsigned long long> h(2 * words);
-            HIP_TRY(hipMemcpy(h.data(), dbgTimelineBuf, 2 * words * 8, hipMemcpyDeviceToHost));
-            FILE* f = fopen(knobs.timelineOut.c_str(), "wb"); if (f) { fwrite(h.data(), 8, words, f); fclose(f); }
-            f = fopen((knobs.timelineOut + ".knock").c_str(), "wb"); if (f) { fwrite(h.data() + words, 8, words, f); fclose(f); }
-        }
-        if (!dbgTimelineBuf) {
-            HIP_TRY(hipMalloc(&dbgTimelineBuf, 2 * words * 8)); HIP_TRY(hipMemset(dbgTimelineBuf, 0, 2 * words * 8));
-            HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dbgTimeline), &dbgTimelineBuf, sizeof(dbgTimelineBuf)));
-        }
-    }
+    { int rct = dbgTimelineDump(); if (rct != MI_OK) return rct; }
 #endif
     if (usedXcd && !hs.solveError) {
         // partitioning is only trusted when the eight residue classes of blockIdx really sat on eight DIFFERENT XCDs (a device
         // that exposes fewer XCDs, or hides the id, runs unpartitioned)
         bool distinct = true;
-        for (int a = 0; a < 8 && distinct; ++a) for (int b = a + 1; b < 8; ++b) if (hs.xccOf[a] == hs.xccOf[b]) { distinct = false; break; }
+        for (int x = 0; x < 8 && distinct; ++x) for (int y = x + 1; y < 8; ++y) if (hs.xccOf[x] == hs.xccOf[y]) { distinct = false; break; }
         if (!distinct) { persistXcd = false; return STEP_RETRY; }
     }
     if (hs.solveError && usedPersist) {
@@ -936,100 +987,110 @@ enqueue_section:
         //   3: blockIdx % 8 does not identify the XCD on this device -> no XCD partitioning from now on;
         //   otherwise: the persistent kernel needs all its workgroups resident at once and the device did not grant that (or
         //   a wait ran out of budget) -> the dispatch-ordered dataflow kernel for good
-        if (hs.solveError == 2u && usedXcd && spec) { haveXcdEstimate = false; return STEP_RETRY; }
+        if (hs.solveError == 2u && usedXcd && a.spec) { haveXcdEstimate = false; return STEP_RETRY; }
         if (usedXcd) persistXcd = false; else persistSolver = false;
         return STEP_RETRY;
     }
-    if (flowFaultTest && !flowFaultFired && useFlow && !usedPersist && !hs.solveError) { flowFaultFired = true; hs.solveError = 1u; }   // test injection
-    if (hs.solveError && useFlow) {
+    if (flowFaultTest && !flowFaultFired && a.useFlow && !usedPersist && !hs.solveError) { flowFaultFired = true; hs.solveError = 1u; }   // test injection
+    if (hs.solveError && a.useFlow) {
         // the dispatch-ordered kernels rely on workgroups being started in index order on a device that is not shared; when a wait
         // runs out of budget nothing persistent has been written: run the step again with one launch per colour, and stay there a while
         launchFallbackSteps = 256u; ++flowFallbacks;
         return STEP_RETRY;
     }
     if (hs.solveError) return fail(MI_ERR_DEVICE, "contact solver reported an error on the per-colour path");
+    return MI_OK;
+}
+
+// What a valid step reports besides the new state: the solver profile, trigger enter / leave and collision begin / end events.
+int mi_world::collectEvents(StepAttempt& a) {
+    const uint32_t B = 256;
+    StepScalars* sc = scalarsPtr(); hipStream_t st = stream;
     if (profileSolve) {
-        if (useFlow) { mainContacts = 0; for (uint32_t bn = 0; bn + 1 < kSchedBins; ++bn) mainContacts += (uint64_t)bins[bn].count * ((bn & 3u) + 1u); }
-        profContacts = mainContacts * iters;
+        if (a.useFlow) { a.mainContacts = 0; for (uint32_t bn = 0; bn + 1 < kSchedBins; ++bn) a.mainContacts += (uint64_t)bins[bn].count * ((bn & 3u) + 1u); }
+        profContacts = a.mainContacts * a.settings.num_rigid_solver_iterations;
         profKernelMs = 0.f;
         for (uint32_t l = 0; l < profLaunches; ++l) profKernelMs += elapsedMs(profEvents[2 * l], profEvents[2 * l + 1]);
     }
-    if (spec && usesInteractions) {   // the trigger overlaps of this step, from the device-sorted interaction list (force fields were applied in-stream)
+    if (a.spec && usesInteractions) {   // the trigger overlaps of this step, from the device-sorted interaction list (force fields were applied in-stream)
         std::vector<DeviceInteraction> list(eventsEnabled ? hs.numInteractions : 0u);
         if (!list.empty()) { HIP_TRY(hipMemcpyAsync(list.data(), interSorted.p, list.size() * sizeof(DeviceInteraction), hipMemcpyDeviceToHost, st)); HIP_TRY(hipStreamSynchronize(st)); }
-        int rc = triggerEventsFrom(list, triggerEvents); if (rc != MI_OK) return rc;
+        int rc = triggerEventsFrom(list, a.triggerEvents); if (rc != MI_OK) return rc;
     }
-    if (eventsEnabled) {
-        pendingEvents.insert(pendingEvents.end(), triggerEvents.begin(), triggerEvents.end());   // handleNonCollisionInteractions runs before the collision events
-        if (!nmBound && tabValid) {   // no manifolds at all this step: every collision of the previous step ended
-            uint32_t cap = last.numManifolds + 1024u;
-            HIP_TRY(devEvents.ensure(cap));
-            const int nt = tabCur ^ 1;
-            HIP_TRY(tab[nt].ensure(1024)); tabMask[nt] = 1023u;
-            HIP_TRY(hipMemsetAsync(tab[nt].p, 0, 1024 * sizeof(HistSlot), st));
-            hintOf[nt] = hintOf[tabCur] ^ 1; HIP_TRY(histHint[hintOf[nt]].ensure(1024)); HIP_TRY(hipMemsetAsync(histHint[hintOf[nt]].p, 0, 1024 * sizeof(uint32_t), st));
-            k_events_end<<<divUp(tabMask[tabCur] + 1u, B), B, 0, st>>>(cap, sc, tab[tabCur].p, tabMask[tabCur], tab[nt].p, tabMask[nt], devEvents.p, histHint[hintOf[nt]].p);
-            HIP_TRY(hipMemcpyAsync(hsPinned, sc, offsetof(Readback, seq), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            hs = hsPinned->sc;
-        }
-        if (hs.numEvents) {
-            std::vector<DeviceEvent> ev_(hs.numEvents);
-            HIP_TRY(hipMemcpyAsync(ev_.data(), devEvents.p, (size_t)hs.numEvents * sizeof(DeviceEvent), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            std::sort(ev_.begin(), ev_.end(), [](const DeviceEvent& x, const DeviceEvent& y) { return x.colliderA != y.colliderA ? x.colliderA < y.colliderA : x.colliderB < y.colliderB; });
-            for (const DeviceEvent& d : ev_) {   // the reference's sorted merge visits the pairs in ascending (a, b) order
-                mi_event e{}; e.type = d.type; e.collider_a = d.colliderA; e.collider_b = d.colliderB;
-                e.entity_a = colliders[d.colliderA].entity; e.entity_b = colliders[d.colliderB].entity;
-                for (int k = 0; k < 3; ++k) { e.point[k] = d.point[k]; e.normal[k] = d.normal[k]; e.relative_velocity[k] = d.relVel[k]; }
-                pendingEvents.push_back(e);
-            }
+    if (!eventsEnabled) return MI_OK;
+    pendingEvents.insert(pendingEvents.end(), a.triggerEvents.begin(), a.triggerEvents.end());   // handleNonCollisionInteractions runs before the collision events
+    if (!a.nmBound && tabValid) {   // no manifolds at all this step: every collision of the previous step ended
+        uint32_t cap = last.numManifolds + 1024u;
+        HIP_TRY(devEvents.ensure(cap));
+        const int nt = tabCur ^ 1;
+        HIP_TRY(tab[nt].ensure(1024)); tabMask[nt] = 1023u;
+        HIP_TRY(hipMemsetAsync(tab[nt].p, 0, 1024 * sizeof(HistSlot), st));
+        hintOf[nt] = hintOf[tabCur] ^ 1; HIP_TRY(histHint[hintOf[nt]].ensure(1024)); HIP_TRY(hipMemsetAsync(histHint[hintOf[nt]].p, 0, 1024 * sizeof(uint32_t), st));
+        k_events_end<<<divUp(tabMask[tabCur] + 1u, B), B, 0, st>>>(cap, sc, tab[tabCur].p, tabMask[tabCur], tab[nt].p, tabMask[nt], devEvents.p, histHint[hintOf[nt]].p);
+        HIP_TRY(hipMemcpyAsync(hsPinned, sc, offsetof(Readback, seq), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        hs = hsPinned->sc;
+    }
+    if (hs.numEvents) {
+        std::vector<DeviceEvent> ev_(hs.numEvents);
+        HIP_TRY(hipMemcpyAsync(ev_.data(), devEvents.p, (size_t)hs.numEvents * sizeof(DeviceEvent), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::sort(ev_.begin(), ev_.end(), [](const DeviceEvent& x, const DeviceEvent& y) { return x.colliderA != y.colliderA ? x.colliderA < y.colliderA : x.colliderB < y.colliderB; });
+        for (const DeviceEvent& d : ev_) {   // the reference's sorted merge visits the pairs in ascending (a, b) order
+            mi_event e{}; e.type = d.type; e.collider_a = d.colliderA; e.collider_b = d.colliderB;
+            e.entity_a = colliders[d.colliderA].entity; e.entity_b = colliders[d.colliderB].entity;
+            for (int k = 0; k < 3; ++k) { e.point[k] = d.point[k]; e.normal[k] = d.normal[k]; e.relative_velocity[k] = d.relVel[k]; }
+            pendingEvents.push_back(e);
         }
     }
-    // the step is valid: the freshly integrated state becomes the current one
-    std::swap(bPos.p, bPosN.p); std::swap(bRot.p, bRotN.p); std::swap(bLinVel.p, bLinVelN.p); std::swap(bAngVel.p, bAngVelN.p);
-    std::swap(bForce.p, bForceN.p); std::swap(bTorque.p, bTorqueN.p);
+    return MI_OK;
+}
+
+// The next step's launch sizes derive from the counts of the last valid step; they are kept as snug, STICKY upper bounds (12.5 % granules, unchanged while
+// they still fit) so that consecutive steps of a scene in a steady state enqueue identical work — which a captured graph can replay.
+static uint32_t stickyBound(uint32_t x, uint32_t prev, uint32_t minGranule) {
+    const uint32_t g = std::max(minGranule, (x ? 1u << (31 - __builtin_clz(x)) : 1u) >> 3);
+    if (prev >= x && prev - x <= 2u * g) return prev;
+    return (x / g + 1u) * g;
+}
+// The step is valid: the freshly integrated state becomes the current one, its counts the next step's estimates.
+void mi_world::commitStep(const StepAttempt& a) {
+    const uint32_t nb = a.nb, nc = a.nc;
+    bPos.swap(bPosN); bRot.swap(bRotN); bLinVel.swap(bLinVelN); bAngVel.swap(bAngVelN); bForce.swap(bForceN); bTorque.swap(bTorqueN);
     if (usesInteractions) prevTriggerOverlaps.swap(nextTriggerOverlaps);
     sapAxis = hs.axisNext; ahead.axis = hs.axisNext; ahead.stale = false;   // (the step is valid: what ran ahead of the next step ran on the state that is now current)
     if (nc) { gridCur ^= 1u; gridValid = true; gridNextCells = hs.numCellsNext; }   // the grid k_pair_finish prepared becomes the next step's
-    if (nmBound) { tabCur ^= 1; tabValid = true; } else tabValid = false;
+    if (a.nmBound) { tabCur ^= 1; tabValid = true; } else tabValid = false;
     hostStale = true;
-    // The next step's launch sizes derive from these counts; they are kept as snug, STICKY upper bounds (12.5 % granules, unchanged while
-    // they still fit) so that consecutive steps of a scene in a steady state enqueue identical work — which a captured graph can replay.
-    auto sticky = [](uint32_t x, uint32_t prev, uint32_t minGranule) {
-        const uint32_t g = std::max(minGranule, (x ? 1u << (31 - __builtin_clz(x)) : 1u) >> 3);
-        if (prev >= x && prev - x <= 2u * g) return prev;
-        return (x / g + 1u) * g;
-    };
-    last.numPairs = sticky(hs.numPairs, last.numPairs, 256); last.numManifolds = sticky(hs.numManifolds, last.numManifolds, 256);
-    last.numContacts = sticky(hs.numContacts, last.numContacts, 256); last.numCells = sticky(hs.numCells, last.numCells, 1024);
-    last.numSmall = sticky(nc - std::min(nc, hs.numLarge + hs.numDead), last.numSmall, 256); last.numLarge = sticky(hs.numLarge, last.numLarge, 16);
-    last.gjkSpan = sticky(hs.gjkHi - hs.gjkLo, last.gjkSpan, 256);
-    last.numInterPairs = sticky(hs.numInterPairs, last.numInterPairs, 256); last.numInteractions = sticky(hs.numInteractions, last.numInteractions, 256);
+    last.numPairs = stickyBound(hs.numPairs, last.numPairs, 256); last.numManifolds = stickyBound(hs.numManifolds, last.numManifolds, 256);
+    last.numContacts = stickyBound(hs.numContacts, last.numContacts, 256); last.numCells = stickyBound(hs.numCells, last.numCells, 1024);
+    last.numSmall = stickyBound(nc - std::min(nc, hs.numLarge + hs.numDead), last.numSmall, 256); last.numLarge = stickyBound(hs.numLarge, last.numLarge, 16);
+    last.gjkSpan = stickyBound(hs.gjkHi - hs.gjkLo, last.gjkSpan, 256);
+    last.numInterPairs = stickyBound(hs.numInterPairs, last.numInterPairs, 256); last.numInteractions = stickyBound(hs.numInteractions, last.numInteractions, 256);
     for (int k = 0; k < 3; ++k) shard.owned[k] = hs.shardOwned[k];
     if (seamMode()) { seamLast[0] = hs.seamStats[0]; seamLast[1] = hs.seamStats[1]; seamViolations += hs.seamStats[2]; }
     shard.flagsSwapPending = shard.enabled; shard.stepOpen = false; shard.flagsOfAStep = shard.enabled;
     haveXcdEstimate = usedXcd; lastXcdSingle = usedXcdSingle;
-    if (usedXcd) { uint32_t m = 0; for (int x = 0; x < 8; ++x) m = std::max(m, hs.xcdCount[x]); lastXcdMax = sticky(m, lastXcdMax, 16); }
+    if (usedXcd) { uint32_t m = 0; for (int x = 0; x < 8; ++x) m = std::max(m, hs.xcdCount[x]); lastXcdMax = stickyBound(m, lastXcdMax, 16); }
     if (hs.tailRounds) { ++tailSteps; tailRoundsSum += hs.tailRounds; }
+    const uint32_t* flagsHost = hsPinned->flags;
     last.colorRounds = 0;
     while (last.colorRounds < 96u && flagsHost[last.colorRounds]) ++last.colorRounds;   // rounds that still had work (+1 to commit) this step
     ++last.colorRounds;
     haveEstimates = true;
     pairsIn = hs.partitioned ? pairKeysS.p : pairKeys.p;
-    lastPartitioned = hs.partitioned != 0u; havePartitionFlag = pairBound != 0u;
+    lastPartitioned = hs.partitioned != 0u; havePartitionFlag = a.pairBound != 0u;
 
     counts.num_rigid_bodies = nb; counts.num_colliders = nc; counts.num_broadphase_overlaps = nc ? hs.numOverlaps : 0;
-    manifoldsLast = pairBound ? hs.numManifolds : 0;
+    manifoldsLast = a.pairBound ? hs.numManifolds : 0;
     counts.num_collisions = manifoldsLast - (manifoldsLast ? hs.numHmManifolds - hs.numHmColliders : 0u);   // terrain: one collision per collider (heightmap_collision.cpp:582-594)
-    counts.num_contacts = pairBound ? hs.numContacts : 0;
+    counts.num_contacts = a.pairBound ? hs.numContacts : 0;
     counts.num_colors = manifoldsLast ? numColorsUsed : 0u /* (a step without manifolds builds no schedule: the mirrored one is an earlier step's) */; counts.sorting_axis = hs.axisCur; counts.reserved = solveLaunches;
     // the step's device times: read from its events LATER (finishTimes), the next step records into the other set
     finishTimes();   // (normally done already, at the start of this step)
-    timesPending = timingLevel != 0u; timesPendingSet = evSet; timesPendingLevel = timingLevel; timesPendingUpdates = (uint64_t)counts.num_contacts * iters;
+    timesPending = timingLevel != 0u; timesPendingSet = evSet; timesPendingLevel = timingLevel; timesPendingUpdates = (uint64_t)counts.num_contacts * a.settings.num_rigid_solver_iterations;
     if (!timesPending) { times = mi_stage_times{}; ++timesSteps; contactUpdatesSum += timesPendingUpdates; }   // timing off: no stale times, and the step / contact-update counts still add up
     evSet ^= 1; ev = evSets[evSet];
-    return MI_OK;
 }
 // (the host gets here after the published read-back of the step the events belong to — but the HIP 7.0 runtime now and then still reports an event
 // attached to a kernel as not ready, ~1 step in 1000: elapsedMs waits for it then instead of reporting 0 ms)
@@ -1039,14 +1100,110 @@ void mi_world::finishTimes() {
     hipEvent_t* e = evSets[timesPendingSet];
     auto el = [&](int a, int b) { return elapsedMs(e[a], e[b]); };
     if (timesStages(timesPendingLevel)) {
-        times.world_colliders = el(0, 1); times.broadphase = el(1, 2); times.narrowphase = el(2, 3); times.integrate_forces = el(3, 4);
-        times.schedule = el(4, 5); times.init_constraints = el(5, 6);
+        times.world_colliders = el(EV_STEP_BEGIN, EV_PREPARED); times.broadphase = el(EV_PREPARED, EV_BROAD); times.narrowphase = el(EV_BROAD, EV_NARROW); times.integrate_forces = el(EV_NARROW, EV_FORCES);
+        times.schedule = el(EV_FORCES, EV_SCHEDULE); times.init_constraints = el(EV_SCHEDULE, EV_SOLVE_BEGIN);
     } else { times.world_colliders = times.broadphase = times.narrowphase = times.integrate_forces = times.schedule = times.init_constraints = 0.f; }
-    times.solve = el(6, 7);
-    if (timesEnds(timesPendingLevel)) { times.integrate_velocities = el(7, 8); times.total = el(0, 8); } else times.integrate_velocities = times.total = 0.f;   // (level 3: the step's ends were not timed)
+    times.solve = el(EV_SOLVE_BEGIN, EV_SOLVE_END);
+    if (timesEnds(timesPendingLevel)) { times.integrate_velocities = el(EV_SOLVE_END, EV_STEP_END); times.total = el(EV_STEP_BEGIN, EV_STEP_END); } else times.integrate_velocities = times.total = 0.f;   // (level 3: the step's ends were not timed)
     { float* a = &timesSum.world_colliders; const float* b = &times.world_colliders; for (int i = 0; i < 9; ++i) a[i] += b[i]; ++timesSteps;
       contactUpdatesSum += timesPendingUpdates; }
 }
+
+#if defined(MI_DBG_KNOCKOUT) || defined(MI_DBG_TIMELINE)
+// ------------------------------------------------------------------------------------------------
+// Development builds only (tools/build_variant.py): knock-out launches and the persistent solver's timeline
+// ------------------------------------------------------------------------------------------------
+#ifdef MI_DBG_KNOCKOUT
+// A knock-out site (tools/gpu_knockout.sh) launches one kernel of the step a FIRST time with parts of it removed (g_dbgKnock, kernels.hpp) and whatever it modifies
+// redirected to scratch; the real launch behind it starts from untouched data and the step goes on from ITS results.  Device time of the knock-out launches -> knockMsSum / knockLaunches.
+int mi_world::dbgKnockWait(KnockSite& s) {   // the previous step's launch of this site
+    if (!s.k0) { HIP_TRY(hipEventCreate(&s.k0)); HIP_TRY(hipEventCreate(&s.k1)); }
+    if (s.pending) { HIP_TRY(hipEventSynchronize(s.k1)); float ms = 0.f; if (hipEventElapsedTime(&ms, s.k0, s.k1) == hipSuccess && timingLevel >= 2u) { knockMsSum += ms; ++knockLaunches; } s.pending = false; }   // (counted while the caller times steps: mi_world_set_stage_timing)
+    return MI_OK;
+}
+template <class F> int mi_world::dbgKnockLaunch(KnockSite& s, uint32_t word, F&& launch) {
+    s.word = word;
+    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &s.word, sizeof(s.word), 0, hipMemcpyHostToDevice, stream));
+    (void)hipEventRecord(s.k0, stream);
+    launch();
+    (void)hipEventRecord(s.k1, stream);
+    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgKnock), &knockZero, sizeof(knockZero), 0, hipMemcpyHostToDevice, stream));
+    s.pending = true;
+    return MI_OK;
+}
+// the grid part of the pair pass, on a scratch pair list and scratch counters (g_dbgKnock bits 16-18)
+int mi_world::dbgKnockBroad(uint32_t bpc, uint32_t cap, GridParams* gridUse) {
+    if (!(knobs.knockout >> 16) || L.dry) return MI_OK;
+    hipStream_t st = stream;
+    int rc = dbgKnockWait(knockBp); if (rc != MI_OK) return rc;
+    HIP_TRY(knockPairs.ensure(pairKeys.cap)); HIP_TRY(knockSc.ensure(sizeof(StepScalars))); HIP_TRY(knockSh.ensure(sizeof(Shards)));
+    HIP_TRY(hipMemcpyAsync(knockSc.p, scalarsPtr(), sizeof(StepScalars), hipMemcpyDeviceToDevice, st)); HIP_TRY(hipMemsetAsync(knockSh.p, 0, sizeof(Shards), st));
+    const uint32_t word = (knobs.knockout >> 16) >= 0x80u ? 0u : (knobs.knockout & 0xFF0000u);   // (0x800000: nothing removed)
+    return dbgKnockLaunch(knockBp, word, [&]() {
+        hipLaunchKernelGGL(k_bp_pairs_grid, dim3(5u * bpc), dim3(256), 0, st, (uint32_t)colliders.size(), bpc, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, knockPairs.p, cap, reinterpret_cast<StepScalars*>(knockSc.p), reinterpret_cast<Shards*>(knockSh.p), InterSink{nullptr, 0u, nullptr});
+    });
+}
+// k_emit_manifolds (g_dbgKnock bits 8-12), its read-modify-write targets (per-body colour masks, the next history table, round-0 proposals, round flags) redirected
+// to scratch; everything else it writes the real launch behind it writes again.
+int mi_world::dbgKnockEmit(const StepAttempt& a) {
+    if (!((knobs.knockout >> 8) & 0xFFu) || L.dry || !tabValid) return MI_OK;
+    const uint32_t nb = a.nb, nc = a.nc, B = 256;
+    hipStream_t st = stream;
+    int rc = dbgKnockWait(knockEmit); if (rc != MI_OK) return rc;
+    HIP_TRY(knockUsed.ensure(bodyUsed.cap)); HIP_TRY(knockTop.ensure(bodyTop.cap)); HIP_TRY(knockTab.ensure(tab[tabCur ^ 1].cap)); HIP_TRY(knockFlags.ensure(64));
+    HIP_TRY(hipMemsetAsync(knockUsed.p, 0, knockUsed.cap * 8, st)); HIP_TRY(hipMemsetAsync(knockTab.p, 0, knockTab.cap * sizeof(HistSlot), st)); HIP_TRY(hipMemsetAsync(knockTop.p, 0, knockTop.cap * 8, st));
+    const uint32_t word = ((knobs.knockout >> 8) & 0xFFu) >= 0x80u ? 0u : (knobs.knockout & 0xFF00u);   // (0x8000: nothing removed = the harness itself)
+    return dbgKnockLaunch(knockEmit, word, [&]() {
+        hipLaunchKernelGGL(k_emit_manifolds, dim3(divUp(a.pairBound, B)), dim3(B), 0, st, nc, nb, pairKeys.p, pairKeysS.p, npPacked.p, npScan.p, cEmit.p,
+                           manPair.p, manBodies.p, manInfo.p, colWork.p, color.p, tab[tabCur].p, tabMask[tabCur], knockUsed.p, eventsEnabled ? manIsNew.p : nullptr, scalarsPtr(),
+                           heightmap ? make_float2(hmParams.restitution, hmParams.friction) : make_float2(0.f, 0.f), knockTab.p, tabMask[tabCur ^ 1], manKept.p, histHint[hintOf[tabCur]].p, histHint[hintOf[tabCur ^ 1]].p /* (a fresh insertion may raise a hint: harmless, they only ever grow) */,
+                           a.seamOn ? seamId.p : nullptr, emitsRound0() ? knockTop.p + (nb + 1) : nullptr, knockFlags.p);
+    });
+}
+// the persistent solver (all-LDS, XCD-partitioned variant) on scratch copies of the velocity arrays, with parts of the tile visit removed
+int mi_world::dbgKnockSolve(const StepAttempt& a, uint32_t ldsMeta) {
+    if (!(knobs.knockout & 0xFFu) || L.dry) return MI_OK;
+    hipStream_t st = stream;
+    int rc = dbgKnockWait(knockSolve); if (rc != MI_OK) return rc;
+    knockVel.flags = gVel.flags;
+    HIP_TRY(knockVel.ensure(gVel.cap)); HIP_TRY(knockVelL.ensure(gVelL.cap));
+    HIP_TRY(hipMemcpyAsync(knockVel.p, gVel.p, gVel.cap * sizeof(float4), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(knockVelL.p, gVelL.p, gVelL.cap * sizeof(float4), hipMemcpyDeviceToDevice, st));
+#ifdef MI_DBG_TIMELINE
+    dbgTimelineKnock = dbgTimelineBuf ? dbgTimelineBuf + (size_t)persistWaves * 256 * 8 : nullptr;   // (the knock-out launch stamps into the second half)
+    if (dbgTimelineBuf) HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgTimeline), &dbgTimelineKnock, sizeof(dbgTimelineKnock), 0, hipMemcpyHostToDevice, st));
+#endif
+    const uint32_t word = (knobs.knockout & 0xFFu) >= 8u ? 0u : (knobs.knockout & 0xFFu);   // (8: the unmodified kernel through the harness — what the harness itself costs)
+    rc = dbgKnockLaunch(knockSolve, word, [&]() {
+        hipLaunchKernelGGL((k_contact_solve_persist<true, true, true>), dim3(persistWaves), dim3(64), ldsMeta, st,
+                           a.settings.num_rigid_solver_iterations, a.persistMaxSlots, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, knockVel.p, scalarsPtr(), xcdTiles.p, a.xcdListCap, bodyOwner.p, knockVelL.p, slotMeta.p, imp.p, 0u, knobs.persistResident ? 1u : 0u);
+    });
+    if (rc != MI_OK) return rc;
+#ifdef MI_DBG_TIMELINE
+    if (dbgTimelineBuf) HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dbgTimeline), &dbgTimelineBuf, sizeof(dbgTimelineBuf), 0, hipMemcpyHostToDevice, st));
+#endif
+    return MI_OK;
+}
+#endif
+#ifdef MI_DBG_TIMELINE
+// per-visit wall-clock stamps of the persistent solver, dumped after step MI_DBG_TIMELINE_STEP (tools/gpu_timeline2.sh, tools/visit_stamps.py)
+int mi_world::dbgTimelineDump() {
+    if (!usedPersist || knobs.timelineOut.empty()) return MI_OK;
+    const size_t words = (size_t)persistWaves * 256 * 8;      // (second half: the stamps of the knock-out launch of a -DMI_DBG_KNOCKOUT build)
+    if (dbgTimelineBuf && totalSteps == (unsigned long long)knobs.timelineStep) {
+        std::vector<unsigned long long> h(2 * words);
+        HIP_TRY(hipMemcpy(h.data(), dbgTimelineBuf, 2 * words * 8, hipMemcpyDeviceToHost));
+        FILE* f = fopen(knobs.timelineOut.c_str(), "wb"); if (f) { fwrite(h.data(), 8, words, f); fclose(f); }
+        f = fopen((knobs.timelineOut + ".knock").c_str(), "wb"); if (f) { fwrite(h.data() + words, 8, words, f); fclose(f); }
+    }
+    if (!dbgTimelineBuf) {
+        HIP_TRY(hipMalloc(&dbgTimelineBuf, 2 * words * 8)); HIP_TRY(hipMemset(dbgTimelineBuf, 0, 2 * words * 8));
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dbgTimeline), &dbgTimelineBuf, sizeof(dbgTimelineBuf)));
+    }
+    return MI_OK;
+}
+#endif
+#endif
 
 // mi_debug_set_solve_order, inside a synchronous step after the manifolds are known (hs = this step's counts): every manifold is given the
 // sequential colour (kOverflowColor: one lane solves that bin slot by slot), and its rank in the caller's list is remembered for the slot order.
