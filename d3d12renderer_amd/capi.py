@@ -36,6 +36,47 @@ assert ray_hit_dtype.itemsize == 40
 RAY_MISS, RAY_TERRAIN = 0xFFFFFFFF, 0xFFFFFFFE
 QUERY_RIGID_BODIES, QUERY_STATIC, QUERY_TERRAIN, QUERY_TRIGGERS, QUERY_FORCE_FIELDS = 1, 2, 4, 8, 16
 QUERY_DEFAULT = QUERY_RIGID_BODIES | QUERY_STATIC | QUERY_TERRAIN
+# mi_query_volume / mi_overlap_hit (mi_world_overlap): a collider in world space with a pose; one record per (volume, collider) that touch
+query_volume_dtype = np.dtype([("type", "<u4"), ("hull_geometry", "<u4"), ("shape", "<f4", 12), ("position", "<f4", 3), ("pad0", "<f4"),
+                               ("rotation", "<f4", 4), ("pad1", "<f4", 2)])
+overlap_hit_dtype = np.dtype([("entity", "<u4"), ("collider", "<u4"), ("object_type", "<u4"), ("volume", "<u4")])
+assert query_volume_dtype.itemsize == 96 and overlap_hit_dtype.itemsize == 16
+MI_ERR_CAPACITY = -5
+QUERY_ALL = QUERY_RIGID_BODIES | QUERY_STATIC | QUERY_TERRAIN | QUERY_TRIGGERS | QUERY_FORCE_FIELDS
+
+
+def make_volume(ctype, shape, position=(0, 0, 0), rotation=(0, 0, 0, 1), hull_geometry=0):
+    """One `query_volume_dtype` record: shape words as in mi_collider_desc::shape, the pose applied like an entity's transform."""
+    v = np.zeros(1, dtype=query_volume_dtype)
+    v["type"] = ctype; v["hull_geometry"] = hull_geometry
+    v["shape"][0, :len(shape)] = np.asarray(shape, np.float32)
+    v["position"] = np.asarray(position, np.float32); v["rotation"] = np.asarray(rotation, np.float32)
+    return v
+
+
+def sphere_volume(center, radius):
+    return make_volume(SPHERE, [*center, radius])
+
+
+def capsule_volume(a, b, radius):
+    return make_volume(CAPSULE, [*a, *b, radius])
+
+
+def cylinder_volume(a, b, radius):
+    return make_volume(CYLINDER, [*a, *b, radius])
+
+
+def box_volume(center, half_extents, rotation=None):
+    """An axis-aligned box (rotation None) or an oriented one (quaternion x, y, z, w) about `center`."""
+    c = np.asarray(center, np.float64); h = np.asarray(half_extents, np.float64)
+    if rotation is None:
+        return make_volume(AABB, [*(c - h), *(c + h)])
+    return make_volume(OBB, [*rotation, *c, *h])
+
+
+def hull_volume(geometry, position=(0, 0, 0), rotation=(0, 0, 0, 1)):
+    return make_volume(HULL, [0, 0, 0, 1, 0, 0, 0], position, rotation, geometry)
+
 
 distance_constraint = np.dtype([("local_anchor_a", "<f4", 3), ("local_anchor_b", "<f4", 3), ("global_length", "<f4")])
 ball_constraint = np.dtype([("local_anchor_a", "<f4", 3), ("local_anchor_b", "<f4", 3)])
@@ -298,6 +339,48 @@ class World:
         enqueued on the world's stream without a host synchronisation."""
         self.L.check(self.L.fn("world_raycast_device_async")(self.h, C.c_uint32(n), C.c_void_p(rays_ptr), C.c_uint32(include),
                                                               C.c_void_p(ranges_ptr or None), C.c_void_p(out_ptr)), "world_raycast_device_async")
+
+    # --- volume-overlap scene queries (which colliders touch a shape; read-only)
+    def _overlap(self, name, volumes, include, entity_ranges, capacity=None):
+        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
+        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
+        offsets = np.zeros(len(v) + 1, np.uint32)
+        total = C.c_uint32(0)
+        cap = max(16, 8 * len(v)) if capacity is None else int(capacity)   # an estimate; MI_ERR_CAPACITY tells the exact number
+        f = self.L.fn(name)
+        while True:
+            hits = np.zeros(cap, dtype=overlap_hit_dtype)
+            rc = f(self.h, C.c_uint32(len(v)), _ptr(v), C.c_uint32(include), _ptr(r), _ptr(offsets), _ptr(hits) if cap else None, C.c_uint32(cap), C.byref(total))
+            if rc == MI_ERR_CAPACITY and capacity is None:
+                cap = total.value
+                continue
+            self.L.check(rc, name)
+            return offsets, hits[:total.value]
+
+    def overlap(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_world_overlap: (offsets[count + 1], hits) in CSR form, `overlap_hit_dtype` records in ascending world collider index per volume.
+        Calls with an estimated capacity and once more with the exact one when that was too small."""
+        return self._overlap("world_overlap", volumes, include, entity_ranges)
+
+    def debug_overlap_exhaustive(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_debug_overlap_exhaustive: the same result from every collider against every volume (byte for byte what overlap returns)."""
+        return self._overlap("debug_overlap_exhaustive", volumes, include, entity_ranges)
+
+    def overlap_raw(self, volumes, include, entity_ranges, capacity, name="world_overlap"):
+        """One call with a fixed capacity: (status, offsets, hits[capacity], total) — the capacity protocol as the C caller sees it."""
+        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
+        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
+        offsets = np.zeros(len(v) + 1, np.uint32); hits = np.zeros(capacity, dtype=overlap_hit_dtype); total = C.c_uint32(0)
+        rc = self.L.fn(name)(self.h, C.c_uint32(len(v)), _ptr(v), C.c_uint32(include), _ptr(r), _ptr(offsets), _ptr(hits) if capacity else None,
+                             C.c_uint32(capacity), C.byref(total))
+        return rc, offsets, hits, total.value
+
+    def overlap_device_async(self, n, volumes_ptr, offsets_ptr, hits_ptr, capacity, total_ptr, include=QUERY_DEFAULT, ranges_ptr=0):
+        """mi_world_overlap_device_async: device buffers (volumes: n x 96 bytes; offsets: n + 1 uint32; hits: capacity x 16 bytes; total: 1 uint32),
+        enqueued on the world's stream without a host synchronisation; nothing is written past `capacity` records."""
+        self.L.check(self.L.fn("world_overlap_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_uint32(include), C.c_void_p(ranges_ptr or None),
+                                                              C.c_void_p(offsets_ptr), C.c_void_p(hits_ptr or None), C.c_uint32(capacity), C.c_void_p(total_ptr)),
+                     "world_overlap_device_async")
 
     def update_constraints(self, ctype, ids, pods):
         """getConstraint(scene, handle) = ... for many constraints of one type."""

@@ -32,6 +32,7 @@
 #include "cloth.hpp"
 #include "knobs.hpp"
 #include "kernels_query.hpp"
+#include "kernels_overlap.hpp"
 
 using namespace mi;
 
@@ -421,8 +422,16 @@ struct mi_world {
         DBuf<float4> shape, mn, mx; DBuf<QueryGrid> grid; DBuf<QPartial> partials; DBuf<uint32_t> count, start, entries, large;
         DeviceScan<uint32_t> scan; Launcher L;
         DBuf<float> rays; DBuf<uint32_t> ranges, hits;   // staging of the blocking variants
+        // overlap queries (mi_world_overlap*): the volumes' world rows, counts, and the scan between the count and the write pass
+        DBuf<float4> vShape, vMn, vMx; DBuf<uint32_t> vRange, vCount;
+        DBuf<uint32_t> vcTypeBody, vcObject; DBuf<float4> vcShape, vcPos, vcRot;   // the volumes as static colliders: what worldCollider reads
+        DeviceScan<uint32_t> scan2;
+        DBuf<float4> xShape, xMn, xMx; DBuf<QPartial> xPartials;   // the exhaustive yardstick's own collider rows, computed per call
+        DBuf<uint32_t> volumes, vOffsets, vTotal; DBuf<uint4> vHits;   // staging of the blocking variants
     } query;
     int queryBuild();
+    int overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t include, const uint32_t* rangesDev, uint32_t* offsetsDev, uint4* hitsDev, uint32_t capacity,
+                       uint32_t* totalDev, bool exhaustive, bool countOnly);
 };
 
 int mi_world::init(int dev) {
@@ -509,4 +518,4 @@ mi_world::~mi_world() {
 #include "world_capi.inc"   // the C ABI of include/mi_physics.h and include/mi_constraints.h
 #include "world_shard.inc"   // sharded world: include/mi_shard.h (tiles, ghosts, RCCL transport, exact seam, load balance)
 #include "world_state.inc"   // checkpoints, body states on the device, stage dumps, debug entry points
-#include "world_query.inc"   // ray-cast scene queries: include/mi_physics.h mi_world_raycast*
+#include "world_query.inc"   // scene queries: include/mi_physics.h mi_world_raycast*, mi_world_overlap*

@@ -1,5 +1,5 @@
-// Part of world.hip (one translation unit; #included there, after world_state.inc): batched ray-cast scene queries (include/mi_physics.h,
-// mi_world_raycast*; kernels in kernels_query.hpp).
+// Part of world.hip (one translation unit; #included there, after world_state.inc): batched scene queries (include/mi_physics.h): ray casts
+// (mi_world_raycast*; kernels in kernels_query.hpp) and volume overlaps (mi_world_overlap*; kernels in kernels_overlap.hpp).
 //
 // The query structure (world AABBs, uniform grid, large list) is built lazily on the world's stream and cached per pose epoch: every
 // internal step, upload (any topology or heightmap edit), body-state write, checkpoint load and shard import bumps mi_world::poseEpoch,
@@ -51,7 +51,7 @@ static QueryScene queryScene(mi_world* w) {
 }
 // what every variant checks first; afterwards the device holds the current scene (pending host edits uploaded)
 static int queryPrepare(mi_world* w) {
-    if (w->shard.enabled) return fail(MI_ERR_UNSUPPORTED, "ray queries on a sharded world: a rank holds only its tile");
+    if (w->shard.enabled) return fail(MI_ERR_UNSUPPORTED, "scene queries on a sharded world: a rank holds only its tile");
     return ensureUploaded(w);
 }
 // accelerated (exhaustive = false) or exhaustive ray kernel over rays already on the device
@@ -91,7 +91,91 @@ static int queryHost(mi_world* w, uint32_t count, const float* origins, const fl
     return MI_OK;
 }
 
+
+// ---- volume overlaps.  Volume rows (two launches), count pass, device scan, write pass: five launches behind the (shared) grid build, no read-back between them.
+int mi_world::overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t include, const uint32_t* rangesDev, uint32_t* offsetsDev, uint4* hitsDev,
+                             uint32_t capacity, uint32_t* totalDev, bool exhaustive, bool countOnly) {
+    QueryCache& qc = query;
+    const uint32_t nc = (uint32_t)colliders.size(), nb = (uint32_t)bodies.size();
+    if (!exhaustive) { int rc = queryBuild(); if (rc != MI_OK) return rc; }
+    HIP_TRY(qc.vShape.ensure(3 * (size_t)count)); HIP_TRY(qc.vMn.ensure(count)); HIP_TRY(qc.vMx.ensure(count));
+    HIP_TRY(qc.vRange.ensure(2 * (size_t)count)); HIP_TRY(qc.vCount.ensure((size_t)count + 1));
+    HIP_TRY(qc.vcTypeBody.ensure(2 * (size_t)count)); HIP_TRY(qc.vcObject.ensure(count)); HIP_TRY(qc.vcShape.ensure(3 * (size_t)count)); HIP_TRY(qc.vcPos.ensure(count)); HIP_TRY(qc.vcRot.ensure(count));
+    OverlapScene s{};
+    s.nc = nc; s.cEntity = cEntity.p; s.hs = HullSet{hullVerts.p, hullRanges.p};
+    Launcher& L = qc.L;
+    L.begin(false, false);
+    if (exhaustive) {   // its own world rows at the current poses: the yardstick does not trust the cache
+        HIP_TRY(qc.xShape.ensure(3 * (size_t)std::max(nc, 1u))); HIP_TRY(qc.xMn.ensure(std::max(nc, 1u))); HIP_TRY(qc.xMx.ensure(std::max(nc, 1u)));
+        HIP_TRY(qc.xPartials.ensure(divUp(std::max(nc, 1u), 256)));
+        if (nc) L.launch(k_q_colliders, dim3(divUp(nc, 256)), dim3(256), 0, stream, nc, nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPos.p, bRot.p, hullAabb.p,
+                         qc.xShape.p, qc.xMn.p, qc.xMx.p, qc.xPartials.p);
+        s.shape = qc.xShape.p; s.mn = qc.xMn.p; s.mx = qc.xMx.p;
+    } else { s.shape = qc.shape.p; s.mn = qc.mn.p; s.mx = qc.mx.p; }
+    const dim3 grid(divUp(count, kOvWaves)), block(64 * kOvWaves);
+    L.launch(k_ov_unpack, dim3(divUp(count, 256)), dim3(256), 0, stream, count, volumesDev, rangesDev, (uint32_t)hulls.size(), qc.vcTypeBody.p, qc.vcObject.p, qc.vcShape.p,
+             qc.vcPos.p, qc.vcRot.p, qc.vRange.p);
+    L.launch(k_ov_prepare, dim3(divUp(count, 256)), dim3(256), 0, stream, count, (const uint32_t*)qc.vcTypeBody.p, (const uint32_t*)qc.vcObject.p, (const float4*)qc.vcShape.p,
+             (const float4*)qc.vcPos.p, (const float4*)qc.vcRot.p, (const float4*)hullAabb.p, qc.vShape.p, qc.vMn.p, qc.vMx.p);
+    for (uint32_t pass = 0; pass < (countOnly ? 1u : 2u); ++pass) {
+        if (exhaustive)
+            L.launch(k_q_overlap_exhaustive, grid, block, 0, stream, pass, count, include, s, (const float4*)qc.vShape.p, (const float4*)qc.vMn.p, (const float4*)qc.vMx.p,
+                     (const uint32_t*)qc.vRange.p, qc.vCount.p, (const uint32_t*)offsetsDev, hitsDev, capacity, totalDev);
+        else
+            L.launch(k_q_overlap, grid, block, 0, stream, pass, count, include, s, (const float4*)qc.vShape.p, (const float4*)qc.vMn.p, (const float4*)qc.vMx.p,
+                     (const uint32_t*)qc.vRange.p, (const QueryGrid*)qc.grid.p, (const uint32_t*)qc.start.p, (const uint32_t*)qc.entries.p, (const uint32_t*)qc.large.p,
+                     qc.vCount.p, (const uint32_t*)offsetsDev, hitsDev, capacity, totalDev);
+        if (pass == 0u) HIP_TRY(qc.scan2.run(L, qc.vCount.p, offsetsDev, count + 1u, stream, false));
+    }
+    if (L.firstError != hipSuccess) return fail(MI_ERR_DEVICE, std::string("overlap query: ") + hipGetErrorString(L.firstError));
+    return MI_OK;
+}
+static int overlapHost(mi_world* w, uint32_t count, const mi_query_volume* volumes, uint32_t include, const uint32_t* ranges, uint32_t* outOffsets, mi_overlap_hit* outHits,
+                       uint32_t capacity, uint32_t* outTotal, bool exhaustive) {
+    if (!w || (count && (!volumes || !outOffsets || !outTotal || (capacity && !outHits)))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = queryPrepare(w); if (rc != MI_OK) return rc;
+    if (outTotal) *outTotal = 0u;
+    if (outOffsets) outOffsets[0] = 0u;
+    if (!count) return MI_OK;
+    mi_world::QueryCache& qc = w->query;
+    HIP_TRY(qc.volumes.ensure(kOvVolumeWords * (size_t)count)); HIP_TRY(qc.vOffsets.ensure((size_t)count + 1)); HIP_TRY(qc.vHits.ensure(std::max(capacity, 1u)));
+    HIP_TRY(hipMemcpyAsync(qc.volumes.p, volumes, (size_t)count * sizeof(mi_query_volume), hipMemcpyHostToDevice, w->stream));
+    if (ranges) {
+        HIP_TRY(qc.ranges.ensure(2 * (size_t)count));
+        HIP_TRY(hipMemcpyAsync(qc.ranges.p, ranges, 2 * (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, w->stream));
+    }
+    rc = w->overlapEnqueue(count, qc.volumes.p, include, ranges ? qc.ranges.p : nullptr, qc.vOffsets.p, qc.vHits.p, capacity, nullptr, exhaustive, capacity == 0u);
+    if (rc != MI_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(outOffsets, qc.vOffsets.p, ((size_t)count + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    const uint32_t total = outOffsets[count];
+    *outTotal = total;
+    const uint32_t n = std::min(total, capacity);
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(outHits, qc.vHits.p, (size_t)n * sizeof(mi_overlap_hit), hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(hipStreamSynchronize(w->stream));
+    }
+    if (total > capacity && (capacity || outHits)) return fail(MI_ERR_CAPACITY, "capacity < overlap records (out_total holds the number)");
+    return MI_OK;
+}
+
 extern "C" {
+
+MI_API int mi_world_overlap(mi_world* w, uint32_t count, const mi_query_volume* volumes, uint32_t include, const uint32_t* ranges2, uint32_t* outOffsets,
+                            mi_overlap_hit* outHits, uint32_t capacity, uint32_t* outTotal) {
+    return overlapHost(w, count, volumes, include, ranges2, outOffsets, outHits, capacity, outTotal, false);
+}
+MI_API int mi_debug_overlap_exhaustive(mi_world* w, uint32_t count, const mi_query_volume* volumes, uint32_t include, const uint32_t* ranges2, uint32_t* outOffsets,
+                                       mi_overlap_hit* outHits, uint32_t capacity, uint32_t* outTotal) {
+    return overlapHost(w, count, volumes, include, ranges2, outOffsets, outHits, capacity, outTotal, true);
+}
+MI_API int mi_world_overlap_device_async(mi_world* w, uint32_t count, const mi_query_volume* volumesDev, uint32_t include, const uint32_t* ranges2Dev, uint32_t* offsetsDev,
+                                         mi_overlap_hit* hitsDev, uint32_t capacity, uint32_t* totalDev) {
+    if (!w || (count && (!volumesDev || !offsetsDev || !totalDev || (capacity && !hitsDev)))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = queryPrepare(w); if (rc != MI_OK) return rc;
+    if (!count) return MI_OK;
+    return w->overlapEnqueue(count, reinterpret_cast<const uint32_t*>(volumesDev), include, ranges2Dev, offsetsDev, reinterpret_cast<uint4*>(hitsDev), capacity, totalDev, false, false);
+}
 
 MI_API int mi_world_raycast(mi_world* w, uint32_t count, const float* origins3, const float* directions3, const float* maxT, uint32_t include,
                             const uint32_t* ranges2, mi_ray_hit* out) {

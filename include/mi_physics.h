@@ -294,6 +294,52 @@ MI_API int mi_world_raycast_device_async(mi_world* world, uint32_t count, const 
 MI_API int mi_debug_raycast_exhaustive(mi_world* world, uint32_t count, const float* origins3, const float* directions3,
                                        const float* max_t, uint32_t include, const uint32_t* entity_ranges2, mi_ray_hit* out);
 
+/*
+ * Batched volume-overlap queries: which colliders touch a shape right now.  Like the ray casts they read physics_transform1 (pending
+ * host edits included), share the ray casts' grid (one build per pose epoch serves both) and change nothing a step computes.
+ *   - A query volume is a collider in world space: type = mi_collider_type (sphere, capsule, cylinder, AABB, OBB, hull), shape laid
+ *     out as mi_collider_desc::shape, hull_geometry an id of this world (hulls only), and a pose (position, rotation x,y,z,w) applied
+ *     exactly as an entity's transform is applied to a static collider: an AABB under a rotation that is not exactly (0,0,0,1) becomes
+ *     an OBB, as in the reference.  Use position 0 and rotation (0,0,0,1) for a shape given in world space.  The rotation is used as
+ *     given, like an entity's: a quaternion that is not of unit length (the zero quaternion too) is not an error and not normalised.
+ *   - World collider k is reported for volume v when (1) k's object type is selected by include (MI_QUERY_*), (2) k's entity lies in
+ *     [lo_v, hi_v) when entity_ranges2 is given, (3) the world AABBs of v and k overlap as closed intervals (a collider whose AABB is
+ *     not finite is never reported), and (4) the reference's boolean overlapCheck(A, B) is true, where A is the one of the two with
+ *     the smaller world type (sphere < capsule < cylinder < AABB < OBB < hull; a rotated AABB counts as OBB), as the trigger path
+ *     passes them; for equal types A is the volume.  This is the test a trigger of that shape runs, reference quirks included (its
+ *     sphere-vs-cylinder cap test compares a squared distance with a radius; the hull and segment-vs-box pairs are GJK with its error
+ *     paths reading as "no overlap").
+ *   - Not reported: the terrain (the reference has no boolean test against the heightmap; MI_QUERY_TERRAIN is accepted and ignored)
+ *     and cloth.  A sharded world returns MI_ERR_UNSUPPORTED.
+ *   - An invalid volume (a non-finite number among the words its type reads or in its pose, a type out of range, an unknown hull
+ *     geometry, a negative radius or half-extent, an AABB with max < min, a world AABB that overflows) reports nothing: an empty
+ *     segment, never an error.
+ *   - Result (CSR): out_offsets[count + 1], and the records of volume v at [out_offsets[v], out_offsets[v + 1]) in ascending world
+ *     collider index, each collider once.  The order is part of the contract.
+ *   - Capacity: out_total always receives the full number of records and out_offsets the full offsets.  When that number exceeds
+ *     capacity, the first `capacity` records (in result order) are written and MI_ERR_CAPACITY is returned; out_hits NULL with
+ *     capacity 0 is the count-only call and returns MI_OK.
+ */
+typedef struct mi_query_volume {   /* 96 bytes, 16-byte aligned rows: usable from the host and as a device buffer */
+    uint32_t type; uint32_t hull_geometry; float shape[12];
+    float position[3]; float pad0; float rotation[4]; float pad1[2];
+} mi_query_volume;
+typedef struct mi_overlap_hit { uint32_t entity, collider, object_type, volume; } mi_overlap_hit;   /* 16 bytes */
+MI_API int mi_world_overlap(mi_world* world, uint32_t count, const mi_query_volume* volumes, uint32_t include,
+                            const uint32_t* entity_ranges2, uint32_t* out_offsets, mi_overlap_hit* out_hits, uint32_t capacity,
+                            uint32_t* out_total);
+/* Device buffers (16-byte aligned), only enqueued on the world's stream: no host synchronisation.  The same truncation rule:
+ * total_dev[0] receives the full count (so the consumer can detect truncation), offsets_dev the full offsets, and nothing is
+ * written at or past hits_dev[capacity].  ranges2_dev may be NULL; hits_dev may be NULL when capacity is 0. */
+MI_API int mi_world_overlap_device_async(mi_world* world, uint32_t count, const mi_query_volume* volumes_dev, uint32_t include,
+                                         const uint32_t* ranges2_dev, uint32_t* offsets_dev, mi_overlap_hit* hits_dev,
+                                         uint32_t capacity, uint32_t* total_dev);
+/* The same result from every collider tested against every volume, without the grid and from collider rows computed for the
+ * call (the yardstick of the accelerated path): byte for byte equal. */
+MI_API int mi_debug_overlap_exhaustive(mi_world* world, uint32_t count, const mi_query_volume* volumes, uint32_t include,
+                                       const uint32_t* entity_ranges2, uint32_t* out_offsets, mi_overlap_hit* out_hits,
+                                       uint32_t capacity, uint32_t* out_total);
+
 /* physicsStep(scene, arena, timer, settings, dt) (src/physics/physics.cpp:1364-1413). */
 MI_API int mi_world_step(mi_world* world, const mi_step_settings* settings, float dt);
 /* n × physicsStepInternal(scene, arena, settings, dt) (src/physics/physics.cpp:1180-1362); no interpolation. */

@@ -143,6 +143,33 @@ public:
         return out;
     }
     mi_ray_hit raycast(ray r, float maxT = INFINITY, uint32_t include = MI_QUERY_DEFAULT) { return raycast(std::vector<ray>{r}, maxT, include)[0]; }
+    // Which colliders touch each volume (mi_world_overlap): CSR offsets [volumes + 1] and the records in ascending collider index; read-only.
+    struct overlap_result { std::vector<uint32_t> offsets; std::vector<mi_overlap_hit> hits; };
+    // entityRanges: empty = the whole scene, otherwise one [lo, hi) pair of entity ids per volume (2 x volumes.size() words)
+    overlap_result overlap(const std::vector<mi_query_volume>& volumes, uint32_t include = MI_QUERY_DEFAULT, const std::vector<uint32_t>& entityRanges = {}) {
+        overlap_result r; r.offsets.assign(volumes.size() + 1, 0u);
+        if (volumes.empty()) return r;
+        if (!entityRanges.empty() && entityRanges.size() != 2 * volumes.size()) throw std::invalid_argument("overlap: entityRanges needs one [lo, hi) pair per volume");
+        const uint32_t* ranges = entityRanges.empty() ? nullptr : entityRanges.data();
+        uint32_t total = 0;   // count first, then fetch: the count-only call costs one pass
+        check(mi_world_overlap(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, r.offsets.data(), nullptr, 0, &total), "mi_world_overlap");
+        r.hits.resize(total);
+        if (total) check(mi_world_overlap(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, r.offsets.data(), r.hits.data(), total, &total), "mi_world_overlap");
+        return r;
+    }
+    std::vector<mi_overlap_hit> overlapSphere(vec3 center, float radius, uint32_t include = MI_QUERY_DEFAULT) {
+        mi_query_volume v{}; v.type = MI_COLLIDER_SPHERE; v.rotation[3] = 1.f;
+        v.shape[0] = center.x; v.shape[1] = center.y; v.shape[2] = center.z; v.shape[3] = radius;
+        return overlap(std::vector<mi_query_volume>{v}, include).hits;
+    }
+    // an oriented box about `center` (rotation = quaternion x, y, z, w); the identity gives the axis-aligned test
+    std::vector<mi_overlap_hit> overlapBox(vec3 center, vec3 halfExtents, quat rotation = quat{0.f, 0.f, 0.f, 1.f}, uint32_t include = MI_QUERY_DEFAULT) {
+        mi_query_volume v{}; v.type = MI_COLLIDER_AABB;
+        v.shape[0] = -halfExtents.x; v.shape[1] = -halfExtents.y; v.shape[2] = -halfExtents.z; v.shape[3] = halfExtents.x; v.shape[4] = halfExtents.y; v.shape[5] = halfExtents.z;
+        v.position[0] = center.x; v.position[1] = center.y; v.position[2] = center.z;
+        v.rotation[0] = rotation.x; v.rotation[1] = rotation.y; v.rotation[2] = rotation.z; v.rotation[3] = rotation.w;
+        return overlap(std::vector<mi_query_volume>{v}, include).hits;
+    }
 
     // deleteConstraint / deleteAllConstraintsFromEntity / deleteAllConstraints — src/physics/physics.h:251-260
     void deleteConstraint(constraint_handle h) { check(mi_constraint_destroy(w_, h.type, h.id), "mi_constraint_destroy"); }

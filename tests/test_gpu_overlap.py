@@ -1,0 +1,362 @@
+"""Volume-overlap scene queries on the GPU (mi_world_overlap, mi_world_overlap_device_async, mi_debug_overlap_exhaustive): against the
+reference's own trigger path (shrunk and grown volumes in oracle worlds), against the numpy gaps of tests/overlap_ref.py, the
+accelerated grid walk against the exhaustive scan byte for byte, the capacity protocol, the device variant, the cache's invalidation,
+and that queries change nothing a step computes."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import overlap_ref as R
+
+pytestmark = pytest.mark.gpu
+
+RIGID, ALL = 1, 31
+SORT_BOUND = 1024   # kOvSortMax: the longest segment a wave sorts in LDS
+
+
+def _world(mi, sc, steps=0):
+    w = sc.populate(mi.create_world(0))
+    if steps:
+        w.step_fixed(sc.settings(), sc.dt, steps)
+    return w
+
+
+def _bodies(sc):
+    from d3d12renderer_amd import capi
+    return np.flatnonzero((sc.entities["kind"] == capi.ENTITY_DYNAMIC) | (sc.entities["kind"] == capi.ENTITY_KINEMATIC)).astype(np.uint32)
+
+
+def _check_result(offsets, hits, count, what=""):
+    """CSR shape, the volume column, and every segment strictly ascending in collider index."""
+    assert len(offsets) == count + 1 and offsets[0] == 0 and offsets[-1] == len(hits), what
+    assert (np.diff(offsets.astype(np.int64)) >= 0).all(), what
+    assert np.array_equal(hits["volume"], np.repeat(np.arange(count, dtype=np.uint32), np.diff(offsets.astype(np.int64)))), what
+    if len(hits) > 1:
+        same = hits["volume"][1:] == hits["volume"][:-1]
+        assert (hits["collider"][1:][same] > hits["collider"][:-1][same]).all(), what
+
+
+def _accel_equals_exhaustive(w, vols, include, ranges=None, what=""):
+    ao, ah = w.overlap(vols, include, ranges)
+    eo, eh = w.debug_overlap_exhaustive(vols, include, ranges)
+    assert ao.tobytes() == eo.tobytes(), f"{what}: offsets differ (first at {np.flatnonzero(ao != eo)[:4]})"
+    if ah.tobytes() != eh.tobytes():
+        bad = [i for i in range(len(ah)) if ah[i].tobytes() != eh[i].tobytes()]
+        raise AssertionError(f"{what}: {len(bad)} of {len(ah)} records differ; first {bad[:4]}: {ah[bad[:2]]} vs {eh[bad[:2]]}")
+    _check_result(ao, ah, len(vols), what)
+    return ao, ah
+
+
+# ---- 1. against the reference's trigger path
+@pytest.mark.parametrize("name", ["shape_zoo", "zones"])
+@pytest.mark.parametrize("settled", [False, True])
+def test_sandwiched_by_the_reference_trigger_path(mi_lib, oracle_mod, name, settled):
+    """shrunk-oracle <= query <= grown-oracle per volume, as entity sets, with no budget: wherever the reference's answer does not depend
+    on a relative 1e-3 of the volume's size, the query gives exactly it."""
+    sc = R.query_scene(name)
+    w = _world(mi_lib, sc, 300 if settled else 0)
+    vols = R.volume_set(name, settled)
+    ents = _bodies(sc)
+    states = (ents, w.get_body_states(ents)) if settled else None
+    shrunk, grown, (subset, both, ambiguous) = R.oracle_sandwich(oracle_mod, sc, vols, states)
+    offsets, hits = w.overlap(vols, include=RIGID)
+    _check_result(offsets, hits, len(vols))
+    assert (hits["object_type"] == 0).all()
+    got = R.entity_sets(offsets, hits, len(vols))
+    print(f"{name} settled={settled}: {sum(map(len, shrunk))} shrunk / {sum(map(len, got))} query / {sum(map(len, grown))} grown; both non-empty {both:.0%}, ambiguous {ambiguous:.2%}")
+    assert subset and sum(map(len, shrunk)) > 100
+    assert both > 0.5 and ambiguous <= 0.02   # the yardstick's own validity for THIS set (a condition on the inputs: seeds and boxes in overlap_ref)
+    missing = [(v, sorted(shrunk[v] - got[v])) for v in range(len(vols)) if not shrunk[v] <= got[v]]
+    extra = [(v, sorted(got[v] - grown[v])) for v in range(len(vols)) if not got[v] <= grown[v]]
+    assert not missing, f"the reference reports these even for the shrunk volume (volume, entities; types {[int(vols['type'][v]) for v, _ in missing[:6]]}): {missing[:6]}"
+    assert not extra, f"the reference reports none of these even for the grown volume (volume, entities; types {[int(vols['type'][v]) for v, _ in extra[:6]]}): {extra[:6]}"
+    w.close()
+
+
+# ---- 2. against the numpy reference
+@pytest.mark.parametrize("name", ["shape_zoo", "zones"])
+def test_closed_form_pairs_match_numpy_gaps(mi_lib, name):
+    sc = R.query_scene(name)
+    w = _world(mi_lib, sc, 40)
+    vols = np.concatenate([R.volume_set(name, False, per_type=24), R.volume_set(name, True, per_type=8)])
+    offsets, hits = w.overlap(vols, include=ALL)
+    _check_result(offsets, hits, len(vols))
+    shapes = R.scene_world_shapes(sc, *w.physics_transforms())
+    compared = skipped = overlapping = 0
+    wrong = []
+    for v in range(len(vols)):
+        reported = set(int(k) for k in hits["collider"][offsets[v]:offsets[v + 1]])
+        vs = R.volume_world_shape(vols[v])
+        for k, (ent, obj, ks) in enumerate(shapes):
+            gap = R.signed_gap(vs, ks)
+            if gap is None:
+                continue
+            if abs(gap) <= 1e-4:
+                skipped += 1
+                continue
+            compared += 1
+            overlapping += gap < 0
+            if (k in reported) != (gap < 0):
+                wrong.append((v, k, float(gap)))
+    for rec in hits[:: max(1, len(hits) // 64)]:   # the records' other columns
+        ent, obj, _ = shapes[int(rec["collider"])]
+        assert rec["entity"] == ent and rec["object_type"] == obj
+    print(f"{name}: {compared} pairs compared ({overlapping} overlapping), {skipped} within 1e-4 not compared")
+    assert not wrong, f"(volume, collider, gap): {wrong[:8]}"
+    assert overlapping > 200 and skipped < 0.01 * (compared + skipped)
+    if name == "zones":   # statics, triggers and force fields are reported under include = ALL
+        assert {1, 2, 3} <= set(int(t) for t in hits["object_type"])
+    w.close()
+
+
+# ---- 3. accelerated equals exhaustive
+def _edge_volumes(rng, lo, hi, hull_ok):
+    """Inside the grid, partly outside, wholly outside, larger than the whole grid, zero-radius spheres, invalid volumes."""
+    from d3d12renderer_amd import capi
+    lo = np.asarray(lo, float); hi = np.asarray(hi, float); span = hi - lo
+    parts = [R.make_volumes(int(rng.integers(1 << 30)), 40, lo, hi, 0.15, 0.04 * float(span.max()) + 1.0),            # inside
+             R.make_volumes(int(rng.integers(1 << 30)), 8, lo - 0.1 * span, hi + 0.1 * span, 0.5, 0.3 * float(span.max())),   # partly outside, many cells
+             R.make_volumes(int(rng.integers(1 << 30)), 4, hi + 2.0 * span, hi + 3.0 * span, 0.5, 3.0)]                  # wholly outside
+    big = [capi.sphere_volume((lo + hi) / 2, 4.0 * float(span.max())), capi.box_volume((lo + hi) / 2, 3.0 * span),
+           capi.box_volume(lo, 2.5 * span, rotation=(0.1, 0.2, 0.3, 0.9)), capi.capsule_volume(lo - span, hi + span, 0.5 * float(span.max()))]
+    zero = [capi.sphere_volume(rng.uniform(lo, hi), 0.0) for _ in range(16)]
+    bad = [capi.sphere_volume((np.nan, 0, 0), 1.0), capi.sphere_volume((0, 1, 0), -1.0), capi.sphere_volume((0, 1, 0), np.inf),
+           capi.make_volume(9, [0, 0, 0, 1]), capi.make_volume(0xFF, [0, 0, 0, 1]), capi.hull_volume(99), capi.box_volume((0, 1, 0), (-1, 1, 1)),
+           capi.box_volume((0, 1, 0), (1, -1, 1), rotation=(0, 0, 0, 1)), capi.capsule_volume((0, 0, 0), (0, 1, 0), -0.5),
+           capi.make_volume(capi.SPHERE, [0, 1, 0, 50.0], position=(np.inf, 0, 0)), capi.make_volume(capi.SPHERE, [0, 1, 0, 50.0], rotation=(0, np.nan, 0, 1)),
+           capi.make_volume(capi.SPHERE, [0, 1, 0, 50.0], position=(3e38, 3e38, 0), rotation=(0, 0, 1, 0))]
+    vols = np.concatenate(parts + big + zero + bad)
+    if not hull_ok:
+        vols = vols[vols["type"] != capi.HULL]
+    n_bad = len([b for b in bad if hull_ok or b["type"][0] != capi.HULL])
+    return vols, n_bad
+
+
+def _dense_cluster():
+    """3000 static spheres in a unit cube (many per grid cell) and a sparse ring of bodies that keeps the cells small: a volume over the
+    cube walks a few hundred cells and reports far more than the LDS sort bound."""
+    from d3d12renderer_amd import capi, scenes
+    rng = np.random.default_rng(77)
+    n, m = 3000, 64
+    e = np.concatenate([scenes.make_entities(m), scenes.make_entities(n, capi.ENTITY_STATIC)])
+    ang = np.linspace(0, 2 * np.pi, m, endpoint=False)
+    e["position"][:m] = np.stack([12 * np.cos(ang), np.full(m, 1.0), 12 * np.sin(ang)], axis=1)
+    e["position"][m:] = rng.uniform(0.0, 1.0, (n, 3)) + (0, 0.5, 0)
+    c = scenes.make_colliders(n + m, capi.SPHERE)
+    c["shape"][:, 3] = 0.1
+    return scenes.Scene("dense_cluster", e, np.arange(n + m, dtype=np.uint32), c, 10)
+
+
+def test_accelerated_equals_exhaustive(mi_lib):
+    from d3d12renderer_amd import capi, scenes
+    rng = np.random.default_rng(15)
+    cases = [(R.query_scene("shape_zoo"), 30, (-7, -1, -7), (7, 8, 7), True),
+             (scenes.obb_pile(128, 4, 128), 60, (-100, -1, -100), (100, 8, 100), False),
+             (scenes.terrain_field(), 30, (-18, -1, -18), (18, 10, 18), False)]
+    for sc, steps, lo, hi, hull_ok in cases:
+        w = _world(mi_lib, sc, steps)
+        vols, n_bad = _edge_volumes(rng, lo, hi, hull_ok)
+        offsets, hits = _accel_equals_exhaustive(w, vols, ALL, what=sc.name)
+        counts = np.diff(offsets.astype(np.int64))
+        assert (counts[-n_bad:] == 0).all(), f"{sc.name}: an invalid volume reported something"
+        assert (counts == 0).any() and (counts > 0).any() and counts.max() > 0.5 * len(sc.colliders), sc.name   # (the giant sphere)
+        if len(sc.colliders) > 10000:
+            assert (counts > SORT_BOUND).any(), sc.name
+        n_ent = len(sc.entities)
+        lo_e = rng.integers(0, n_ent, len(vols)).astype(np.uint32)
+        ranges = np.stack([lo_e, np.minimum(lo_e + rng.integers(1, max(2, n_ent // 4), len(vols)), n_ent)], axis=1).astype(np.uint32)
+        ranges[::5] = (0, 0xFFFFFFFF)
+        ro, rh = _accel_equals_exhaustive(w, vols, ALL, ranges, what=f"{sc.name} ranges")
+        per_hit = ranges[rh["volume"]]
+        assert ((rh["entity"] >= per_hit[:, 0]) & (rh["entity"] < per_hit[:, 1])).all(), sc.name
+        sub = vols[:: max(1, len(vols) // 96)]
+        for include in range(32):
+            mo, mh = _accel_equals_exhaustive(w, sub, include, what=f"{sc.name} include {include}")
+            flags = np.array([2 ** 0, 2 ** 1, 2 ** 4, 2 ** 3])[mh["object_type"]] if len(mh) else np.zeros(0, int)
+            assert ((flags & include) != 0).all(), (sc.name, include)
+            if include in (0, 4):   # nothing selected; the terrain is accepted and ignored
+                assert len(mh) == 0
+        w.close()
+    # segments beyond the LDS sort bound out of a walk over few cells
+    sc = _dense_cluster()
+    w = _world(mi_lib, sc)
+    vols = np.concatenate([capi.box_volume((0.5, 1.0, 0.5), (0.6, 0.6, 0.6)), capi.sphere_volume((0.5, 1.0, 0.5), 0.45), capi.sphere_volume((0.2, 0.8, 0.3), 0.3),
+                           capi.box_volume((0.5, 1.0, 0.5), (0.7, 0.7, 0.7), rotation=(0.0, 0.38268343, 0.0, 0.92387953)), capi.sphere_volume((12.0, 1.0, 0.0), 0.2),
+                           R.make_volumes(5, 6, (0, 0.5, 0), (1, 1.5, 1), 0.05, 0.5)])
+    offsets, hits = _accel_equals_exhaustive(w, vols, ALL, what="dense cluster")
+    counts = np.diff(offsets.astype(np.int64))
+    assert counts[0] == 3000 and counts[1] > SORT_BOUND and 0 < counts[2] <= SORT_BOUND and counts[4] == 1, counts[:5]
+    w.close()
+
+
+# ---- 4. capacity protocol
+def test_capacity_protocol(mi_lib):
+    from d3d12renderer_amd import capi
+    import torch
+    sc = R.query_scene("shape_zoo")
+    w = _world(mi_lib, sc, 20)
+    vols = R.volume_set("shape_zoo", False)
+    offsets, hits = w.overlap(vols, include=ALL)
+    total = len(hits)
+    assert total > 50
+    rc, o, h, t = w.overlap_raw(vols, ALL, None, 0)                       # count only
+    assert rc == 0 and t == total and o.tobytes() == offsets.tobytes()
+    rc, o, h, t = w.overlap_raw(vols, ALL, None, total)                   # exact capacity
+    assert rc == 0 and t == total and o.tobytes() == offsets.tobytes() and h.tobytes() == hits.tobytes()
+    for name in ("world_overlap", "debug_overlap_exhaustive"):
+        for cap in (total - 1, total // 2, 1):                            # short: the prefix, full offsets and total
+            rc, o, h, t = w.overlap_raw(vols, ALL, None, cap, name=name)
+            assert rc == capi.MI_ERR_CAPACITY == -5 and t == total and o.tobytes() == offsets.tobytes(), (name, cap)
+            assert h.tobytes() == hits[:cap].tobytes(), (name, cap)
+    # the device variant writes nothing at or past `capacity`
+    vols_d = torch.tensor(np.frombuffer(vols.tobytes(), np.uint8).copy(), device="cuda")
+    off_d = torch.zeros(len(vols) + 1, dtype=torch.int32, device="cuda"); tot_d = torch.zeros(1, dtype=torch.int32, device="cuda")
+    for cap in (total // 3, total - 1, total, 0):
+        buf = torch.full(((cap + 64) * 16,), 0xAB, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        w.overlap_device_async(len(vols), vols_d.data_ptr(), off_d.data_ptr(), buf.data_ptr(), cap, tot_d.data_ptr(), include=ALL)
+        w.overlap(vols[:1], include=0)   # (a blocking call: synchronises the world's stream)
+        out = buf.cpu().numpy()
+        assert (out[cap * 16:] == 0xAB).all(), cap
+        assert out[: cap * 16].tobytes() == hits[:cap].tobytes(), cap
+        assert int(tot_d.cpu()[0]) == total and off_d.cpu().numpy().view(np.uint32).tobytes() == offsets.tobytes(), cap
+    w.close()
+
+
+# ---- 5. device variant
+def test_device_variant_equals_host_variant(mi_lib):
+    import torch
+    sc = R.query_scene("shape_zoo")
+    w = _world(mi_lib, sc, 10)
+    rng = np.random.default_rng(4)
+    vols = np.concatenate([R.volume_set("shape_zoo", False), R.volume_set("shape_zoo", True)])
+    cap = 16384
+    vols_d = torch.tensor(np.frombuffer(vols.tobytes(), np.uint8).copy(), device="cuda")
+    off_d = torch.zeros(len(vols) + 1, dtype=torch.int32, device="cuda"); tot_d = torch.zeros(1, dtype=torch.int32, device="cuda")
+    hits_d = torch.zeros(cap * 16, dtype=torch.uint8, device="cuda")
+    lo_e = rng.integers(0, len(sc.entities), len(vols)).astype(np.uint32)
+    ranges = np.stack([lo_e, lo_e + 60], axis=1).astype(np.uint32)
+    ranges_d = torch.tensor(ranges.view(np.int32), device="cuda")
+    torch.cuda.synchronize()
+
+    def device_result():
+        total = int(tot_d.cpu()[0])
+        return off_d.cpu().numpy().view(np.uint32).tobytes(), hits_d.cpu().numpy()[: total * 16].tobytes()
+
+    previous = None
+    for _ in range(2):
+        w.step_fixed(sc.settings(), sc.dt, 1)
+        w.overlap_device_async(len(vols), vols_d.data_ptr(), off_d.data_ptr(), hits_d.data_ptr(), cap, tot_d.data_ptr(), include=ALL)   # right behind the step
+        offsets, hits = w.overlap(vols, include=ALL)                                                                                # (synchronises that stream)
+        dev = device_result()
+        assert len(hits) <= cap and dev == (offsets.tobytes(), hits.tobytes())
+        assert previous is None or dev != previous
+        previous = dev
+        w.overlap_device_async(len(vols), vols_d.data_ptr(), off_d.data_ptr(), hits_d.data_ptr(), cap, tot_d.data_ptr(), include=RIGID, ranges_ptr=ranges_d.data_ptr())
+        offsets, hits = w.overlap(vols, include=RIGID, entity_ranges=ranges)
+        assert device_result() == (offsets.tobytes(), hits.tobytes())
+        w.step_fixed(sc.settings(), sc.dt, 20)
+    w.close()
+
+
+# ---- 6. the cache
+def test_cache_follows_every_change(mi_lib):
+    from d3d12renderer_amd import capi, scenes
+    import torch
+    sc = scenes.shape_zoo(3, 2, 3)
+    w = _world(mi_lib, sc, 5)
+    vols = np.concatenate([R.make_volumes(9, 16, (-4, 0, -4), (4, 5, 4), 0.2, 3.0),
+                           R.make_volumes(10, 2, (-45, 0, -45), (45, 6, 45), 1.0, 4.0)])
+    rng = np.random.default_rng(2)
+    ro = rng.uniform((-4, -1, -4), (4, 6, 4), (512, 3)).astype(np.float32)
+    rd = rng.normal(size=(512, 3)); rd = (rd / np.linalg.norm(rd, axis=1, keepdims=True)).astype(np.float32)
+
+    def check(what):
+        return _accel_equals_exhaustive(w, vols, ALL, what=what)
+
+    def around(p, r=0.5):
+        o, h = w.overlap(capi.sphere_volume(p, r), include=ALL)
+        return set(int(e) for e in h["entity"])
+
+    check("start")
+    w.step_fixed(sc.settings(), sc.dt, 1); check("step")
+    st = w.get_body_states([3]); st[0, :3] = (40.0, 3.0, -35.0); w.set_body_states([3], st)      # host write: far from the grid the last query built
+    assert around((40.0, 3.0, -35.0)) == {3}; check("set_body_states")
+    body = w.entities_to_bodies([4])
+    st = w.get_body_states([4]); st[0, :3] = (-30.0, 2.0, 33.0)
+    ids = torch.tensor(body.astype(np.int32), device="cuda"); sd = torch.tensor(st, device="cuda")
+    torch.cuda.synchronize()
+    w.set_body_states_device_async(1, ids.data_ptr(), sd.data_ptr())                            # device write on the world's stream
+    assert around((-30.0, 2.0, 33.0)) == {4}; check("set_body_states_device_async")
+    blob = w.save_checkpoint()
+    before = w.overlap(vols, include=ALL)
+    w.step_fixed(sc.settings(), sc.dt, 10)
+    after = check("steps")
+    assert after[1].tobytes() != before[1].tobytes()
+    w.load_checkpoint(blob)
+    again = w.overlap(vols, include=ALL)
+    assert again[0].tobytes() == before[0].tobytes() and again[1].tobytes() == before[1].tobytes(); check("load_checkpoint")
+    w.destroy_entity(3)
+    assert around((40.0, 3.0, -35.0)) == set(); check("destroy")
+    e = w.create_entities(scenes.make_entities(1, capi.ENTITY_STATIC))
+    c = scenes.make_colliders(1, capi.SPHERE); c["shape"][0, :4] = (25.0, 4.0, 25.0, 1.0)
+    w.add_colliders([e], c)
+    o, h = w.overlap(capi.sphere_volume((25.0, 5.2, 25.0), 0.3), include=ALL)
+    assert len(h) == 1 and h["entity"][0] == e and h["object_type"][0] == 1; check("collider add")
+    # rays and volumes interleaved in one pose epoch share one build
+    w.step_fixed(sc.settings(), sc.dt, 1)
+    for i in range(3):
+        a = w.raycast(ro, rd, include=ALL); check(f"interleaved {i}")
+        assert a.tobytes() == w.debug_raycast_exhaustive(ro, rd, include=ALL).tobytes()
+        assert a.tobytes() == w.raycast(ro, rd, include=ALL).tobytes()
+    w.close()
+
+
+# ---- 7. queries change nothing
+def test_queries_change_nothing(mi_lib):
+    sc = R.query_scene("shape_zoo")
+    a = _world(mi_lib, sc); b = _world(mi_lib, sc)
+    vols = np.concatenate([R.volume_set("shape_zoo", False), R.volume_set("shape_zoo", True)])
+    s = sc.settings()
+    ents = _bodies(sc)
+    for i in range(100):
+        a.step_fixed(s, sc.dt, 1); b.step_fixed(s, sc.dt, 1)
+        b.overlap(vols, include=ALL)
+        if i % 10 == 0:
+            b.debug_overlap_exhaustive(vols, include=RIGID)
+    assert a.get_body_states(ents).tobytes() == b.get_body_states(ents).tobytes()
+    assert a.debug_step_ahead_stats() == b.debug_step_ahead_stats()
+    a.close(); b.close()
+
+
+# ---- 8. errors
+def test_errors(mi_lib):
+    from d3d12renderer_amd import capi, scenes, sharding
+    sc = scenes.shape_zoo(2, 1, 2)
+    w = _world(mi_lib, sc)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    vol = capi.sphere_volume((0, 1, 0), 5.0); off = np.zeros(2, np.uint32); hits = np.zeros(64, capi.overlap_hit_dtype); total = C.c_uint32(7)
+    u = C.c_uint32
+    for name in ("world_overlap", "debug_overlap_exhaustive"):
+        f = w.L.fn(name)
+        assert f(None, u(1), p(vol), u(ALL), None, p(off), p(hits), u(64), C.byref(total)) == -1
+        assert f(w.h, u(1), None, u(ALL), None, p(off), p(hits), u(64), C.byref(total)) == -1
+        assert f(w.h, u(1), p(vol), u(ALL), None, None, p(hits), u(64), C.byref(total)) == -1
+        assert f(w.h, u(1), p(vol), u(ALL), None, p(off), None, u(64), C.byref(total)) == -1
+        assert f(w.h, u(1), p(vol), u(ALL), None, p(off), p(hits), u(64), None) == -1
+        assert f(w.h, u(0), None, u(ALL), None, None, None, u(0), None) == 0
+        assert f(w.h, u(0), None, u(ALL), None, p(off), None, u(0), C.byref(total)) == 0 and total.value == 0 and off[0] == 0
+        assert f(w.h, u(1), p(vol), u(ALL), None, p(off), p(hits), u(64), C.byref(total)) == 0 and total.value == off[1] >= 4
+    d = w.L.fn("world_overlap_device_async")
+    assert d(w.h, u(1), None, u(ALL), None, None, None, u(0), None) == -1
+    assert d(None, u(1), None, u(ALL), None, None, None, u(0), None) == -1
+    assert d(w.h, u(0), None, u(ALL), None, None, None, u(0), None) == 0
+    o, h = w.overlap(np.zeros(0, capi.query_volume_dtype))
+    assert len(o) == 1 and o[0] == 0 and len(h) == 0
+    w.close()
+    w = _world(mi_lib, sc)
+    w.shard_enable(sharding._desc_for(sharding.tile_grid(sc, 1), 0))
+    for name in ("world_overlap", "debug_overlap_exhaustive"):
+        assert w.L.fn(name)(w.h, u(1), p(vol), u(ALL), None, p(off), p(hits), u(64), C.byref(total)) == -6
+    w.close()
