@@ -1,4 +1,11 @@
 // kernels_broad.hpp — world-space colliders and the broad phase (grid + counting sort, pair kernels, bucket partition, pair statistics).
+//   worldCollider / ColliderRows     one collider's world shape + AABB; the rows it reads and writes as one kernel argument (also used by the scene queries)
+//   boxInfo, classifyBox, cellKey, extentCount / extentFlush, axisAccumulate / axisWaveReduce, boundsWaveReduce / boundsOfRows
+//                                    lane-level pieces of the classification: the five first-step kernels and k_bp_prepare (every later step) are made of them
+//   largeLimit, gridFit, gridWrite   grid set-up; the threshold rule differs: k_bp_threshold (first step) / nextStepThreshold (pairFinishStats, later steps)
+//   pairStage / pairFlush            LDS staging and block flush of both pair passes
+//   bpPairsGridBody = bpColumnRange (column header) + bpWalkCandidates (candidate walk) + pairKey, pairStage + pairFlush;  bpPairsLargeBody;  k_bp_pairs runs both
+//   pairFinishCounts / pairFinishStats, k_pair_partition     what a step's pair list ends with; next sweep axis and next grid
 // Part of the ONE translation unit of the physics library (world.hip includes kernels.hpp, which includes the stage files in pipeline order).
 #pragma once   // (included by kernels.hpp only, after the stage files before it)
 
@@ -23,35 +30,43 @@ __device__ inline void boxToAABB(V3 lmn, V3 lmx, Q4 rot, V3 tr, V3& mn, V3& mx) 
     growBox(mn, mx, rotate(rot, lmx) + tr);
 }
 
+// The rows one collider's world shape and AABB are made from and written to, as ONE kernel argument (the host fills it per pose set and output row set:
+// mi_world::colliderRows).  No padding bytes: a step's signature hashes the argument as it lies in memory (launcher.hpp).
+struct ColliderRows {
+    const uint32_t* cTypeBody;   // [2*nc]: type, body (kNoBody = static); null in k_bp_prepare: not fused, aabbMin / aabbMax hold this step's rows already
+    const uint32_t* cObject;     // colliders without a body: physics_object_type | object index << 8 (static / force field / trigger)
+    const float4* cShape; const float4* cStaticPos; const float4* cStaticRot;
+    const float4* bPos; const float4* bRot;
+    const float4* hullAabb;      // [2*numHulls]
+    float4* wShape; float4* aabbMin; float4* aabbMax;
+    const uint8_t* bodyActive;       // sharded world: 0 = body not simulated by this rank this step, or null
+    const uint8_t* bodyActivePrev;   // ... and in the previous step
+    uint32_t nb, unused;
+};
+static_assert(std::has_unique_object_representations_v<ColliderRows>, "hashed byte by byte into the step's signature");
+
 // one collider: world shape + AABB rows (written unless the collider is dead in this and the previous step: its rows already hold the dead box);
-// mnOut / mxOut = the rows in either case
-__device__ __forceinline__ void worldCollider(
-    uint32_t k, uint32_t nb, const uint32_t* __restrict__ cTypeBody,  // [2*nc]: type, body (kNoBody = static)
-    const uint32_t* __restrict__ cObject,   // colliders without a body: physics_object_type | object index << 8 (static / force field / trigger)
-    const float4* __restrict__ cShape, const float4* __restrict__ cStaticPos, const float4* __restrict__ cStaticRot,
-    const float4* __restrict__ bPos, const float4* __restrict__ bRot,
-    const float4* __restrict__ hullAabb,  // [2*numHulls]
-    float4* __restrict__ wShape, float4* __restrict__ aabbMin, float4* __restrict__ aabbMax,
-    const uint8_t* __restrict__ bodyActive /* sharded world: 0 = body not simulated by this rank this step, or null */,
-    const uint8_t* __restrict__ bodyActivePrev /* ... and in the previous step */, float4& mnOut, float4& mxOut) {
-    uint32_t type = cTypeBody[2 * k], body = cTypeBody[2 * k + 1];
-    if (bodyActive && body != kNoBody && !bodyActive[body]) {
+// mnOut / mxOut = the rows in either case.  SHARDED = false: the caller knows there are no shard flags (scene queries), and the dead branch is not compiled.
+template <bool SHARDED = true>
+__device__ __forceinline__ void worldCollider(uint32_t k, const ColliderRows& r, float4& mnOut, float4& mxOut) {
+    uint32_t type = r.cTypeBody[2 * k], body = r.cTypeBody[2 * k + 1];
+    if (SHARDED && r.bodyActive && body != kNoBody && !r.bodyActive[body]) {
         // a DEAD collider: inverted box (overlaps nothing, centre exactly 0 so the axis statistics are unaffected), skipped by the grid
         mnOut = make_float4(kDeadBox, kDeadBox, kDeadBox, __uint_as_float(type | (OBJ_RIGID_BODY << 8)));
         mxOut = make_float4(-kDeadBox, -kDeadBox, -kDeadBox, __uint_as_float(body));
-        if (!bodyActivePrev[body]) return;   // dead before as well: its rows already hold this (most colliders of a many-tile scene, every step)
-        wShape[3 * k] = make_float4(0, 0, 0, 0); wShape[3 * k + 1] = make_float4(0, 0, 0, 0); wShape[3 * k + 2] = make_float4(0, 0, 0, 1);
-        aabbMin[k] = mnOut; aabbMax[k] = mxOut;
+        if (!r.bodyActivePrev[body]) return;   // dead before as well: its rows already hold this (most colliders of a many-tile scene, every step)
+        r.wShape[3 * k] = make_float4(0, 0, 0, 0); r.wShape[3 * k + 1] = make_float4(0, 0, 0, 0); r.wShape[3 * k + 2] = make_float4(0, 0, 0, 1);
+        r.aabbMin[k] = mnOut; r.aabbMax[k] = mxOut;
         return;
     }
     V3 tp; Q4 tr; uint32_t objType, objIndex;
-    if (body != kNoBody) { tp = xyz(bPos[body]); tr = toQ(bRot[body]); objType = OBJ_RIGID_BODY; objIndex = body; }
+    if (body != kNoBody) { tp = xyz(r.bPos[body]); tr = toQ(r.bRot[body]); objType = OBJ_RIGID_BODY; objIndex = body; }
     else {
-        tp = xyz(cStaticPos[k]); tr = toQ(cStaticRot[k]);
-        uint32_t o = cObject[k];
-        objType = o & 0xFFu; objIndex = objType == OBJ_STATIC ? nb : (o >> 8);
+        tp = xyz(r.cStaticPos[k]); tr = toQ(r.cStaticRot[k]);
+        uint32_t o = r.cObject[k];
+        objType = o & 0xFFu; objIndex = objType == OBJ_STATIC ? r.nb : (o >> 8);
     }
-    float4 s0 = cShape[3 * k], s1 = cShape[3 * k + 1], s2 = cShape[3 * k + 2];
+    float4 s0 = r.cShape[3 * k], s1 = r.cShape[3 * k + 1], s2 = r.cShape[3 * k + 2];
     float4 o0 = make_float4(0, 0, 0, 0), o1 = o0, o2 = make_float4(0, 0, 0, 1);
     V3 mn, mx;
     uint32_t wtype = type;
@@ -99,27 +114,22 @@ __device__ __forceinline__ void worldCollider(
             Q4 lrot(s0.x, s0.y, s0.z, s0.w); V3 lp(s1.x, s1.y, s1.z);
             uint32_t geom = __float_as_uint(s1.w);
             Q4 wrot = tr * lrot; V3 wp = rotate(tr, lp) + tp;
-            boxToAABB(xyz(hullAabb[2 * geom]), xyz(hullAabb[2 * geom + 1]), wrot, wp, mn, mx);
+            boxToAABB(xyz(r.hullAabb[2 * geom]), xyz(r.hullAabb[2 * geom + 1]), wrot, wp, mn, mx);
             o0 = f4(wp, s1.w); o2 = fromQ(wrot);
         } break;
     }
-    wShape[3 * k] = o0; wShape[3 * k + 1] = o1; wShape[3 * k + 2] = o2;
+    r.wShape[3 * k] = o0; r.wShape[3 * k + 1] = o1; r.wShape[3 * k + 2] = o2;
     mnOut = f4(mn, __uint_as_float(wtype | (objType << 8)));
     mxOut = f4(mx, __uint_as_float(objIndex));
-    aabbMin[k] = mnOut; aabbMax[k] = mxOut;
+    r.aabbMin[k] = mnOut; r.aabbMax[k] = mxOut;
 }
-__global__ __launch_bounds__(256) void k_world_colliders(
-    uint32_t nc, uint32_t nb, const uint32_t* __restrict__ cTypeBody, const uint32_t* __restrict__ cObject,
-    const float4* __restrict__ cShape, const float4* __restrict__ cStaticPos, const float4* __restrict__ cStaticRot,
-    const float4* __restrict__ bPos, const float4* __restrict__ bRot, const float4* __restrict__ hullAabb,
-    float4* __restrict__ wShape, float4* __restrict__ aabbMin, float4* __restrict__ aabbMax, StepScalars* sc, uint32_t axisCur,
-    const uint8_t* __restrict__ bodyActive, const uint8_t* __restrict__ bodyActivePrev,
+__global__ __launch_bounds__(256) void k_world_colliders(uint32_t nc, ColliderRows rows, StepScalars* sc, uint32_t axisCur,
     const uint32_t* __restrict__ axisDev /* sharded world: the sweep axis lives on the device (k_shard_axis, from the sums over all ranks), or null */) {
     uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k == 0) { sc->axisCur = axisDev ? *axisDev : axisCur; }   // the SAP axis chosen at the end of the previous (successful) step
     if (k >= nc) return;
     float4 mn, mx;
-    worldCollider(k, nb, cTypeBody, cObject, cShape, cStaticPos, cStaticRot, bPos, bRot, hullAabb, wShape, aabbMin, aabbMax, bodyActive, bodyActivePrev, mn, mx);
+    worldCollider(k, rows, mn, mx);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -177,7 +187,7 @@ __device__ __forceinline__ void axisAccumulate(bool counted, float cx, float cy,
     if (!counted) return;
     axisTerms(cx, v[0], v[3], v[6]); axisTerms(cy, v[1], v[4], v[7]); axisTerms(cz, v[2], v[5], v[8]);
 }
-// wave sums (any order: integers) -> sm[wave][9]; after a barrier thread 0 adds the four and writes the block's partial
+// wave sums (any order: integers) -> sm[wave][9]; after a barrier axisBlockSum adds the four
 __device__ __forceinline__ void axisWaveReduce(unsigned long long v[kAxisSums], unsigned long long (*sm)[kAxisSums]) {
     for (int off = 32; off >= 1; off >>= 1) {
 #pragma unroll
@@ -185,6 +195,62 @@ __device__ __forceinline__ void axisWaveReduce(unsigned long long v[kAxisSums], 
     }
     if ((threadIdx.x & 63u) == 0u) { for (uint32_t c = 0; c < kAxisSums; ++c) sm[threadIdx.x >> 6][c] = v[c]; }
 }
+__device__ __forceinline__ unsigned long long axisBlockSum(const unsigned long long (*sm)[kAxisSums], uint32_t c) { return sm[0][c] + sm[1][c] + sm[2][c] + sm[3][c]; }
+
+// ---- what the classification kernels share, lane by lane (first step: k_axis_partials, k_bp_classify, k_bp_cell_ids; later steps: k_bp_prepare) ----
+// What the broad phase asks of one AABB: centre, largest extent, and whether it is the inverted box of a DEAD collider (sharded world: not simulated by this rank,
+// worldCollider).  A lane without a collider holds the default.
+struct BoxInfo { float cx = 0.f, cy = 0.f, cz = 0.f, ext = 0.f; bool dead = false; };
+__device__ __forceinline__ BoxInfo boxInfo(const float4& mn, const float4& mx) {
+    BoxInfo b;
+    b.cx = (mn.x + mx.x) * 0.5f; b.cy = (mn.y + mx.y) * 0.5f; b.cz = (mn.z + mx.z) * 0.5f;
+    b.ext = fmaxr(fmaxr(mx.x - mn.x, mx.y - mn.y), mx.z - mn.z);
+    b.dead = mx.x < mn.x;
+    return b;
+}
+constexpr uint32_t kBoxSmall = 0u, kBoxLarge = 1u, kBoxDead = 2u;   // what isLarge[] holds: anything non-zero keeps the collider out of the grid
+__device__ __forceinline__ uint32_t boxClass(const BoxInfo& b, float largeThreshold) { return b.dead ? kBoxDead : b.ext > largeThreshold ? kBoxLarge : kBoxSmall; }
+__device__ __forceinline__ uint32_t cellKey(const GridParams& g, const BoxInfo& b) {
+    const uint32_t ix = min((uint32_t)fmaxr(0.f, (b.cx - g.origin[0]) * g.invCell), g.dims[0] - 1u);
+    const uint32_t iy = min((uint32_t)fmaxr(0.f, (b.cy - g.origin[1]) * g.invCell), g.dims[1] - 1u);
+    const uint32_t iz = min((uint32_t)fmaxr(0.f, (b.cz - g.origin[2]) * g.invCell), g.dims[2] - 1u);
+    return (ix * g.dims[1] + iy) * g.dims[2] + iz;
+}
+// Extent histogram of the LIVE colliders (it only steers the cell size, never results; its total = live colliders: the dead ones of a sharded world stay out).  A block
+// counts in LDS (zeroed by the caller, barrier behind it) and adds its bins to one of the shards' copies after a barrier; extentHistTotal sums the copies.
+__device__ __forceinline__ void extentCount(uint32_t* hist, const BoxInfo& b) { if (!b.dead) atomicAdd(&hist[extentBin(b.ext)], 1u); }
+__device__ __forceinline__ void extentFlush(const uint32_t* hist, Shards* sh, uint32_t block) {
+    if (hist[threadIdx.x]) atomicAdd(&sh->extentHist[block & (kShards - 1u)][threadIdx.x], hist[threadIdx.x]);
+}
+__device__ __forceinline__ uint32_t extentHistTotal(const Shards* __restrict__ sh, uint32_t bin) {
+    uint32_t v = 0;
+    for (uint32_t k = 0; k < kShards; ++k) v += sh->extentHist[k][bin];
+    return v;
+}
+// Bounds of the small colliders' centres as six ordered ints, [0..2] min and [3..5] max: per lane, reduced over the wave into rows[wave] and, after a barrier,
+// over the four rows.
+__device__ __forceinline__ int boundsEmpty(int a) { return a < 3 ? 0x7FFFFFFF : (int)0x80000000; }
+__device__ __forceinline__ void boundsMerge(int v[6], int a, int x) { v[a] = a < 3 ? min(v[a], x) : max(v[a], x); }
+__device__ __forceinline__ void boundsWaveReduce(int v[6], int (*rows)[6]) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) boundsMerge(v, a, __shfl_xor(v[a], d, 64));
+    if ((threadIdx.x & 63u) == 0u) for (int a = 0; a < 6; ++a) rows[threadIdx.x >> 6][a] = v[a];
+}
+__device__ __forceinline__ int boundsOfRows(const int (*rows)[6], int a) {
+    int x = rows[0][a];
+    for (int w = 1; w < 4; ++w) x = a < 3 ? min(x, rows[w][a]) : max(x, rows[w][a]);
+    return x;
+}
+// one collider against the threshold: a large one joins the large list, a small one's centre the lane's bounds.  Returns its class.
+__device__ __forceinline__ uint32_t classifyBox(uint32_t i, const BoxInfo& b, float largeThreshold, StepScalars* sc, uint32_t* __restrict__ largeList, int bounds[6]) {
+    const uint32_t cls = boxClass(b, largeThreshold);
+    if (cls == kBoxLarge) { uint32_t slot = atomicAdd(&sc->numLarge, 1u); largeList[slot] = i; }
+    else if (cls == kBoxSmall) { bounds[0] = bounds[3] = orderedInt(b.cx); bounds[1] = bounds[4] = orderedInt(b.cy); bounds[2] = bounds[5] = orderedInt(b.cz); }
+    return cls;
+}
+
 __global__ __launch_bounds__(256) void k_axis_partials(uint32_t nc, const float4* __restrict__ aabbMin, const float4* __restrict__ aabbMax,
                                                        unsigned long long* __restrict__ partials, Shards* sh,
                                                        const uint8_t* __restrict__ bodyActive /* sharded world: this step's body flags, or null */, uint32_t countUnowned) {
@@ -194,32 +260,34 @@ __global__ __launch_bounds__(256) void k_axis_partials(uint32_t nc, const float4
     __syncthreads();
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
     unsigned long long v[kAxisSums];
-    bool counted = false; float cx = 0.f, cy = 0.f, cz = 0.f;
+    BoxInfo b; bool counted = false;
     if (i < nc) {
         float4 mn = aabbMin[i], mx = aabbMax[i];
-        cx = (mn.x + mx.x) * 0.5f; cy = (mn.y + mx.y) * 0.5f; cz = (mn.z + mx.z) * 0.5f;
+        b = boxInfo(mn, mx);
         counted = axisCounted(mn, mx, bodyActive, countUnowned);
-        const float ext = fmaxr(fmaxr(mx.x - mn.x, mx.y - mn.y), mx.z - mn.z);
-        if (!(mx.x < mn.x)) atomicAdd(&hist[extentBin(ext)], 1u);   // only steers the cell size, never results; dead colliders (sharded world) stay out: the histogram total = live colliders
+        extentCount(hist, b);
     }
-    axisAccumulate(counted, cx, cy, cz, v);
+    axisAccumulate(counted, b.cx, b.cy, b.cz, v);
     axisWaveReduce(v, sm);
     __syncthreads();
-    if (hist[threadIdx.x]) atomicAdd(&sh->extentHist[blockIdx.x & (kShards - 1u)][threadIdx.x], hist[threadIdx.x]);
-    if (threadIdx.x < kAxisSums) partials[blockIdx.x * kAxisSums + threadIdx.x] = sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
+    extentFlush(hist, sh, blockIdx.x);
+    if (threadIdx.x < kAxisSums) partials[blockIdx.x * kAxisSums + threadIdx.x] = axisBlockSum(sm, threadIdx.x);
 }
-// Cell size = smallest extent bin edge that leaves at most `limit` colliders above it; those few "large"
-// colliders (ground, walls, outliers) are handled by the brute-force pass.
+
+// Cell size = smallest extent bin edge that leaves at most `limit` colliders above it; those few "large" colliders (ground, walls, outliers) are handled by the
+// brute-force pass, which streams numLarge x n boxes: `costCap` bounds that product.
+__device__ __forceinline__ uint32_t largeLimit(uint32_t n, uint32_t& costCap) {
+    costCap = (uint32_t)(67108864ull / (uint64_t)max(n, 1u));
+    return max(8u, min(max(16u, n / 16384u), costCap));
+}
+// A world's FIRST step: one candidate, budgeted over all nc colliders, found by a serial walk from the top bin.  (Later steps: nextStepThreshold.)
 __global__ __launch_bounds__(256) void k_bp_threshold(uint32_t nc, const Shards* __restrict__ sh, StepScalars* sc) {
     __shared__ uint32_t hist[256];
-    uint32_t v = 0;
-    for (uint32_t k = 0; k < kShards; ++k) v += sh->extentHist[k][threadIdx.x];
-    hist[threadIdx.x] = v;
+    hist[threadIdx.x] = extentHistTotal(sh, threadIdx.x);
     __syncthreads();
     if (threadIdx.x != 0) return;
-    uint32_t limit = max(16u, nc / 16384u);
-    uint32_t costCap = (uint32_t)(67108864ull / (uint64_t)max(nc, 1u));
-    limit = max(8u, min(limit, costCap));
+    uint32_t costCap;
+    const uint32_t limit = largeLimit(nc, costCap);
     uint32_t above = 0; int b = 255;
     for (; b >= 0; --b) { if (above + hist[b] > limit) break; above += hist[b]; }
     sc->largeThreshold = b < 0 ? 0.f : extentBinUpper((uint32_t)b);
@@ -231,34 +299,18 @@ __global__ __launch_bounds__(256) void k_bp_classify(uint32_t nc, const float4* 
     __shared__ int sb[4][6];
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     float thr = sc->largeThreshold;
-    int lo[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+    int bounds[6];
+    for (int a = 0; a < 6; ++a) bounds[a] = boundsEmpty(a);
     bool dead = false;
     if (i < nc) {
-        float4 mn = aabbMin[i], mx = aabbMax[i];
-        float ext = fmaxr(fmaxr(mx.x - mn.x, mx.y - mn.y), mx.z - mn.z);
-        bool large = ext > thr;
-        dead = mx.x < mn.x;                                   // sharded world: not simulated by this rank (k_world_colliders)
-        isLarge[i] = dead ? 2u : large ? 1u : 0u;             // anything non-zero keeps the collider out of the grid
-        if (dead) {}
-        else if (large) { uint32_t slot = atomicAdd(&sc->numLarge, 1u); largeList[slot] = i; }
-        else {
-            lo[0] = hi[0] = orderedInt((mn.x + mx.x) * 0.5f);
-            lo[1] = hi[1] = orderedInt((mn.y + mx.y) * 0.5f);
-            lo[2] = hi[2] = orderedInt((mn.z + mx.z) * 0.5f);
-        }
+        const BoxInfo b = boxInfo(aabbMin[i], aabbMax[i]);
+        dead = b.dead;
+        isLarge[i] = classifyBox(i, b, thr, sc, largeList, bounds);
     }
     { const unsigned long long deadMask = __ballot(dead); if (deadMask && (threadIdx.x & 63u) == 0u) atomicAdd(&sc->numDead, (uint32_t)__popcll(deadMask)); }
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], __shfl_xor(lo[a], off, 64)); hi[a] = max(hi[a], __shfl_xor(hi[a], off, 64)); }
-    uint32_t wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) for (int a = 0; a < 3; ++a) { sb[wv][a] = lo[a]; sb[wv][3 + a] = hi[a]; }
+    boundsWaveReduce(bounds, sb);
     __syncthreads();
-    if (threadIdx.x < 6) {
-        int v = sb[0][threadIdx.x];
-        for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? min(v, sb[w][threadIdx.x]) : max(v, sb[w][threadIdx.x]);
-        blockBounds[blockIdx.x * 6 + threadIdx.x] = v;
-    }
+    if (threadIdx.x < 6) blockBounds[blockIdx.x * 6 + threadIdx.x] = boundsOfRows(sb, threadIdx.x);
 }
 
 // Cell size >= `cell` (grown in steps of 1.3 x) and the grid dimensions over [lo, hi] that fit a table of cellCap cells.  The loop runs until they fit — a world
@@ -279,37 +331,29 @@ __device__ inline float gridFit(const float lo[3], const float hi[3], float cell
     dims[0] = dims[1] = dims[2] = 1u;
     return cell;
 }
-__global__ __launch_bounds__(256) void k_bp_grid_setup(uint32_t nc, uint32_t numBlocks, uint32_t cellCap, const int* __restrict__ blockBounds, StepScalars* sc, GridParams* g) {
-    __shared__ int red[4][6];
-    int v[6] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-    for (uint32_t b = threadIdx.x; b < numBlocks; b += 256)
-        for (int a = 0; a < 6; ++a) { int x = blockBounds[b * 6 + a]; v[a] = a < 3 ? min(v[a], x) : max(v[a], x); }
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { int o = __shfl_xor(v[a], d, 64); v[a] = a < 3 ? min(v[a], o) : max(v[a], o); }
-    if ((threadIdx.x & 63u) == 0) for (int a = 0; a < 6; ++a) red[threadIdx.x >> 6][a] = v[a];
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int t = 1; t < 4; ++t) for (int a = 0; a < 6; ++a) v[a] = a < 3 ? min(v[a], red[t][a]) : max(v[a], red[t][a]);
-    float thr = sc->largeThreshold;
-    float cell = thr * 1.001f + 1e-6f;
+// The grid for a threshold: cells just above it, over the bounds of the small centres (the waves' rows, behind a barrier), fitted into a table of cellCap cells (the host
+// sized the cell histogram + scan for that many).  One thread.  Returns the number of cells.
+__device__ inline uint32_t gridWrite(GridParams* g, const int (*rows)[6], float thr, uint32_t cellCap, uint32_t numLarge) {
     float lo[3], hi[3];
-    bool any = v[0] != 0x7FFFFFFF;
-    for (int a = 0; a < 3; ++a) { lo[a] = any ? fromOrderedInt(v[a]) : 0.f; hi[a] = any ? fromOrderedInt(v[3 + a]) : 0.f; }
-    cell = gridFit(lo, hi, cell, cellCap, g->dims);   // the host sized the cell table (histogram + scan) for cellCap cells
+    const bool any = boundsOfRows(rows, 0) != 0x7FFFFFFF;
+    for (int a = 0; a < 3; ++a) { lo[a] = any ? fromOrderedInt(boundsOfRows(rows, a)) : 0.f; hi[a] = any ? fromOrderedInt(boundsOfRows(rows, 3 + a)) : 0.f; }
+    const float cell = gridFit(lo, hi, thr * 1.001f + 1e-6f, cellCap, g->dims);
     g->numCells = g->dims[0] * g->dims[1] * g->dims[2];
-    sc->numCells = g->numCells;
     g->cell = cell; g->invCell = 1.f / cell;
     for (int a = 0; a < 3; ++a) g->origin[a] = lo[a];
-    g->numLarge = sc->numLarge + sc->numDead;   // everything that is not in the cell-sorted arrays
-    g->largeThreshold = thr;
+    g->numLarge = numLarge; g->largeThreshold = thr;
+    return g->numCells;
 }
-
-__device__ __forceinline__ void cellOf(const GridParams& g, float cx, float cy, float cz, uint32_t& ix, uint32_t& iy, uint32_t& iz) {
-    ix = min((uint32_t)fmaxr(0.f, (cx - g.origin[0]) * g.invCell), g.dims[0] - 1u);
-    iy = min((uint32_t)fmaxr(0.f, (cy - g.origin[1]) * g.invCell), g.dims[1] - 1u);
-    iz = min((uint32_t)fmaxr(0.f, (cz - g.origin[2]) * g.invCell), g.dims[2] - 1u);
+__global__ __launch_bounds__(256) void k_bp_grid_setup(uint32_t nc, uint32_t numBlocks, uint32_t cellCap, const int* __restrict__ blockBounds, StepScalars* sc, GridParams* g) {
+    __shared__ int red[4][6];
+    int v[6];
+    for (int a = 0; a < 6; ++a) v[a] = boundsEmpty(a);
+    for (uint32_t b = threadIdx.x; b < numBlocks; b += 256)
+        for (int a = 0; a < 6; ++a) boundsMerge(v, a, blockBounds[b * 6 + a]);
+    boundsWaveReduce(v, red);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    sc->numCells = gridWrite(g, red, sc->largeThreshold, cellCap, sc->numLarge + sc->numDead /* everything that is not in the cell-sorted arrays */);
 }
 
 // Cell id of every small collider + its arrival rank inside the cell (the returned value of the histogram atomic):
@@ -323,115 +367,93 @@ __global__ __launch_bounds__(256) void k_bp_cell_ids(uint32_t nc, const float4* 
     GridParams g = *gp;
     uint32_t key = 0xFFFFFFFFu, rank = 0;
     if (!isLarge[i]) {
-        float4 mn = aabbMin[i], mx = aabbMax[i];
-        uint32_t ix, iy, iz;
-        cellOf(g, (mn.x + mx.x) * 0.5f, (mn.y + mx.y) * 0.5f, (mn.z + mx.z) * 0.5f, ix, iy, iz);
-        key = (ix * g.dims[1] + iy) * g.dims[2] + iz;
+        key = cellKey(g, boxInfo(aabbMin[i], aabbMax[i]));
         rank = atomicAdd(&cellCount[key], 1u);
     }
     keys[i] = key; ranks[i] = rank;
 }
 
+// the shard block-skip arguments of k_bp_prepare (sharded world, all null otherwise): per collider block the body blocks its colliders' bodies lie in (x > y: always
+// visited), the body blocks that are live, and — written here — the collider blocks that hold a collider that is not dead
+struct BlockSkip { const uint2* cbRange; const uint8_t* blockLive; uint8_t* cbLive; };
+// is anything simulated, now or in the previous step, in a body block collider block cb refers to?  (No: its rows already say "dead", its partial results are empty.)
+__device__ __forceinline__ bool colliderBlockLive(const BlockSkip& skip, uint32_t cb) {
+    if (!skip.cbRange) return true;
+    const uint2 rg = skip.cbRange[cb];
+    bool any = rg.x > rg.y;
+    for (uint32_t b = rg.x; b <= rg.y && !any; ++b) any = skip.blockLive[b] != 0u;
+    if (!any && skip.cbLive[cb]) skip.cbLive[cb] = 0u;
+    return any;
+}
 
-// Steps after the first use the grid computed at the END OF THE PREVIOUS STEP (k_pair_finish): threshold, cell size, origin and dims
+// Steps after the first use the grid computed at the END OF THE PREVIOUS STEP (pairFinishStats): threshold, cell size, origin and dims
 // only steer which colliders go through the grid and how fine it is, never the pair set — every small collider still has an extent
 // <= the cell (it is classified against the same threshold), and centres outside the old bounds clamp to the rim cells, which keeps
 // neighbours neighbours.  That takes k_bp_threshold and k_bp_grid_setup off the step's critical path and lets ONE kernel do what
-// k_axis_partials, k_bp_classify and k_bp_cell_ids did: centre statistics (same fixed reduction shape), extent histogram,
+// k_axis_partials, k_bp_classify and k_bp_cell_ids do in a first step, with the same lane-level pieces: centre statistics, extent histogram,
 // dead / large / small classification, bounds of the small centres, cell id + arrival rank.
+// FUSED with k_world_colliders (rows.cTypeBody non-null): the lane computes its collider's world shape and AABB first and goes on with them in registers — one launch
+// and one pass over the AABB rows less (the grid it classifies against is the previous step's).  Not fused: rows.aabbMin / aabbMax hold this step's rows, and of the
+// rest only the shard flags are read.
 template <bool STRIDED>
-__global__ __launch_bounds__(256) void k_bp_prepare(uint32_t nc, const float4* __restrict__ aabbMin, const float4* __restrict__ aabbMax, const GridParams* __restrict__ gp,
+__global__ __launch_bounds__(256) void k_bp_prepare(uint32_t nc, ColliderRows rows, const GridParams* __restrict__ gp,
                                                     unsigned long long* __restrict__ partials, Shards* sh, StepScalars* sc, uint32_t* __restrict__ largeList, uint32_t* __restrict__ isLarge,
                                                     int* __restrict__ blockBounds, uint32_t* __restrict__ keys, uint32_t* __restrict__ ranks, uint32_t* __restrict__ cellCount,
-                                                    const uint8_t* __restrict__ bodyActivePrev /* sharded world: the previous step's body flags, or null */,
-                                                    const uint8_t* __restrict__ bodyActive /* sharded world: this step's body flags, or null */, uint32_t countUnowned,
-                                                    // FUSED with k_world_colliders (cTypeBody non-null): the lane computes its collider's world shape and AABB first and goes on
-                                                    // with them in registers — one launch and one pass over the AABB rows less (the grid it classifies against is the previous step's)
-                                                    uint32_t nb, const uint32_t* __restrict__ cTypeBody, const uint32_t* __restrict__ cObject, const float4* __restrict__ cShape,
-                                                    const float4* __restrict__ cStaticPos, const float4* __restrict__ cStaticRot, const float4* __restrict__ bPos, const float4* __restrict__ bRot,
-                                                    const float4* __restrict__ hullAabb, float4* __restrict__ wShape, float4* __restrict__ aabbMinW, float4* __restrict__ aabbMaxW,
-                                                    uint32_t axisCur, const uint32_t* __restrict__ axisDev,
-                                                    const uint2* __restrict__ cbRange /* sharded world: per collider block the body blocks its colliders' bodies lie in (x > y: always visited), or null */,
-                                                    const uint8_t* __restrict__ blockLive, uint8_t* __restrict__ cbLive) {
+                                                    uint32_t countUnowned, uint32_t axisCur, const uint32_t* __restrict__ axisDev, BlockSkip skip) {
     __shared__ unsigned long long sm[4][kAxisSums];
     __shared__ uint32_t hist[256];
     __shared__ int sb[4][6];
+    const bool fused = rows.cTypeBody != nullptr;
+    const uint8_t* __restrict__ bodyActive = rows.bodyActive; const uint8_t* __restrict__ bodyActivePrev = rows.bodyActivePrev;
   // the step's sweep axis: written by the first workgroup whatever blocks it goes on to visit (a sharded rank that simulates nothing in collider block 0 skips that block's
   // body below; the axis word must follow the exchange's axisDev all the same, or this rank orients its pairs along a stale axis)
-  if (cTypeBody && blockIdx.x == 0 && threadIdx.x == 0) sc->axisCur = axisDev ? *axisDev : axisCur;
-  // (one workgroup per collider block unless the world is sharded: then a collider block is skipped when nothing is simulated, now or in the previous step, in any body
-  // block it refers to — its rows already say "dead", its partial results are empty)
-  forLiveBlocks<STRIDED>(blockIdx.x, gridDim.x, (nc + 255u) / 256u, [&](uint32_t cb) {
-        if (!cbRange) return true;
-        const uint2 rg = cbRange[cb];
-        bool any = rg.x > rg.y;
-        for (uint32_t b = rg.x; b <= rg.y && !any; ++b) any = blockLive[b] != 0u;
-        if (!any && cbLive[cb]) cbLive[cb] = 0u;
-        return any;
-    }, [&](uint32_t cb) {
+  if (fused && blockIdx.x == 0 && threadIdx.x == 0) sc->axisCur = axisDev ? *axisDev : axisCur;
+  // (one workgroup per collider block unless the world is sharded: then the workgroups stride over the blocks that are live)
+  forLiveBlocks<STRIDED>(blockIdx.x, gridDim.x, (nc + 255u) / 256u, [&](uint32_t cb) { return colliderBlockLive(skip, cb); }, [&](uint32_t cb) {
     __syncthreads();   // (the previous block's shared results have been read)
     hist[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t i = cb * 256 + threadIdx.x;
-    if (cTypeBody && bodyActive) {
+    if (fused && bodyActive) {
         // sharded world: a workgroup whose colliders are all dead now and were dead in the previous step (7 of 8 workgroups of an 8-tile scene) has nothing to
         // compute, nothing to reduce and nothing to rewrite but its own (empty) partial results
         bool stale = true;
-        if (i < nc) { const uint32_t body = cTypeBody[2 * i + 1]; stale = body != kNoBody && !bodyActive[body] && !bodyActivePrev[body]; }
+        if (i < nc) { const uint32_t body = rows.cTypeBody[2 * i + 1]; stale = body != kNoBody && !bodyActive[body] && !bodyActivePrev[body]; }
         if (!__syncthreads_or(stale ? 0 : 1)) {
             if (threadIdx.x < kAxisSums) partials[cb * kAxisSums + threadIdx.x] = 0ull;
-            if (threadIdx.x < 6) blockBounds[cb * 6 + threadIdx.x] = threadIdx.x < 3 ? 0x7FFFFFFF : (int)0x80000000;
-            if (cbLive && threadIdx.x == 0) cbLive[cb] = 0u;
+            if (threadIdx.x < 6) blockBounds[cb * 6 + threadIdx.x] = boundsEmpty((int)threadIdx.x);
+            if (skip.cbLive && threadIdx.x == 0) skip.cbLive[cb] = 0u;
             return;
         }
     }
     const GridParams g = *gp;
     unsigned long long v[kAxisSums];
-    int lo[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-    bool dead = false, counted = false; float cx = 0.f, cy = 0.f, cz = 0.f;
+    int bounds[6];
+    for (int a = 0; a < 6; ++a) bounds[a] = boundsEmpty(a);
+    BoxInfo b; bool counted = false;
     if (i < nc) {
         float4 mn, mx;
-        if (cTypeBody) worldCollider(i, nb, cTypeBody, cObject, cShape, cStaticPos, cStaticRot, bPos, bRot, hullAabb, wShape, aabbMinW, aabbMaxW, bodyActive, bodyActivePrev, mn, mx);
-        else { mn = aabbMin[i]; mx = aabbMax[i]; }
-        cx = (mn.x + mx.x) * 0.5f; cy = (mn.y + mx.y) * 0.5f; cz = (mn.z + mx.z) * 0.5f;
+        if (fused) worldCollider(i, rows, mn, mx);
+        else { mn = rows.aabbMin[i]; mx = rows.aabbMax[i]; }
+        b = boxInfo(mn, mx);
         counted = axisCounted(mn, mx, bodyActive, countUnowned);
-        const float ext = fmaxr(fmaxr(mx.x - mn.x, mx.y - mn.y), mx.z - mn.z);
-        dead = mx.x < mn.x;
-        if (!dead) atomicAdd(&hist[extentBin(ext)], 1u);   // only steers the NEXT step's cell size; its total = live colliders (k_pair_finish derives numDead from it:
-                                                            // a counter bumped once per wave of dead colliders cost 0.3 ms in an 8-tile world, ~90 same-address atomics per us)
-        const bool large = ext > g.largeThreshold;
+        extentCount(hist, b);   // steers the NEXT step's cell size; pairFinishStats derives numDead from its total (a counter bumped once per wave of dead colliders
+                                // cost 0.3 ms in an 8-tile world, ~90 same-address atomics per us)
         // a collider that was dead in the previous step too already has (2, 0xFFFFFFFF, 0) in these rows
-        const bool stale = dead && bodyActivePrev && !bodyActivePrev[__float_as_uint(mx.w)];
-        if (!stale) isLarge[i] = dead ? 2u : large ? 1u : 0u;
+        const bool stale = b.dead && bodyActivePrev && !bodyActivePrev[__float_as_uint(mx.w)];
+        const uint32_t cls = classifyBox(i, b, g.largeThreshold, sc, largeList, bounds);
         uint32_t key = 0xFFFFFFFFu, rank = 0;
-        if (dead) {}
-        else if (large) { uint32_t slot = atomicAdd(&sc->numLarge, 1u); largeList[slot] = i; }
-        else {
-            lo[0] = hi[0] = orderedInt(cx); lo[1] = hi[1] = orderedInt(cy); lo[2] = hi[2] = orderedInt(cz);
-            uint32_t ix, iy, iz;
-            cellOf(g, cx, cy, cz, ix, iy, iz);
-            key = (ix * g.dims[1] + iy) * g.dims[2] + iz;
-            rank = atomicAdd(&cellCount[key], 1u);
-        }
-        if (!stale) { keys[i] = key; ranks[i] = rank; }
+        if (cls == kBoxSmall) { key = cellKey(g, b); rank = atomicAdd(&cellCount[key], 1u); }
+        if (!stale) { isLarge[i] = cls; keys[i] = key; ranks[i] = rank; }
     }
-    axisAccumulate(counted, cx, cy, cz, v);
+    axisAccumulate(counted, b.cx, b.cy, b.cz, v);
     axisWaveReduce(v, sm);
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], __shfl_xor(lo[a], off, 64)); hi[a] = max(hi[a], __shfl_xor(hi[a], off, 64)); }
-    }
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { for (int a = 0; a < 3; ++a) { sb[wv][a] = lo[a]; sb[wv][3 + a] = hi[a]; } }
-    const int anyAlive = __syncthreads_or((i < nc && !dead) ? 1 : 0);
-    if (cbLive && threadIdx.x == 0) cbLive[cb] = anyAlive ? 1u : 0u;
-    if (hist[threadIdx.x]) atomicAdd(&sh->extentHist[cb & (kShards - 1u)][threadIdx.x], hist[threadIdx.x]);
-    if (threadIdx.x < kAxisSums) partials[cb * kAxisSums + threadIdx.x] = sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
-    if (threadIdx.x < 6) {
-        int x = sb[0][threadIdx.x];
-        for (int w = 1; w < 4; ++w) x = threadIdx.x < 3 ? min(x, sb[w][threadIdx.x]) : max(x, sb[w][threadIdx.x]);
-        blockBounds[cb * 6 + threadIdx.x] = x;
-    }
+    boundsWaveReduce(bounds, sb);
+    const int anyAlive = __syncthreads_or((i < nc && !b.dead) ? 1 : 0);
+    if (skip.cbLive && threadIdx.x == 0) skip.cbLive[cb] = anyAlive ? 1u : 0u;
+    extentFlush(hist, sh, cb);
+    if (threadIdx.x < kAxisSums) partials[cb * kAxisSums + threadIdx.x] = axisBlockSum(sm, threadIdx.x);
+    if (threadIdx.x < 6) blockBounds[cb * 6 + threadIdx.x] = boundsOfRows(sb, threadIdx.x);
   });
 }
 
@@ -469,8 +491,9 @@ __device__ __forceinline__ bool pairKey(uint32_t i, const float4& imn, const flo
     uint32_t bi = __float_as_uint(imx.w), bj = __float_as_uint(jmx.w);
     if (oi != OBJ_RIGID_BODY && oj != OBJ_RIGID_BODY) return false;
     if (oi == OBJ_RIGID_BODY && oj == OBJ_RIGID_BODY && bi == bj) return false;
-    float mi_ = axis == 0 ? imn.x : (axis == 1 ? imn.y : imn.z);
-    float mj_ = axis == 0 ? jmn.x : (axis == 1 ? jmn.y : jmn.z);
+    const float ix = imn.x, iy = imn.y, iz = imn.z, jx = jmn.x, jy = jmn.y, jz = jmn.z;   // (read first: a select between the loads becomes an indexed load, and a box held in registers goes to scratch for it)
+    float mi_ = axis == 0 ? ix : (axis == 1 ? iy : iz);
+    float mj_ = axis == 0 ? jx : (axis == 1 ? jy : jz);
     bool iIsNew = (mi_ > mj_) || (mi_ == mj_ && i < j);
     uint32_t a = iIsNew ? i : j, b = iIsNew ? j : i;
     uint32_t ta = (iIsNew ? ti : tj) & 0xFF, tb = (iIsNew ? tj : ti) & 0xFF;
@@ -544,107 +567,131 @@ struct PairLds {
     uint32_t blockBase;
     uint32_t bhist[32];            // [0..20] bucket histogram, [31] overlaps
 };
+// Staging of both pair passes.  A lane owns CHUNKS sub-buffers of SLOTS keys in L.buf (the grid pass: one per chunk of 256 sorted colliders, kGridChunks x kPairBuf; the
+// large pass: 1 x kLargeBuf), counts the hits of each in a register (beyond SLOTS: they went to the overflow tiers) and keeps this:
+struct PairLane {
+    uint32_t overlaps = 0;        // AABB overlaps seen, keyed or not
+    uint32_t runBucket = 0, runCount = 0;   // the lane's hits go to the bucket histogram in runs (a pile: one bucket -> one LDS atomic per lane, not per hit)
+};
+// (workgroup) before the first hit of a round
+__device__ __forceinline__ void pairStageBegin(PairLds& L) {
+    if (threadIdx.x < 32) L.bhist[threadIdx.x] = 0;
+    if (threadIdx.x == 32) L.ovfCount = 0;
+    __syncthreads();
+}
+// One hit, the lane's nhit-th of chunk `ch`: into its slots; when they are full into the block-shared overflow area; when that is full too — rare — straight to the pair list.
+template <uint32_t SLOTS>
+__device__ __forceinline__ void pairStage(PairLds& L, PairLane& me, uint32_t ch, uint32_t& nhit, uint64_t pk, uint64_t* __restrict__ pairKeys, uint32_t pairCap, StepScalars* sc) {
+    if (nhit < SLOTS) L.buf[(ch * 256u + threadIdx.x) * SLOTS + nhit] = pk;
+    else {
+        const uint32_t o = atomicAdd(&L.ovfCount, 1u);
+        if (o < kPairOverflow) L.ovf[o] = pk;
+        else { uint32_t slot = atomicAdd(&sc->numPairs, 1u); if (slot < pairCap) pairKeys[slot] = pk; }
+    }
+    const uint32_t bk = (uint32_t)(pk >> 58);
+    if (bk != me.runBucket && me.runCount) { atomicAdd(&L.bhist[me.runBucket], me.runCount); me.runCount = 0; }
+    me.runBucket = bk; ++me.runCount;
+    ++nhit;
+}
+// (workgroup) Block flush: exclusive scan of the staged counts (wave shuffles + the four wave totals), ONE returning atomic on the pair list's counter for the whole
+// workgroup, copy-out — the lanes' keys in thread order, chunks in order, the overflow keys behind them — and the sum-only counters into the shard line `shardIdx`.
+template <uint32_t CHUNKS, uint32_t SLOTS>
+__device__ __forceinline__ void pairFlush(PairLds& L, PairLane& me, const uint32_t (&nhit)[CHUNKS], uint32_t shardIdx, uint64_t* __restrict__ pairKeys, uint32_t pairCap, StepScalars* sc, Shards* sh) {
+    if (me.runCount) atomicAdd(&L.bhist[me.runBucket], me.runCount);   // the lane's last run
+    uint32_t nh[CHUNKS], mine = 0;
+#pragma unroll
+    for (uint32_t ch = 0; ch < CHUNKS; ++ch) { nh[ch] = min(nhit[ch], SLOTS); mine += nh[ch]; }
+    uint32_t incl = mine;
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    for (int off = 1; off < 64; off <<= 1) { uint32_t v = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += v; }
+    if (lane == 63) L.waveTotals[wv] = incl;
+    for (int off = 32; off >= 1; off >>= 1) me.overlaps += __shfl_xor(me.overlaps, off, 64);
+    if (lane == 0 && me.overlaps) atomicAdd(&L.bhist[31], me.overlaps);
+    __syncthreads();
+    uint32_t wbase = 0;
+    for (uint32_t w = 0; w < wv; ++w) wbase += L.waveTotals[w];
+    const uint32_t staged = L.waveTotals[0] + L.waveTotals[1] + L.waveTotals[2] + L.waveTotals[3];
+    const uint32_t nOvf = min(L.ovfCount, kPairOverflow);
+    if (threadIdx.x == 0) { const uint32_t total = staged + nOvf; L.blockBase = total ? atomicAdd(&sc->numPairs, total) : 0u; }
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < nOvf; k += 256u) { const uint32_t d = L.blockBase + staged + k; if (d < pairCap) pairKeys[d] = L.ovf[k]; }
+    uint32_t dst = L.blockBase + wbase + incl - mine;
+#pragma unroll
+    for (uint32_t ch = 0; ch < CHUNKS; ++ch) {
+        const uint64_t* mybuf = L.buf + (ch * 256u + threadIdx.x) * SLOTS;
+        for (uint32_t k = 0; k < nh[ch]; ++k, ++dst) if (dst < pairCap) pairKeys[dst] = mybuf[k];
+    }
+    ShardCounters* shard = &sh->c[shardIdx & (kShards - 1u)];
+    if (threadIdx.x < kNumBuckets && L.bhist[threadIdx.x]) atomicAdd(&shard->bucketHist[threadIdx.x], L.bhist[threadIdx.x]);
+    if (threadIdx.x == 31 && L.bhist[31]) atomicAdd(&shard->numOverlaps, L.bhist[31]);
+}
+
+// Column header of the grid pass: the candidates of the sorted collider at position i (cell `key`) in forward neighbour column `col` = the range [s, e) of the sorted
+// arrays.  False: the column lies outside the grid.
+__device__ __forceinline__ bool bpColumnRange(uint32_t col, uint32_t i, uint32_t key, const GridParams* __restrict__ gp, const uint32_t* __restrict__ cellLower, uint32_t& s, uint32_t& e) {
+    const uint32_t dx = gp->dims[0], dy = gp->dims[1], dz = gp->dims[2];
+    const uint32_t iz = key % dz, iy = (key / dz) % dy, ix = key / (dz * dy);
+    const int x = (int)ix + (col >= 2 ? 1 : 0);
+    const int y = (int)iy + (col == 1 ? 1 : (col >= 2 ? (int)col - 3 : 0));
+    if (!(x < (int)dx && y >= 0 && y < (int)dy)) return false;
+    int z0 = col == 0 ? (int)iz : (int)iz - 1, z1 = (int)iz + 1;
+    if (z0 < 0) z0 = 0;
+    if (z1 >= (int)dz) z1 = (int)dz - 1;
+    const uint32_t cbase = ((uint32_t)x * dy + (uint32_t)y) * dz;
+    s = col == 0 ? i + 1u : cellLower[cbase + (uint32_t)z0];
+    e = cellLower[cbase + (uint32_t)z1 + 1u];
+    return true;
+}
+// Candidate walk of the grid pass: the rows [s, e) of the sorted arrays against the box (amn, amx), fetched kPairFetch at a time; hit(j, bmn, bmx) for every row that
+// overlaps.  (The part a faster broad phase replaces: see DESIGN.md §9.)
+template <class Hit>
+__device__ __forceinline__ void bpWalkCandidates(uint32_t s, uint32_t e, const float4& amn, const float4& amx, const float4* __restrict__ sMin, const float4* __restrict__ sMax, Hit hit) {
+    for (uint32_t j = s; j < e; j += kPairFetch) {
+        float4 bmn[kPairFetch], bmx[kPairFetch];
+#pragma unroll
+        for (uint32_t u = 0; u < kPairFetch; ++u) { uint32_t jj = min(j + u, e - 1u); bmn[u] = sMin[jj]; bmx[u] = sMax[jj]; }
+#pragma unroll
+        for (uint32_t u = 0; u < kPairFetch; ++u)
+            if (j + u < e && aabbOverlap(amn, amx, bmn[u], bmx[u])) hit(j + u, bmn[u], bmx[u]);
+    }
+}
 __device__ __forceinline__ void bpPairsGridBody(PairLds& L, const uint32_t blockId /* workgroup of the grid pass */, uint32_t nc, uint32_t blocksPerColumn, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                 const float4* __restrict__ sMin, const float4* __restrict__ sMax,
                                                 const uint32_t* __restrict__ cellLower,
                                                 const GridParams* __restrict__ gp, uint64_t* __restrict__ pairKeys, uint32_t pairCap,
                                                 StepScalars* sc, Shards* sh, InterSink inter) {
-    uint64_t* const buf = L.buf; uint64_t* const ovf = L.ovf; uint32_t& ovfCount = L.ovfCount; uint32_t* const waveTotals = L.waveTotals; uint32_t& blockBase = L.blockBase; uint32_t* const bhist = L.bhist;
     const uint32_t col = blockId / blocksPerColumn;
     // blocksPerColumn is a multiple of 8: the workgroups of one XCD (blockIdx % 8, a speed assumption only) walk ONE contiguous
     // eighth of the cell-sorted colliders instead of every eighth block of all of them, so the AABB rows they share stay in that XCD's L2
     const uint32_t inCol = blockId % blocksPerColumn;
-    const uint32_t dy = gp->dims[1], dz = gp->dims[2], dx = gp->dims[0];
     const uint32_t axis = sc->axisCur;
     const uint32_t numSmall = cellLower[gp->numCells];   // total of the cell histogram = this step's small colliders = the filled part of the sorted arrays
     // The host sizes the launch for the small colliders it EXPECTS (previous step's count + slack; a sharded world holds mostly dead
     // colliders, and an idle workgroup still costs its dispatch slot: 0.27 ms in an 8-tile world); if there are more, the workgroups go round again.
     const uint32_t perRound = blocksPerColumn * (kGridChunks * 256u);
     for (uint32_t roundBase = 0; roundBase < numSmall; roundBase += perRound) {
-    if (roundBase) __syncthreads();
-    if (threadIdx.x < 32) bhist[threadIdx.x] = 0;
-    if (threadIdx.x == 32) ovfCount = 0;
-    __syncthreads();
-    const uint32_t base = roundBase + ((inCol & 7u) * (blocksPerColumn >> 3) + (inCol >> 3)) * (kGridChunks * 256u);
-    uint32_t overlaps = 0, nh[kGridChunks];
-    uint32_t runBucket = 0, runCount = 0;   // this lane's hits go to the bucket histogram in runs (a pile: one bucket -> one LDS atomic per lane, not per hit)
+        if (roundBase) __syncthreads();
+        pairStageBegin(L);
+        const uint32_t base = roundBase + ((inCol & 7u) * (blocksPerColumn >> 3) + (inCol >> 3)) * (kGridChunks * 256u);
+        PairLane me; uint32_t nhit[kGridChunks];
 #pragma unroll
-    for (uint32_t ch = 0; ch < kGridChunks; ++ch) {
-        const uint32_t i = base + ch * 256u + threadIdx.x;
-        uint64_t* mybuf = buf + (ch * 256u + threadIdx.x) * kPairBuf;
-        uint32_t nhit = 0;
-        uint32_t key = i < numSmall ? keys[i] : 0xFFFFFFFFu;   // sorted positions [0, numSmall) hold the small colliders
-        if (key != 0xFFFFFFFFu) {
-            uint32_t iz = key % dz, iy = (key / dz) % dy, ix = key / (dz * dy);
-            int x = (int)ix + (col >= 2 ? 1 : 0);
-            int y = (int)iy + (col == 1 ? 1 : (col >= 2 ? (int)col - 3 : 0));
-            if (x < (int)dx && y >= 0 && y < (int)dy) {
-                int z0 = col == 0 ? (int)iz : (int)iz - 1, z1 = (int)iz + 1;
-                if (z0 < 0) z0 = 0;
-                if (z1 >= (int)dz) z1 = (int)dz - 1;
-                uint32_t cbase = ((uint32_t)x * dy + (uint32_t)y) * dz;
-                uint32_t s = col == 0 ? i + 1u : cellLower[cbase + (uint32_t)z0];
-                uint32_t e = cellLower[cbase + (uint32_t)z1 + 1u];
-                if (MI_BP_KNOCK(16)) e = s;
-                float4 amn = sMin[i], amx = sMax[i];
-                uint32_t ci = vals[i];
-                for (uint32_t j = s; j < e; j += kPairFetch) {
-                    float4 bmn[kPairFetch], bmx[kPairFetch];
-#pragma unroll
-                    for (uint32_t u = 0; u < kPairFetch; ++u) { uint32_t jj = min(j + u, e - 1u); bmn[u] = sMin[jj]; bmx[u] = sMax[jj]; }
-#pragma unroll
-                    for (uint32_t u = 0; u < kPairFetch; ++u) {
-                        if (j + u >= e || !aabbOverlap(amn, amx, bmn[u], bmx[u])) continue;
-                        ++overlaps;
-                        if (MI_BP_KNOCK(17)) continue;
-                        uint64_t pk;
-                        if (!pairKey(ci, amn, amx, vals[j + u], bmn[u], bmx[u], axis, pk, inter)) continue;
-                        if (nhit < kPairBuf) mybuf[nhit] = pk;
-                        else {
-                            const uint32_t o = atomicAdd(&ovfCount, 1u);
-                            if (o < kPairOverflow) ovf[o] = pk;
-                            else { uint32_t slot = atomicAdd(&sc->numPairs, 1u); if (slot < pairCap) pairKeys[slot] = pk; }   // both stagings full: rare
-                        }
-                        { const uint32_t bk = (uint32_t)(pk >> 58); if (bk != runBucket && runCount) { atomicAdd(&bhist[runBucket], runCount); runCount = 0; } runBucket = bk; ++runCount; }
-                        ++nhit;
-                    }
-                }
+        for (uint32_t ch = 0; ch < kGridChunks; ++ch) {
+            const uint32_t i = base + ch * 256u + threadIdx.x;
+            const uint32_t key = i < numSmall ? keys[i] : 0xFFFFFFFFu;   // sorted positions [0, numSmall) hold the small colliders
+            uint32_t s, e, n = 0;
+            if (key != 0xFFFFFFFFu && bpColumnRange(col, i, key, gp, cellLower, s, e) && !MI_BP_KNOCK(16) /* (knock-out harness: no candidate walk) */) {
+                const float4 amn = sMin[i], amx = sMax[i];
+                const uint32_t ci = vals[i];
+                bpWalkCandidates(s, e, amn, amx, sMin, sMax, [&](uint32_t j, const float4& bmn, const float4& bmx) {
+                    ++me.overlaps;
+                    if (MI_BP_KNOCK(17)) return;   // (no keying, no staging)
+                    uint64_t pk;
+                    if (pairKey(ci, amn, amx, vals[j], bmn, bmx, axis, pk, inter)) pairStage<kPairBuf>(L, me, ch, n, pk, pairKeys, pairCap, sc);
+                });
             }
+            nhit[ch] = n;
         }
-        nh[ch] = min(nhit, kPairBuf);
-    }
-    if (runCount) atomicAdd(&bhist[runBucket], runCount);
-    if (MI_BP_KNOCK(18)) continue;
-    // block exclusive scan of the staged counts
-    uint32_t mine = 0;
-#pragma unroll
-    for (uint32_t ch = 0; ch < kGridChunks; ++ch) mine += nh[ch];
-    uint32_t incl = mine;
-    uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    for (int off = 1; off < 64; off <<= 1) { uint32_t v = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += v; }
-    if (lane == 63) waveTotals[wv] = incl;
-    for (int off = 32; off >= 1; off >>= 1) overlaps += __shfl_xor(overlaps, off, 64);
-    if (lane == 0 && overlaps) atomicAdd(&bhist[31], overlaps);
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (uint32_t w = 0; w < wv; ++w) wbase += waveTotals[w];
-    const uint32_t staged = waveTotals[0] + waveTotals[1] + waveTotals[2] + waveTotals[3];
-    const uint32_t nOvf = min(ovfCount, kPairOverflow);
-    if (threadIdx.x == 0) {
-        const uint32_t total = staged + nOvf;
-        blockBase = total ? atomicAdd(&sc->numPairs, total) : 0u;
-    }
-    __syncthreads();
-    for (uint32_t k = threadIdx.x; k < nOvf; k += 256u) { const uint32_t d = blockBase + staged + k; if (d < pairCap) pairKeys[d] = ovf[k]; }
-    uint32_t dst = blockBase + wbase + incl - mine;
-#pragma unroll
-    for (uint32_t ch = 0; ch < kGridChunks; ++ch) {
-        const uint64_t* mybuf = buf + (ch * 256u + threadIdx.x) * kPairBuf;
-        for (uint32_t k = 0; k < nh[ch]; ++k, ++dst) if (dst < pairCap) pairKeys[dst] = mybuf[k];
-    }
-    ShardCounters* shard = &sh->c[blockId & (kShards - 1u)];
-    if (threadIdx.x < kNumBuckets && bhist[threadIdx.x]) atomicAdd(&shard->bucketHist[threadIdx.x], bhist[threadIdx.x]);
-    if (threadIdx.x == 31 && bhist[31]) atomicAdd(&shard->numOverlaps, bhist[31]);
+        if (!MI_BP_KNOCK(18)) pairFlush<kGridChunks, kPairBuf>(L, me, nhit, blockId, pairKeys, pairCap, sc, sh);   // (or: no block flush)
     }
 }
 
@@ -672,15 +719,11 @@ __device__ __forceinline__ void bpPairsLargeBody(PairLds& L, const uint32_t bx, 
     // same-address atomic per wave per hit-iteration made this kernel 40 us
     constexpr uint32_t kLargeBuf = 4;
     static_assert(256 * kLargeBuf * 8 + 2 * 64 * 16 + 64 * 4 <= sizeof(L.buf), "the large pass's staging + its slice of the large list live in the grid pass's staging area");
-    uint64_t* const buf = L.buf; uint64_t* const ovf = L.ovf; uint32_t& ovfCount = L.ovfCount; uint32_t* const waveTotals = L.waveTotals; uint32_t& blockBase = L.blockBase; uint32_t* const bhist = L.bhist;
-    if (threadIdx.x < 32) bhist[threadIdx.x] = 0;
-    if (threadIdx.x == 32) ovfCount = 0;
-    __syncthreads();
+    pairStageBegin(L);
     uint32_t nl = sc->numLarge;
     uint32_t axis = sc->axisCur;
     const uint32_t numSmall = cellLower[gp->numCells];
-    uint32_t overlaps = 0, nhit = 0, runBucket = 0, runCount = 0;
-    uint64_t* mybuf = buf + threadIdx.x * kLargeBuf;
+    PairLane me; uint32_t nhit[1] = {0u};
     // One lane per CANDIDATE — the cell-sorted small colliders [0, numSmall) (contiguous rows) and then the large list itself, not all
     // nc colliders: the dead ones of a sharded world are in neither — which it loads once and tests against every large collider,
     // 256 of them staged in LDS at a time (a few walls and a ground in a pile; hundreds of terrain tiles under vehicles).
@@ -707,45 +750,17 @@ __device__ __forceinline__ void bpPairsLargeBody(PairLds& L, const uint32_t bx, 
                     const bool ok = small || j > lIdx[w0 + l];          // large-large pairs once, from the lower index
                     if (ok && aabbOverlap(lMin[w0 + l], lMax[w0 + l], bmn, bmx)) hitMask |= 1ull << l;
                 }
-                overlaps += (uint32_t)__popcll(hitMask);
+                me.overlaps += (uint32_t)__popcll(hitMask);
                 while (hitMask) {
                     const uint32_t l = w0 + (uint32_t)__ffsll((long long)hitMask) - 1u;
                     hitMask &= hitMask - 1ull;
                     uint64_t pk = 0;
-                    if (!pairKey(lIdx[l], lMin[l], lMax[l], j, bmn, bmx, axis, pk, inter)) continue;
-                    { const uint32_t bk = (uint32_t)(pk >> 58); if (bk != runBucket && runCount) { atomicAdd(&bhist[runBucket], runCount); runCount = 0; } runBucket = bk; ++runCount; }
-                    if (nhit < kLargeBuf) mybuf[nhit] = pk;
-                    else {
-                        const uint32_t o = atomicAdd(&ovfCount, 1u);
-                        if (o < kPairOverflow) ovf[o] = pk;
-                        else { uint32_t slot = atomicAdd(&sc->numPairs, 1u); if (slot < pairCap) pairKeys[slot] = pk; }
-                    }
-                    ++nhit;
+                    if (pairKey(lIdx[l], lMin[l], lMax[l], j, bmn, bmx, axis, pk, inter)) pairStage<kLargeBuf>(L, me, 0u, nhit[0], pk, pairKeys, pairCap, sc);
                 }
             }
         }
     }
-    if (runCount) atomicAdd(&bhist[runBucket], runCount);
-    const uint32_t mine = min(nhit, kLargeBuf);
-    uint32_t incl = mine;
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    for (int off = 1; off < 64; off <<= 1) { uint32_t v = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += v; }
-    if (lane == 63) waveTotals[wv] = incl;
-    for (int off = 32; off >= 1; off >>= 1) overlaps += __shfl_xor(overlaps, off, 64);
-    if (lane == 0 && overlaps) atomicAdd(&bhist[31], overlaps);
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (uint32_t w = 0; w < wv; ++w) wbase += waveTotals[w];
-    const uint32_t staged = waveTotals[0] + waveTotals[1] + waveTotals[2] + waveTotals[3];
-    const uint32_t nOvf = min(ovfCount, kPairOverflow);
-    if (threadIdx.x == 0) { const uint32_t total = staged + nOvf; blockBase = total ? atomicAdd(&sc->numPairs, total) : 0u; }
-    __syncthreads();
-    for (uint32_t k = threadIdx.x; k < nOvf; k += 256u) { const uint32_t d = blockBase + staged + k; if (d < pairCap) pairKeys[d] = ovf[k]; }
-    uint32_t dst = blockBase + wbase + incl - mine;
-    for (uint32_t k = 0; k < mine; ++k, ++dst) if (dst < pairCap) pairKeys[dst] = mybuf[k];
-    ShardCounters* shard = &sh->c[(bx + by) & (kShards - 1u)];
-    if (threadIdx.x < kNumBuckets && bhist[threadIdx.x]) atomicAdd(&shard->bucketHist[threadIdx.x], bhist[threadIdx.x]);
-    if (threadIdx.x == 31 && bhist[31]) atomicAdd(&shard->numOverlaps, bhist[31]);
+    pairFlush<1, kLargeBuf>(L, me, nhit, bx + by, pairKeys, pairCap, sc, sh);
 }
 
 __global__ __launch_bounds__(256) void k_bp_pairs_large(uint32_t nc, const uint32_t* __restrict__ largeList, const float4* __restrict__ aabbMin, const float4* __restrict__ aabbMax,
@@ -780,19 +795,12 @@ __host__ __device__ __forceinline__ int gjkMode(uint32_t ta, uint32_t tb);
 __host__ __device__ __forceinline__ int gjkModeOfBucket(uint32_t bucket);
 // One workgroup after the pair pass: the sharded counters summed (k_pair_totals), the bucket offsets / GJK span / "partition needed"
 // (formerly k_pair_ranges) and — with `partials` — the next sweep axis (formerly k_axis_final): three single-workgroup launches in one.
-// The part of the pair stage that nothing in the rest of the step waits for: the centre statistics -> next sweep axis, and the NEXT step's grid (threshold,
-// cell size, origin, dims) from this step's extent histogram and centre bounds.  One workgroup of 256; it used to be the tail of k_pair_finish, i.e. ~10 us
-// of single-workgroup work on the step's critical path — now an extra workgroup of k_emit_manifolds runs it beside that kernel's thousands.
-__device__ inline void pairFinishStats(const Shards* __restrict__ sh, StepScalars* sc, uint32_t nc, uint32_t numBlocks, const unsigned long long* __restrict__ partials,
-                                       const int* __restrict__ blockBounds, GridParams* gridNext, uint32_t cellCapNext, const uint8_t* __restrict__ cbLive = nullptr /* sharded world: only these blocks' rows are not empty */) {
-    const uint32_t t = threadIdx.x;
-    __shared__ unsigned long long sm[4][kAxisSums];
-    unsigned long long v[kAxisSums];
-#pragma unroll
-    for (uint32_t c = 0; c < kAxisSums; ++c) v[c] = 0ull;
-    // (sharded world: first WHICH of a thread's rows are not empty — 32 independent flag loads —, then those rows: a flag load in front of every row's loads made this
-    // workgroup, 32 rows per thread in an 8-tile scene, the tail of k_emit_manifolds)
-    for (uint32_t b0 = t; b0 < numBlocks; b0 += 256u * 32u) {
+// The per-block rows b = t, t + 256, ... < numBlocks of the collider blocks' partial results that are not empty (sharded world, cbLive: first WHICH of a thread's rows
+// are live — 32 independent flag loads —, then those rows: a flag load in front of every row's loads made this workgroup, 32 rows per thread in an 8-tile scene, the
+// tail of k_emit_manifolds)
+template <class Row>
+__device__ __forceinline__ void forLiveRows(uint32_t numBlocks, const uint8_t* __restrict__ cbLive, Row row) {
+    for (uint32_t b0 = threadIdx.x; b0 < numBlocks; b0 += 256u * 32u) {
         uint32_t rowsLive = 0xFFFFFFFFu;
         if (cbLive) { rowsLive = 0u;
 #pragma unroll
@@ -800,85 +808,72 @@ __device__ inline void pairFinishStats(const Shards* __restrict__ sh, StepScalar
         for (uint32_t k = 0; k < 32u; ++k) {
             const uint32_t b = b0 + 256u * k;
             if (b >= numBlocks) break;
-            if (!((rowsLive >> k) & 1u)) continue;
-#pragma unroll
-            for (uint32_t c = 0; c < kAxisSums; ++c) v[c] += partials[(size_t)b * kAxisSums + c];
+            if ((rowsLive >> k) & 1u) row(b);
         }
     }
-    axisWaveReduce(v, sm);
-    const uint32_t lane = t & 63, wv = t >> 6;
+}
+// Steps after the first (one workgroup of 256, thread t holds extent bin t's count): TWO candidates, budgeted over the LIVE colliders (the histogram's total; numDead
+// follows from it), each the upper edge of the highest bin b whose bins ABOVE hold <= limit colliders while b itself would exceed it — a suffix sum over the 256 bins
+// (wave shuffles + the 4 wave totals) instead of k_bp_threshold's serial walk.  Every thread returns the threshold.
+__device__ inline float nextStepThreshold(const uint32_t binCount, StepScalars* sc, uint32_t nc) {
+    __shared__ uint32_t hist[256], wsum[4], liveShared;
+    __shared__ float thrShared, thrShared2;
+    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    hist[t] = binCount;
+    if (t == 0) { thrShared = 0.f; thrShared2 = 0.f; }
+    uint32_t suf = binCount;                                        // inclusive suffix sum within the wave
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) { uint32_t o = (uint32_t)__shfl_down((int)suf, d, 64); if (lane + d < 64u) suf += o; }
+    if (lane == 0) wsum[wv] = suf;
     __syncthreads();
-    if (gridNext) {   // k_bp_threshold + k_bp_grid_setup for the next step, from this step's extent histogram and centre bounds
-        __shared__ uint32_t hist[256];
+    for (uint32_t w = wv + 1; w < 4; ++w) suf += wsum[w];
+    if (t == 0) { liveShared = suf; sc->numDead = nc - suf; }       // histogram total = live colliders (dead ones of a sharded world are not in it)
+    __syncthreads();
+    const uint32_t live = liveShared;
+    uint32_t costCap;
+    const uint32_t limit = largeLimit(live, costCap);
+    const uint32_t above = suf - hist[t];                           // colliders in bins > t
+    if (above <= limit && suf > limit) thrShared = extentBinUpper(t);
+    // A second candidate with a much larger budget of "large" colliders: worth it only where the sizes are bimodal — a few hundred
+    // terrain tiles among tens of thousands of vehicle parts (cfg5) would otherwise set the cell size, every cell then holds a whole
+    // vehicle and the column scans do 64 x the tests (k_bp_pairs_grid 102 us for 22 k colliders).  The brute-force pass over the
+    // large ones streams numLarge x live boxes; it stays under the same cost cap.
+    const uint32_t limit2 = max(limit, min(live / 32u, costCap));
+    if (above <= limit2 && suf > limit2) thrShared2 = extentBinUpper(t);
+    __syncthreads();
+    const float thr = thrShared, thr2 = thrShared2;
+    return (thr2 > 0.f && thr2 <= 0.5f * thr) ? thr2 : thr;         // the second only when the cells shrink at least 2 x (8 x fewer candidates each)
+}
+// The part of the pair stage that nothing in the rest of the step waits for: the centre statistics -> next sweep axis, and the NEXT step's grid (threshold,
+// cell size, origin, dims: what k_bp_threshold + k_bp_grid_setup do for a first step) from this step's extent histogram and centre bounds.  One workgroup of 256; it used
+// to be the tail of k_pair_finish, i.e. ~10 us of single-workgroup work on the step's critical path — now an extra workgroup of k_emit_manifolds runs it beside that
+// kernel's thousands.
+__device__ inline void pairFinishStats(const Shards* __restrict__ sh, StepScalars* sc, uint32_t nc, uint32_t numBlocks, const unsigned long long* __restrict__ partials,
+                                       const int* __restrict__ blockBounds, GridParams* gridNext, uint32_t cellCapNext, const uint8_t* __restrict__ cbLive = nullptr /* sharded world: only these blocks' rows are not empty */) {
+    const uint32_t t = threadIdx.x;
+    __shared__ unsigned long long sm[4][kAxisSums];
+    unsigned long long v[kAxisSums];
+#pragma unroll
+    for (uint32_t c = 0; c < kAxisSums; ++c) v[c] = 0ull;
+    forLiveRows(numBlocks, cbLive, [&](uint32_t b) {
+#pragma unroll
+        for (uint32_t c = 0; c < kAxisSums; ++c) v[c] += partials[(size_t)b * kAxisSums + c];
+    });
+    axisWaveReduce(v, sm);
+    __syncthreads();
+    if (gridNext) {
         __shared__ int red[4][6];
-        { uint32_t h = 0; for (uint32_t k = 0; k < kShards; ++k) h += sh->extentHist[k][t]; hist[t] = h; }
-        int b6[6] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-        for (uint32_t b0 = t; b0 < numBlocks; b0 += 256u * 32u) {
-            uint32_t rowsLive = 0xFFFFFFFFu;
-            if (cbLive) { rowsLive = 0u;
-#pragma unroll
-                for (uint32_t k = 0; k < 32u; ++k) { const uint32_t b = b0 + 256u * k; if (b < numBlocks && cbLive[b]) rowsLive |= 1u << k; } }
-            for (uint32_t k = 0; k < 32u; ++k) {
-                const uint32_t b = b0 + 256u * k;
-                if (b >= numBlocks) break;
-                if (!((rowsLive >> k) & 1u)) continue;
-                for (int a = 0; a < 6; ++a) { int x = blockBounds[b * 6 + a]; b6[a] = a < 3 ? min(b6[a], x) : max(b6[a], x); }
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) { int o = __shfl_xor(b6[a], d, 64); b6[a] = a < 3 ? min(b6[a], o) : max(b6[a], o); }
-        if (lane == 0) for (int a = 0; a < 6; ++a) red[wv][a] = b6[a];
-        __syncthreads();
-        // threshold = upper edge of the highest bin b whose bins ABOVE hold <= limit colliders while b itself would exceed it: a suffix
-        // sum over the 256 bins (wave shuffles + the 4 wave totals) instead of a serial walk
-        __shared__ uint32_t wsum[4];
-        __shared__ float thrShared, thrShared2;
-        if (t == 0) { thrShared = 0.f; thrShared2 = 0.f; }
-        uint32_t suf = hist[t];                                         // inclusive suffix sum within the wave
-#pragma unroll
-        for (uint32_t d = 1; d < 64u; d <<= 1) { uint32_t o = (uint32_t)__shfl_down((int)suf, d, 64); if (lane + d < 64u) suf += o; }
-        if (lane == 0) wsum[wv] = suf;
-        __syncthreads();
-        for (uint32_t w = wv + 1; w < 4; ++w) suf += wsum[w];
-        {
-            __shared__ uint32_t liveShared;
-            if (t == 0) { liveShared = suf; sc->numDead = nc - suf; }   // histogram total = live colliders (dead ones of a sharded world are not in it)
-            __syncthreads();
-            const uint32_t live = liveShared;
-            uint32_t limit = max(16u, live / 16384u);
-            const uint32_t costCap = (uint32_t)(67108864ull / (uint64_t)max(live, 1u));
-            limit = max(8u, min(limit, costCap));
-            const uint32_t above = suf - hist[t];                       // colliders in bins > t
-            if (above <= limit && suf > limit) thrShared = extentBinUpper(t);
-            // A second candidate with a much larger budget of "large" colliders: worth it only where the sizes are bimodal — a few hundred
-            // terrain tiles among tens of thousands of vehicle parts (cfg5) would otherwise set the cell size, every cell then holds a whole
-            // vehicle and the column scans do 64 x the tests (k_bp_pairs_grid 102 us for 22 k colliders).  The brute-force pass over the
-            // large ones streams numLarge x live boxes; it stays under the same cost cap.
-            const uint32_t limit2 = max(limit, min(live / 32u, costCap));
-            if (above <= limit2 && suf > limit2) thrShared2 = extentBinUpper(t);
-        }
-        __syncthreads();
-        if (t == 0) {
-            float thr = thrShared;
-            if (thrShared2 > 0.f && thrShared2 <= 0.5f * thr) thr = thrShared2;   // only when the cells shrink at least 2 x (8 x fewer candidates each)
-            for (int w = 1; w < 4; ++w) for (int a = 0; a < 6; ++a) b6[a] = a < 3 ? min(b6[a], red[w][a]) : max(b6[a], red[w][a]);
-            float cell = thr * 1.001f + 1e-6f;
-            float lo[3], hi[3];
-            const bool any = b6[0] != 0x7FFFFFFF;
-            for (int a = 0; a < 3; ++a) { lo[a] = any ? fromOrderedInt(b6[a]) : 0.f; hi[a] = any ? fromOrderedInt(b6[3 + a]) : 0.f; }
-            cell = gridFit(lo, hi, cell, cellCapNext, gridNext->dims);
-            gridNext->numCells = gridNext->dims[0] * gridNext->dims[1] * gridNext->dims[2];
-            sc->numCellsNext = gridNext->numCells;
-            gridNext->cell = cell; gridNext->invCell = 1.f / cell;
-            for (int a = 0; a < 3; ++a) gridNext->origin[a] = lo[a];
-            gridNext->numLarge = 0; gridNext->largeThreshold = thr;
-        }
+        const uint32_t binCount = extentHistTotal(sh, t);
+        int b6[6];
+        for (int a = 0; a < 6; ++a) b6[a] = boundsEmpty(a);
+        forLiveRows(numBlocks, cbLive, [&](uint32_t b) { for (int a = 0; a < 6; ++a) boundsMerge(b6, a, blockBounds[b * 6 + a]); });
+        boundsWaveReduce(b6, red);
+        const float thr = nextStepThreshold(binCount, sc, nc);   // (its barriers stand between the waves' rows in `red` and thread 0 reading them)
+        if (t == 0) sc->numCellsNext = gridWrite(gridNext, red, thr, cellCapNext, 0u);
     }
     if (t != 0) return;
     unsigned long long s9[kAxisSums];
-    for (uint32_t c = 0; c < kAxisSums; ++c) { s9[c] = sm[0][c] + sm[1][c] + sm[2][c] + sm[3][c]; sc->axisSums[c] = s9[c]; }
+    for (uint32_t c = 0; c < kAxisSums; ++c) { s9[c] = axisBlockSum(sm, c); sc->axisSums[c] = s9[c]; }
     sc->axisNext = axisFromSums(s9, nc);   // (sharded world: from this rank's own sums — the exchange replaces it by the axis of the sums over all ranks)
 }
 // The counts a step's pair list ends with (wave 0 of k_pair_finish; or, fused, wave 0 of the first workgroup of k_narrow): bucket histogram summed over the counter shards, bucket offsets, the GJK span, whether the list wants partitioning, and the

@@ -70,14 +70,13 @@ __global__ __launch_bounds__(256) void k_ov_unpack(uint32_t count, const uint32_
     vRange[2 * v] = ranges ? ranges[2 * v] : 0u; vRange[2 * v + 1] = ranges ? ranges[2 * v + 1] : 0xFFFFFFFFu;
 }
 // one lane per volume: world shape rows and AABB by worldCollider itself
-__global__ __launch_bounds__(256) void k_ov_prepare(uint32_t count, const uint32_t* __restrict__ vcTypeBody, const uint32_t* __restrict__ vcObject, const float4* __restrict__ vcShape,
-                                                    const float4* __restrict__ vcPos, const float4* __restrict__ vcRot, const float4* __restrict__ hullAabb,
-                                                    float4* __restrict__ vShape, float4* __restrict__ vMin, float4* __restrict__ vMax) {
+__global__ __launch_bounds__(256) void k_ov_prepare(uint32_t count, ColliderRows rows /* the volumes as static colliders (k_ov_unpack) -> the volumes' world rows */) {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= count) return;
-    if (vcTypeBody[2 * v] != kOvInvalid) {
+    float4* __restrict__ vShape = rows.wShape; float4* __restrict__ vMin = rows.aabbMin; float4* __restrict__ vMax = rows.aabbMax;
+    if (rows.cTypeBody[2 * v] != kOvInvalid) {
         float4 mn, mx;
-        worldCollider(v, 0u, vcTypeBody, vcObject, vcShape, vcPos, vcRot, vcPos, vcRot /* (no bodies: never read) */, hullAabb, vShape, vMin, vMax, nullptr, nullptr, mn, mx);
+        worldCollider<false>(v, rows, mn, mx);
         if (qExtent(mn, mx) >= 0.f) return;   // (a pose or size that overflows leaves a non-finite box: reports nothing)
     }
     vShape[3 * (size_t)v] = make_float4(0, 0, 0, 0); vShape[3 * (size_t)v + 1] = make_float4(0, 0, 0, 0); vShape[3 * (size_t)v + 2] = make_float4(0, 0, 0, 1);

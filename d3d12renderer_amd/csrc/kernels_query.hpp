@@ -54,16 +54,13 @@ __device__ __forceinline__ void qBlockReduce(QPartial* sP, QPartial mine) {
     for (uint32_t st = blockDim.x / 2; st > 0; st >>= 1) { if (tid < st) qCombine(sP[tid], sP[tid + st]); __syncthreads(); }
 }
 
-__global__ __launch_bounds__(256) void k_q_colliders(uint32_t nc, uint32_t nb, const uint32_t* __restrict__ cTypeBody, const uint32_t* __restrict__ cObject,
-                                                     const float4* __restrict__ cShape, const float4* __restrict__ cStaticPos, const float4* __restrict__ cStaticRot,
-                                                     const float4* __restrict__ bPos, const float4* __restrict__ bRot, const float4* __restrict__ hullAabb,
-                                                     float4* __restrict__ qShape, float4* __restrict__ qMin, float4* __restrict__ qMax, QPartial* __restrict__ partA) {
+__global__ __launch_bounds__(256) void k_q_colliders(uint32_t nc, ColliderRows rows /* the world's colliders at the current poses -> the query's rows */, QPartial* __restrict__ partA) {
     __shared__ QPartial sP[256];
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     QPartial p = qEmptyPartial();
     if (k < nc) {
         float4 mn, mx;
-        worldCollider(k, nb, cTypeBody, cObject, cShape, cStaticPos, cStaticRot, bPos, bRot, hullAabb, qShape, qMin, qMax, nullptr, nullptr, mn, mx);
+        worldCollider<false>(k, rows, mn, mx);
         const float e = qExtent(mn, mx);
         if (e >= 0.f) { p.sum = e; p.cnt = 1.f; }
     }

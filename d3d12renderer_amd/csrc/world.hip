@@ -264,6 +264,12 @@ struct mi_world {
     // and comes back with the next step's launches (~25 us the device used to idle).  The next step adopts the result if nothing its inputs depend on has changed (same arrays, same
     // grid, same axis, no outside write: `stale`), otherwise it clears what the kernel counted and starts as before.
     DBuf<float4> wShapeAlt, aabbMinAlt, aabbMaxAlt;
+    // the one argument worldCollider's kernels take: the collider table, a pose set (bPos / bRot or the "N" set) and the rows to write (the step's, the Alt set, a query's)
+    ColliderRows colliderRows(const float4* pos, const float4* rot, float4* shape, float4* mn, float4* mx) const {
+        return ColliderRows{cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, pos, rot, hullAabb.p, shape, mn, mx,
+                            shard.enabled ? shard.active.p : nullptr, shard.enabled ? shard.activePrev.p : nullptr, (uint32_t)bodies.size(), 0u};
+    }
+    uint32_t countUnowned() const { return shard.enabled && shard.desc.rank != 0u ? 0u : 1u; }   // does this world count the colliders without a body in its centre statistics (axisCounted)
     struct Ahead { bool pending = false, stale = false; uint32_t nc = 0, nb = 0, gridIdx = 0, axis = 0; const void* pos = nullptr; const void* rot = nullptr; const void* shape = nullptr; } ahead; uint64_t aheadUsed = 0, aheadEnqueued = 0;
     // broad phase
     DBuf<unsigned long long> axisPartials;

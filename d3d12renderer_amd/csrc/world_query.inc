@@ -8,7 +8,7 @@
 
 int mi_world::queryBuild() {
     QueryCache& qc = query;
-    const uint32_t nc = (uint32_t)colliders.size(), nb = (uint32_t)bodies.size();
+    const uint32_t nc = (uint32_t)colliders.size();
     if (qc.builtEpoch == poseEpoch && qc.nc == nc) return MI_OK;
     const uint32_t maxCells = std::min<uint32_t>(std::max<uint32_t>(4u * nc, 4096u), 1u << 22);
     HIP_TRY(qc.shape.ensure(3 * (size_t)std::max(nc, 1u))); HIP_TRY(qc.mn.ensure(std::max(nc, 1u))); HIP_TRY(qc.mx.ensure(std::max(nc, 1u)));
@@ -20,8 +20,7 @@ int mi_world::queryBuild() {
     HIP_TRY(L.memsetAsync(qc.count.p, 0, ((size_t)maxCells + 1) * sizeof(uint32_t), stream));
     if (nc) {
         const uint32_t blocks = divUp(nc, 256);
-        L.launch(k_q_colliders, dim3(blocks), dim3(256), 0, stream, nc, nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPos.p, bRot.p, hullAabb.p,
-                 qc.shape.p, qc.mn.p, qc.mx.p, qc.partials.p);
+        L.launch(k_q_colliders, dim3(blocks), dim3(256), 0, stream, nc, colliderRows(bPos.p, bRot.p, qc.shape.p, qc.mn.p, qc.mx.p), qc.partials.p);
         L.launch(k_q_mean, dim3(1), dim3(kQParamThreads), 0, stream, blocks, (const QPartial*)qc.partials.p, qc.grid.p);
         L.launch(k_q_filter, dim3(blocks), dim3(256), 0, stream, nc, (const float4*)qc.mn.p, (const float4*)qc.mx.p, (const QueryGrid*)qc.grid.p, qc.partials.p + blocks);
         L.launch(k_q_params, dim3(1), dim3(kQParamThreads), 0, stream, blocks, maxCells, (const QPartial*)(qc.partials.p + blocks), qc.grid.p);
@@ -96,7 +95,7 @@ static int queryHost(mi_world* w, uint32_t count, const float* origins, const fl
 int mi_world::overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t include, const uint32_t* rangesDev, uint32_t* offsetsDev, uint4* hitsDev,
                              uint32_t capacity, uint32_t* totalDev, bool exhaustive, bool countOnly) {
     QueryCache& qc = query;
-    const uint32_t nc = (uint32_t)colliders.size(), nb = (uint32_t)bodies.size();
+    const uint32_t nc = (uint32_t)colliders.size();
     if (!exhaustive) { int rc = queryBuild(); if (rc != MI_OK) return rc; }
     HIP_TRY(qc.vShape.ensure(3 * (size_t)count)); HIP_TRY(qc.vMn.ensure(count)); HIP_TRY(qc.vMx.ensure(count));
     HIP_TRY(qc.vRange.ensure(2 * (size_t)count)); HIP_TRY(qc.vCount.ensure((size_t)count + 1));
@@ -108,15 +107,15 @@ int mi_world::overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_
     if (exhaustive) {   // its own world rows at the current poses: the yardstick does not trust the cache
         HIP_TRY(qc.xShape.ensure(3 * (size_t)std::max(nc, 1u))); HIP_TRY(qc.xMn.ensure(std::max(nc, 1u))); HIP_TRY(qc.xMx.ensure(std::max(nc, 1u)));
         HIP_TRY(qc.xPartials.ensure(divUp(std::max(nc, 1u), 256)));
-        if (nc) L.launch(k_q_colliders, dim3(divUp(nc, 256)), dim3(256), 0, stream, nc, nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPos.p, bRot.p, hullAabb.p,
-                         qc.xShape.p, qc.xMn.p, qc.xMx.p, qc.xPartials.p);
+        if (nc) L.launch(k_q_colliders, dim3(divUp(nc, 256)), dim3(256), 0, stream, nc, colliderRows(bPos.p, bRot.p, qc.xShape.p, qc.xMn.p, qc.xMx.p), qc.xPartials.p);
         s.shape = qc.xShape.p; s.mn = qc.xMn.p; s.mx = qc.xMx.p;
     } else { s.shape = qc.shape.p; s.mn = qc.mn.p; s.mx = qc.mx.p; }
     const dim3 grid(divUp(count, kOvWaves)), block(64 * kOvWaves);
     L.launch(k_ov_unpack, dim3(divUp(count, 256)), dim3(256), 0, stream, count, volumesDev, rangesDev, (uint32_t)hulls.size(), qc.vcTypeBody.p, qc.vcObject.p, qc.vcShape.p,
              qc.vcPos.p, qc.vcRot.p, qc.vRange.p);
-    L.launch(k_ov_prepare, dim3(divUp(count, 256)), dim3(256), 0, stream, count, (const uint32_t*)qc.vcTypeBody.p, (const uint32_t*)qc.vcObject.p, (const float4*)qc.vcShape.p,
-             (const float4*)qc.vcPos.p, (const float4*)qc.vcRot.p, (const float4*)hullAabb.p, qc.vShape.p, qc.vMn.p, qc.vMx.p);
+    ColliderRows volumes = colliderRows(nullptr, nullptr /* (no bodies) */, qc.vShape.p, qc.vMn.p, qc.vMx.p);   // the volumes as static colliders; the world's hulls
+    volumes.cTypeBody = qc.vcTypeBody.p; volumes.cObject = qc.vcObject.p; volumes.cShape = qc.vcShape.p; volumes.cStaticPos = qc.vcPos.p; volumes.cStaticRot = qc.vcRot.p; volumes.nb = 0u;
+    L.launch(k_ov_prepare, dim3(divUp(count, 256)), dim3(256), 0, stream, count, volumes);
     for (uint32_t pass = 0; pass < (countOnly ? 1u : 2u); ++pass) {
         if (exhaustive)
             L.launch(k_q_overlap_exhaustive, grid, block, 0, stream, pass, count, include, s, (const float4*)qc.vShape.p, (const float4*)qc.vMn.p, (const float4*)qc.vMx.p,

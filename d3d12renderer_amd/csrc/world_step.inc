@@ -440,14 +440,11 @@ int mi_world::stagePrepare(StepAttempt& a) {
         // Not launched if the previous step ran it (step-ahead).  Behind a skipped reset it is the first kernel of the step and carries the start event (sharded: k_shard_classify before it is not in the step's time).
         if (!a.useAhead)
             L.launchTimed(a.skipReset && startTimed, ev[EV_STEP_BEGIN], nullptr, a.blockSkip ? k_bp_prepare<true> : k_bp_prepare<false>, dim3(bodyGrid(a, divUp(nc, 256))), dim3(256), 0, st,
-                          nc, aabbMin.p, aabbMax.p, grid.p + gridCur, axisPartials.p, shards.p, sc, largeList.p, isLarge.p, blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p,
-                          shard.enabled ? shard.activePrev.p : nullptr, shard.enabled ? shard.active.p : nullptr, shard.enabled && shard.desc.rank != 0u ? 0u : 1u,
-                          nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPos.p, bRot.p, hullAabb.p, wShape.p, aabbMin.p, aabbMax.p, sapAxis, shard.enabled ? shard.axisDev.p : nullptr,
-                          a.blockSkip ? cbRange.p : nullptr, a.blockSkip ? shard.blockLive.p : nullptr, a.blockSkip ? shard.cbLive.p : nullptr);
+                          nc, colliderRows(bPos.p, bRot.p, wShape.p, aabbMin.p, aabbMax.p), grid.p + gridCur, axisPartials.p, shards.p, sc, largeList.p, isLarge.p, blockBounds.p, cellKeys.p, cellRanks.p,
+                          cellCount.p, countUnowned(), sapAxis, shard.enabled ? shard.axisDev.p : nullptr, a.blockSkip ? BlockSkip{cbRange.p, shard.blockLive.p, shard.cbLive.p} : BlockSkip{});
         a.prepared = true;
     } else
-        L.launch(k_world_colliders, dim3(divUp(nc, B)), dim3(B), 0, st, nc, nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPos.p, bRot.p, hullAabb.p,
-                 wShape.p, aabbMin.p, aabbMax.p, sc, sapAxis, shard.enabled ? shard.active.p : nullptr, shard.activePrev.p, shard.enabled ? shard.axisDev.p : nullptr);
+        L.launch(k_world_colliders, dim3(divUp(nc, B)), dim3(B), 0, st, nc, colliderRows(bPos.p, bRot.p, wShape.p, aabbMin.p, aabbMax.p), sc, sapAxis, shard.enabled ? shard.axisDev.p : nullptr);
     if (heightmap) {   // terrain contacts per collider, their offsets and totals (they join the pair list after the collider-pair narrow phase)
         const HullSet hmHulls{hullVerts.p, hullRanges.p};
         L.launch(k_hm_lowest, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmSlow.p, hmHulls);
@@ -477,10 +474,12 @@ int mi_world::stageBroad(StepAttempt& a) {
     else if (gridValid) {
         // the grid prepared at the end of the previous step (k_pair_finish): one fused kernel instead of five launches; the cell histogram
         // is all zero here (cleared once at upload, and every scan clears the cells it has read)
-        L.launch(k_bp_prepare<false>, dim3(nblk), dim3(256), 0, st, nc, aabbMin.p, aabbMax.p, gridUse, axisPartials.p, shards.p, sc, largeList.p, isLarge.p, blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p, shard.enabled ? shard.activePrev.p : nullptr, shard.enabled ? shard.active.p : nullptr, shard.enabled && shard.desc.rank != 0u ? 0u : 1u,
-                 nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr, nullptr);
+        ColliderRows given{};   // no collider table: k_world_colliders has written this step's rows, the kernel reads them (and the shard flags)
+        given.aabbMin = aabbMin.p; given.aabbMax = aabbMax.p; given.bodyActive = shard.enabled ? shard.active.p : nullptr; given.bodyActivePrev = shard.enabled ? shard.activePrev.p : nullptr;
+        L.launch(k_bp_prepare<false>, dim3(nblk), dim3(256), 0, st, nc, given, gridUse, axisPartials.p, shards.p, sc, largeList.p, isLarge.p, blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p,
+                 countUnowned(), 0u, nullptr, BlockSkip{});
     } else {
-        L.launch(k_axis_partials, dim3(nblk), dim3(256), 0, st, nc, aabbMin.p, aabbMax.p, axisPartials.p, shards.p, shard.enabled ? shard.active.p : nullptr, shard.enabled && shard.desc.rank != 0u ? 0u : 1u);
+        L.launch(k_axis_partials, dim3(nblk), dim3(256), 0, st, nc, aabbMin.p, aabbMax.p, axisPartials.p, shards.p, shard.enabled ? shard.active.p : nullptr, countUnowned());
         L.launch(k_bp_threshold, dim3(1), dim3(256), 0, st, nc, shards.p, sc);
         L.launch(k_bp_classify, dim3(divUp(nc, B)), dim3(B), 0, st, nc, aabbMin.p, aabbMax.p, sc, largeList.p, isLarge.p, blockBounds.p);
         L.launch(k_bp_grid_setup, dim3(1), dim3(256), 0, st, nc, nblk, cellCap, blockBounds.p, sc, gridUse);
@@ -925,10 +924,8 @@ int mi_world::stagePublish(StepAttempt& a) {
     if (knobs.stepAhead && a.spec && a.pass == PASS_PLAIN && spinReadback && a.fuseResetStep && !shard.enabled && nc && gridValid && knobs.fuseWorld && !a.graphStep && !knobs.debugSync &&
         !timesEnds(timingLevel) && !debugOrderPending && !heightmap && !usesInteractions) {
         HIP_TRY(wShapeAlt.ensure(wShape.cap)); HIP_TRY(aabbMinAlt.ensure(aabbMin.cap)); HIP_TRY(aabbMaxAlt.ensure(aabbMax.cap));
-        hipLaunchKernelGGL(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, aabbMinAlt.p, aabbMaxAlt.p, grid.p + (gridCur ^ 1u), axisPartials.p, shards.p, sc, largeList.p, isLarge.p,
-                           blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p, (const uint8_t*)nullptr, (const uint8_t*)nullptr, 1u,
-                           nb, cTypeBody.p, cObject.p, cShape.p, cStaticPos.p, cStaticRot.p, bPosN.p, bRotN.p, hullAabb.p, wShapeAlt.p, aabbMinAlt.p, aabbMaxAlt.p, sapAxis, &sc->axisNext,
-                           (const uint2*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr);
+        hipLaunchKernelGGL(k_bp_prepare<false>, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, colliderRows(bPosN.p, bRotN.p, wShapeAlt.p, aabbMinAlt.p, aabbMaxAlt.p), grid.p + (gridCur ^ 1u),
+                           axisPartials.p, shards.p, sc, largeList.p, isLarge.p, blockBounds.p, cellKeys.p, cellRanks.p, cellCount.p, 1u, sapAxis, &sc->axisNext, BlockSkip{});
         ++aheadEnqueued;
         ahead.pending = true; ahead.stale = true /* until this step is known to be valid */; ahead.nc = nc; ahead.nb = nb; ahead.gridIdx = gridCur ^ 1u; ahead.pos = bPosN.p; ahead.rot = bRotN.p; ahead.shape = cShape.p; ahead.axis = 0xFFFFFFFFu;
     }

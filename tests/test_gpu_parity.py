@@ -11,7 +11,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 import make_golden  # noqa: E402
 from d3d12renderer_amd import scenes, capi  # noqa: E402
-from helpers import assert_schedule_valid, contact_set, single_body_scene  # noqa: E402
+from helpers import assert_schedule_valid, contact_set, overlap_census, single_body_scene  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 REL_TOL = 1e-4   # north_star tolerance for float state; the assertions below are stricter (bit-exact)
@@ -501,14 +501,16 @@ def test_gpu_other_contact_solvers_match_oracle(mi_lib, oracle_mod, monkeypatch,
 
 @pytest.mark.parametrize("env", [{"MI_FUSE_RESET": "0"}, {"MI_ROUND0_EMIT": "0"}, {"MI_FUSE_LARGE": "0"}, {"MI_FINISH_IN_NARROW": "0"}, {"MI_COLOR_TAIL": "0"},
                                  {"MI_COLOR_ROUNDS_MAX": "1"}, {"MI_COLOR_ROUNDS_MAX": "1", "MI_ROUND0_EMIT": "0"}, {"MI_COLOR_ROUNDS_MAX": "2", "MI_PERSIST_XCD_MIN": "1"},
-                                 {"MI_FUSE_KEYS": "0", "MI_PERSIST_XCD_MIN": "1"},
-                                 {"MI_FUSE_RESET": "0", "MI_ROUND0_EMIT": "0", "MI_FUSE_LARGE": "0", "MI_FINISH_IN_NARROW": "0", "MI_COLOR_TAIL": "0", "MI_FUSE_KEYS": "0", "MI_PERSIST_XCD_MIN": "1"}],
+                                 {"MI_FUSE_KEYS": "0", "MI_PERSIST_XCD_MIN": "1"}, {"MI_FUSE_WORLD": "0"},
+                                 {"MI_FUSE_RESET": "0", "MI_ROUND0_EMIT": "0", "MI_FUSE_LARGE": "0", "MI_FINISH_IN_NARROW": "0", "MI_COLOR_TAIL": "0", "MI_FUSE_KEYS": "0", "MI_PERSIST_XCD_MIN": "1",
+                                  "MI_FUSE_WORLD": "0"}],
                          ids=lambda e: ",".join(f"{k[3:]}={v}" for k, v in e.items()))
 def test_gpu_step_launch_variants_match_oracle(mi_lib, oracle_mod, monkeypatch, env):
     """The launches a steady step no longer makes, each behind a switch that brings it back (knobs.hpp): k_reset_scalars (its work rides in k_publish_readback), colouring
     round 0 (inside k_emit_manifolds), the large colliders' pair pass (first workgroups of k_bp_pairs), k_pair_finish (every workgroup of k_narrow derives the list's final
     counts itself), the margin of colouring rounds (k_bin_hist runs whatever rounds the enqueued ones left over: MI_COLOR_ROUNDS_MAX=1 makes it run nearly all of them),
-    k_manifold_keys (same launch as k_integrate_forces: k_forces_keys; needs the XCD-partitioned layout, forced onto this small pile).  A falling pile — every count grows from step
+    k_manifold_keys (same launch as k_integrate_forces: k_forces_keys; needs the XCD-partitioned layout, forced onto this small pile), k_world_colliders (inside k_bp_prepare;
+    MI_FUSE_WORLD=0: k_bp_prepare reads the rows that launch wrote).  A falling pile — every count grows from step
     to step — against the oracle, bit for bit, and without a synchronous re-run beyond the first steps."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -524,6 +526,66 @@ def test_gpu_step_launch_variants_match_oracle(mi_lib, oracle_mod, monkeypatch, 
     tail_steps, tail_rounds = g.color_tail_stats()
     if env.get("MI_COLOR_TAIL") == "0": assert tail_steps == 0
     if "MI_COLOR_ROUNDS_MAX" in env: assert tail_steps >= 30 and tail_rounds >= 2 * tail_steps, "with one or two rounds enqueued the tail has to colour nearly everything"
+
+
+def _sphere_clump(n=96):
+    """n spheres of radius 0.5 with centres jittered inside a 0.1 m cube, weightless, nothing else."""
+    e = scenes.make_entities(n)
+    e["position"] = np.stack([scenes.uniform(11, a, n, -0.05, 0.05) for a in range(3)], axis=1).astype(np.float32)
+    e["gravity_factor"] = 0.0
+    c = scenes.make_colliders(n, capi.SPHERE)
+    c["shape"][:, 3] = 0.5
+    return scenes.Scene("sphere_clump", e, np.arange(n, dtype=np.uint32), c, 2)
+
+
+def _slab_stack(slabs=66, low=16, high=2384):
+    """`slabs` static 40 x 0.5 x 40 m boxes over one footprint, each 1 mm above the one before; `low` spheres of radius 0.25 in a 4 x 4 cluster whose AABBs cut every slab;
+    `high` more on a lattice 50 m up that touch nothing."""
+    se = scenes.make_entities(slabs, capi.ENTITY_STATIC)
+    sc_ = scenes.make_colliders(slabs, capi.AABB, friction=1.0)
+    for k in range(slabs):
+        sc_["shape"][k, :6] = (-20.0, 0.001 * k, -20.0, 20.0, 0.5 + 0.001 * k, 20.0)
+    n = low + high
+    e = scenes.make_entities(n)
+    side = int(round(low ** 0.5))
+    e["position"][:low] = [(0.3 * (i % side) - 0.45, 0.28, 0.3 * (i // side) - 0.45) for i in range(low)]
+    hs = int(np.ceil(high ** (1.0 / 3.0)))
+    idx = np.arange(high)
+    e["position"][low:] = np.stack([(idx % hs) - hs / 2.0, 50.0 + (idx // hs) % hs, (idx // (hs * hs)) - hs / 2.0], axis=1).astype(np.float32)
+    c = scenes.make_colliders(n, capi.SPHERE)
+    c["shape"][:, 3] = 0.25
+    return scenes.Scene("slab_stack", np.concatenate([se, e]), np.arange(slabs + n, dtype=np.uint32), np.concatenate([sc_, c]), 2)
+
+
+@pytest.mark.parametrize("make", [_sphere_clump, _slab_stack], ids=["grid pass: slots, overflow, direct append", "large pass: two slices, overflow"])
+def test_gpu_pair_staging_tiers_match_oracle(mi_lib, oracle_mod, make):
+    """The deeper tiers of the pair staging (kernels_broad.hpp: pairStage / pairFlush), which the other scenes reach only incidentally.  Nothing exported reports the path
+    taken; the scenes reach theirs by construction, and every step is held against the oracle: counts, contacts as a set, transforms byte for byte, and the overlap count
+    against a census of the AABBs.
+
+    Sphere clump — the grid pass's three tiers.  96 equal spheres: one extent bin holding 96 > limit 16, so none is large and the cell is 1.09 m; their centres span < 0.1 m,
+    so all 96 are in ONE cell and one workgroup.  In column 0 the lane at sorted position i walks the positions behind it and hits all 95 - i of them.  6 are staged in its
+    slots (kPairBuf); the workgroup's excess is sum(max(0, 95 - i - 6)) = 89 * 90 / 2 = 4005 > kPairOverflow = 512: 512 go to the block's overflow area, 3493 straight to
+    the list.  96 * 95 / 2 = 4560 overlaps (the oracle alone: 4560 overlaps, manifolds and contacts in each of the three steps; two solver iterations do not part the clump).
+
+    Slab stack — the large pass with more than one 64-wide slice and more than kLargeBuf = 4 hits per candidate.  The first step's threshold (one candidate, limit 16) leaves
+    the 66 slabs in the grid.  From the second step on the grid is pairFinishStats's: live = 2466, limit2 = max(16, 2466 / 32) = 77 >= 66 and the second candidate (the
+    spheres' extent bin, about 0.55 m) is less than half the first (the slabs', about 41 m), so the 66 slabs are the large list: two slices, walked by one row of workgroups
+    in the second step (gy = 1: sized from the first step's empty list) and by two in the third.  Each of the 16 low spheres hits all 66 slabs against 4 slots: 16 * 62 = 992
+    excess keys, overflow area and direct append.  The 66 * 65 / 2 = 2145 slab-slab overlaps are counted once each and yield no key.  (The oracle alone, each of the three steps: extent bins 120 with the 2400 spheres and 170 with the 66 slabs; 3243 overlaps = 2145 + 16 * 66 + 42 inside the cluster; 1098 manifolds.)"""
+    sc = make()
+    g = sc.populate(gpu_world(mi_lib)); o = sc.populate(oracle_mod.create_world(oracle_mod.ORDER_CANONICAL))
+    s = sc.settings()
+    for i in range(3):
+        g.step_fixed(s, sc.dt, 1); o.step_fixed(s, sc.dt, 1)
+        cg, co = g.counts(), o.counts()
+        assert cg == co, f"step {i}"
+        assert contact_set(g.contacts()) == contact_set(o.contacts()), f"step {i}"
+        pg, qg = g.physics_transforms(); po, qo = o.physics_transforms()
+        assert pg.tobytes() == po.tobytes() and qg.tobytes() == qo.tobytes(), f"step {i}"
+        assert cg["num_broadphase_overlaps"] == overlap_census(o.aabbs(), co["sorting_axis"])[0], f"step {i}"
+        if make is _sphere_clump:
+            assert cg["num_broadphase_overlaps"] == 4560
 
 
 @pytest.mark.parametrize("variant", ["0", "1"], ids=["GJK by lanes + EPA queue", "GJK and EPA by one wave per pair"])
