@@ -41,6 +41,11 @@ query_volume_dtype = np.dtype([("type", "<u4"), ("hull_geometry", "<u4"), ("shap
                                ("rotation", "<f4", 4), ("pad1", "<f4", 2)])
 overlap_hit_dtype = np.dtype([("entity", "<u4"), ("collider", "<u4"), ("object_type", "<u4"), ("volume", "<u4")])
 assert query_volume_dtype.itemsize == 96 and overlap_hit_dtype.itemsize == 16
+# mi_volume_contact (mi_world_volume_contacts): one manifold per (volume, collider); count_flags = contacts | volume-was-B << 8; points = (xyz, depth)
+volume_contact_dtype = np.dtype([("entity", "<u4"), ("collider", "<u4"), ("object_type", "<u4"), ("volume", "<u4"), ("normal", "<f4", 3), ("count_flags", "<u4"),
+                                 ("points", "<f4", (4, 4))])
+assert volume_contact_dtype.itemsize == 96
+VOLUME_CONTACT_COUNT_MASK, VOLUME_CONTACT_VOLUME_IS_B = 7, 1 << 8
 MI_ERR_CAPACITY = -5
 QUERY_ALL = QUERY_RIGID_BODIES | QUERY_STATIC | QUERY_TERRAIN | QUERY_TRIGGERS | QUERY_FORCE_FIELDS
 
@@ -381,6 +386,63 @@ class World:
         self.L.check(self.L.fn("world_overlap_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_uint32(include), C.c_void_p(ranges_ptr or None),
                                                               C.c_void_p(offsets_ptr), C.c_void_p(hits_ptr or None), C.c_uint32(capacity), C.c_void_p(total_ptr)),
                      "world_overlap_device_async")
+
+    # --- contact-manifold scene queries (where a shape touches the world, along which normal, how deep; read-only)
+    def _volume_contacts(self, name, volumes, include, entity_ranges):
+        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
+        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
+        offsets = np.zeros(len(v) + 1, np.uint32)
+        total = C.c_uint32(0)
+        cap = max(16, 4 * len(v))   # an estimate; MI_ERR_CAPACITY tells the exact number
+        f = self.L.fn(name)
+        while True:
+            recs = np.zeros(cap, dtype=volume_contact_dtype)
+            rc = f(self.h, C.c_uint32(len(v)), _ptr(v), C.c_uint32(include), _ptr(r), _ptr(offsets), _ptr(recs), C.c_uint32(cap), C.byref(total))
+            if rc == MI_ERR_CAPACITY:
+                cap = total.value
+                continue
+            self.L.check(rc, name)
+            return offsets, recs[:total.value]
+
+    def volume_contacts(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_world_volume_contacts: (offsets[count + 1], records) in CSR form, `volume_contact_dtype` records in ascending world collider index per
+        volume: the narrow phase's manifold of (A, B), A = the smaller world type (the volume for equal types); normal from A to B."""
+        return self._volume_contacts("world_volume_contacts", volumes, include, entity_ranges)
+
+    def debug_volume_contacts_exhaustive(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_debug_volume_contacts_exhaustive: the same result with every collider a candidate (byte for byte what volume_contacts returns)."""
+        return self._volume_contacts("debug_volume_contacts_exhaustive", volumes, include, entity_ranges)
+
+    def volume_contacts_raw(self, volumes, include, entity_ranges, capacity, name="world_volume_contacts", fill=0):
+        """One call with a fixed capacity: (status, offsets, records[capacity], total); the records start out as bytes of `fill`."""
+        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
+        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
+        offsets = np.zeros(len(v) + 1, np.uint32); total = C.c_uint32(0)
+        recs = np.frombuffer(bytearray([fill]) * (96 * capacity), dtype=volume_contact_dtype)
+        rc = self.L.fn(name)(self.h, C.c_uint32(len(v)), _ptr(v), C.c_uint32(include), _ptr(r), _ptr(offsets), _ptr(recs) if capacity else None,
+                             C.c_uint32(capacity), C.byref(total))
+        return rc, offsets, recs, total.value
+
+    def debug_volume_contacts_times(self):
+        """mi_debug_volume_contacts_times: (primitive / box kernel, GJK kernel, narrow phase + compaction) of the last contact query in ms; zeros unless
+        set_stage_timing was on."""
+        out = np.zeros(3, np.float32)
+        self.L.check(self.L.fn("debug_volume_contacts_times")(self.h, _ptr(out)), "debug_volume_contacts_times")
+        return tuple(float(x) for x in out)
+
+    def volume_contacts_reserve(self, max_candidates):
+        """mi_world_volume_contacts_reserve: sizes the candidate staging the device call uses (grow-only)."""
+        self.L.check(self.L.fn("world_volume_contacts_reserve")(self.h, C.c_uint32(max_candidates)), "world_volume_contacts_reserve")
+
+    def volume_contacts_device_async(self, n, volumes_ptr, offsets_ptr, contacts_ptr, capacity, totals_ptr, include=QUERY_DEFAULT, ranges_ptr=0):
+        """mi_world_volume_contacts_device_async: device buffers (volumes: n x 96 bytes; offsets: n + 1 uint32; contacts: capacity x 96 bytes; totals:
+        2 uint32 = records, candidates found), enqueued on the world's stream without a host synchronisation.  Returns the status: 0, or
+        MI_ERR_CAPACITY when nothing was reserved (anything else raises)."""
+        rc = self.L.fn("world_volume_contacts_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_uint32(include), C.c_void_p(ranges_ptr or None),
+                                                             C.c_void_p(offsets_ptr), C.c_void_p(contacts_ptr or None), C.c_uint32(capacity), C.c_void_p(totals_ptr))
+        if rc != MI_ERR_CAPACITY:
+            self.L.check(rc, "world_volume_contacts_device_async")
+        return rc
 
     def update_constraints(self, ctype, ids, pods):
         """getConstraint(scene, handle) = ... for many constraints of one type."""

@@ -97,12 +97,15 @@ __device__ __forceinline__ void writeManifold(uint32_t p, bool hit, const Manifo
         for (uint32_t k = 0; k < 4; ++k) if (k < cnt) npPoints[4 * p + k] = f4(m.p[k], m.d[k]);   // (static indices: the manifold stays in registers, not in scratch)
     }
 }
-__device__ __forceinline__ void boxPairShapes(const float4* __restrict__ wShape, uint32_t a, uint32_t b, uint32_t ta,
-                                              Q4& arot, V3& acen, V3& arad, Q4& brot, V3& bcen, V3& brad) {
-    Shape sa = loadShape(wShape, a, ta), sb = loadShape(wShape, b, T_OBB);
+// (sa, sb) = (AABB or OBB, OBB) as loadShape gives them -> the two boxes as obbSat / obbContactsLds take them
+__device__ __forceinline__ void boxPairOfShapes(const Shape& sa, const Shape& sb, uint32_t ta, Q4& arot, V3& acen, V3& arad, Q4& brot, V3& bcen, V3& brad) {
     if (ta == T_AABB) { arot = Q4(0.f, 0.f, 0.f, 1.f); acen = (sa.a + sa.b) * 0.5f; arad = (sa.b - sa.a) * 0.5f; }
     else { arot = sa.rot; acen = sa.a; arad = sa.b; }
     brot = sb.rot; bcen = sb.a; brad = sb.b;
+}
+__device__ __forceinline__ void boxPairShapes(const float4* __restrict__ wShape, uint32_t a, uint32_t b, uint32_t ta,
+                                              Q4& arot, V3& acen, V3& arad, Q4& brot, V3& bcen, V3& brad) {
+    boxPairOfShapes(loadShape(wShape, a, ta), loadShape(wShape, b, T_OBB), ta, arot, acen, arad, brot, bcen, brad);
 }
 constexpr uint32_t kBoxQueues = 16;
 // A word every workgroup reads, through the scalar cache — explicitly: after the stores of pairFinishCounts (other path, same kernel) the compiler no longer proves the

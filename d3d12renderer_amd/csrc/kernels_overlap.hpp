@@ -20,6 +20,7 @@ constexpr uint32_t kOvWaves = 4;            // volumes per 256-thread workgroup
 constexpr uint32_t kOvMaxCells = 512;       // a volume over more cells strides over all colliders instead (ordered by construction)
 constexpr uint32_t kOvSortMax = 1024;       // longest segment a wave sorts in LDS; a longer one is written by the stride over all colliders
 constexpr uint32_t kOvInvalid = 0xFFu;      // world type of a volume that reports nothing
+constexpr uint32_t kOvPassCount = 1u, kOvPassWrite = 2u;   // what one overlapEnqueue runs (world_query.inc)
 constexpr uint32_t kOvVolumeWords = 24;     // mi_query_volume: type, hull_geometry, shape[12], position[3], pad, rotation[4], pad[2]
 
 // what a volume sees: the world rows of the colliders at the current poses (k_q_colliders) and who they belong to
@@ -95,8 +96,9 @@ __device__ __forceinline__ OverlapVolume ovLoadVolume(const float4* __restrict__
     return q;
 }
 // THE predicate: is collider k reported for this volume?  Object type, entity range, closed world AABBs (a non-finite one never), then the
-// reference's overlapCheck(A, B) with A = the smaller world type, the volume for equal types.
-__device__ inline bool ovTest(const OverlapScene& s, const OverlapVolume& q, uint32_t k) {
+// reference's overlapCheck(A, B) with A = the smaller world type, the volume for equal types.  kBoxesOnly: everything but overlapCheck —
+// the candidates of the contact query (kernels_contacts_query.hpp), whose narrow phase decides instead.
+template <bool kBoxesOnly> __device__ inline bool ovTest(const OverlapScene& s, const OverlapVolume& q, uint32_t k) {
     const float4 a = s.mn[k], b = s.mx[k];
     const uint32_t tag = __float_as_uint(a.w), type = tag & 0xFFu, obj = (tag >> 8) & 0xFFu;
     if (!(q.include & qFlagOf(obj))) return false;
@@ -104,6 +106,7 @@ __device__ inline bool ovTest(const OverlapScene& s, const OverlapVolume& q, uin
     if (ent < q.lo || ent >= q.hi) return false;
     if (!(qExtent(a, b) >= 0.f)) return false;
     if (q.mx.x < a.x || q.mn.x > b.x || q.mx.y < a.y || q.mn.y > b.y || q.mx.z < a.z || q.mn.z > b.z) return false;
+    if (kBoxesOnly) return true;
     const Shape c = loadShape(s.shape, k, type);
     return (int)type < q.s.type ? overlapCheck(c, q.s, s.hs) : overlapCheck(q.s, c, s.hs);
 }
@@ -114,11 +117,11 @@ __device__ __forceinline__ void ovWrite(const OverlapScene& s, uint4* __restrict
 }
 
 // one wave over all colliders in index order: the count, and with `write` the records from `base` on (ascending by construction)
-__device__ inline uint32_t ovLinear(const OverlapScene& s, const OverlapVolume& q, uint32_t v, uint32_t lane, bool write, uint4* __restrict__ hits, uint32_t capacity, uint32_t base) {
+template <bool kBoxesOnly> __device__ inline uint32_t ovLinear(const OverlapScene& s, const OverlapVolume& q, uint32_t v, uint32_t lane, bool write, uint4* __restrict__ hits, uint32_t capacity, uint32_t base) {
     uint32_t n = 0;
     for (uint32_t k0 = 0; k0 < s.nc; k0 += 64u) {
         const uint32_t k = k0 + lane;
-        const bool hit = k < s.nc && ovTest(s, q, k);
+        const bool hit = k < s.nc && ovTest<kBoxesOnly>(s, q, k);
         const unsigned long long m = __ballot(hit);
         if (write && hit) ovWrite(s, hits, capacity, base + n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)), k, v);
         n += (uint32_t)__popcll(m);
@@ -148,7 +151,7 @@ __device__ __forceinline__ void ovKeep(uint32_t* keys, uint32_t slot, bool hit, 
 // lanes stride over the row's whole span.  A collider sits in every cell of its range; it is reported from ONE entry: the one in the lowest
 // cell, per axis, of the intersection of its range (qCellRange, which inserted it) with the volume's.  keys != null: the matches are
 // compacted into keys[0 .. n) (LDS, any order); the caller guarantees n <= kOvSortMax.
-__device__ inline uint32_t ovGridWalk(const OverlapScene& s, const OverlapVolume& q, const QueryGrid& g, const uint32_t lo[3], const uint32_t hi[3],
+template <bool kBoxesOnly> __device__ inline uint32_t ovGridWalk(const OverlapScene& s, const OverlapVolume& q, const QueryGrid& g, const uint32_t lo[3], const uint32_t hi[3],
                                       const uint32_t* __restrict__ start, const uint32_t* __restrict__ entries, const uint32_t* __restrict__ large, uint32_t lane,
                                       uint32_t* keys) {
     uint32_t n = 0;
@@ -164,7 +167,7 @@ __device__ inline uint32_t ovGridWalk(const OverlapScene& s, const OverlapVolume
                     uint32_t klo[3], khi[3];
                     if (qCellRange(g, s.mn[k], s.mx[k], klo, khi) && max(klo[1], lo[1]) == y && max(klo[2], lo[2]) == z) {
                         const uint32_t c = row + max(klo[0], lo[0]);
-                        hit = start[c] <= e && e < start[c + 1u] && ovTest(s, q, k);
+                        hit = start[c] <= e && e < start[c + 1u] && ovTest<kBoxesOnly>(s, q, k);
                     }
                 }
                 const unsigned long long m = __ballot(hit);
@@ -176,7 +179,7 @@ __device__ inline uint32_t ovGridWalk(const OverlapScene& s, const OverlapVolume
     for (uint32_t i0 = 0; i0 < nl; i0 += 64u) {
         const uint32_t i = i0 + lane;
         const uint32_t k = i < nl ? large[i] : 0u;
-        const bool hit = i < nl && ovTest(s, q, k);
+        const bool hit = i < nl && ovTest<kBoxesOnly>(s, q, k);
         const unsigned long long m = __ballot(hit);
         ovKeep(keys, n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)), hit, k);
         n += (uint32_t)__popcll(m);
@@ -186,7 +189,7 @@ __device__ inline uint32_t ovGridWalk(const OverlapScene& s, const OverlapVolume
 
 // pass 0: counts[v] (and counts[count] = 0 for the scan).  pass 1: offsets = the scanned counts; the segment of volume v is written in
 // ascending collider index: a grid-walk segment is sorted in LDS by its wave, the others come from the stride over all colliders.
-__global__ __launch_bounds__(64 * kOvWaves) void k_q_overlap(uint32_t pass, uint32_t count, uint32_t include, OverlapScene s, const float4* __restrict__ vShape,
+template <bool kBoxesOnly> __global__ __launch_bounds__(64 * kOvWaves) void k_q_overlap(uint32_t pass, uint32_t count, uint32_t include, OverlapScene s, const float4* __restrict__ vShape,
                                                              const float4* __restrict__ vMin, const float4* __restrict__ vMax, const uint32_t* __restrict__ vRange,
                                                              const QueryGrid* __restrict__ grid, const uint32_t* __restrict__ start, const uint32_t* __restrict__ entries,
                                                              const uint32_t* __restrict__ large, uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets,
@@ -202,14 +205,14 @@ __global__ __launch_bounds__(64 * kOvWaves) void k_q_overlap(uint32_t pass, uint
         uint32_t lo[3], hi[3];
         const bool walk = q.valid && ovCellRange(g, q, lo, hi);
         if (pass == 0u) {
-            const uint32_t n = !q.valid ? 0u : walk ? ovGridWalk(s, q, g, lo, hi, start, entries, large, lane, nullptr) : ovLinear(s, q, v, lane, false, nullptr, 0u, 0u);
+            const uint32_t n = !q.valid ? 0u : walk ? ovGridWalk<kBoxesOnly>(s, q, g, lo, hi, start, entries, large, lane, nullptr) : ovLinear<kBoxesOnly>(s, q, v, lane, false, nullptr, 0u, 0u);
             if (lane == 0u) counts[v] = n;
         } else {
             base = offsets[v];
             const uint32_t n = offsets[v + 1u] - base;
             if (n != 0u && base < capacity) {
-                if (walk && n <= kOvSortMax) nSort = min(ovGridWalk(s, q, g, lo, hi, start, entries, large, lane, sKeys[wave]), n);   // (= n: the count pass walked the same entries)
-                else ovLinear(s, q, v, lane, true, hits, capacity, base);
+                if (walk && n <= kOvSortMax) nSort = min(ovGridWalk<kBoxesOnly>(s, q, g, lo, hi, start, entries, large, lane, sKeys[wave]), n);   // (= n: the count pass walked the same entries)
+                else ovLinear<kBoxesOnly>(s, q, v, lane, true, hits, capacity, base);
             }
         }
     }
@@ -240,7 +243,7 @@ __global__ __launch_bounds__(64 * kOvWaves) void k_q_overlap(uint32_t pass, uint
 }
 
 // ---- exhaustive: one wave per volume over every collider, no grid; the rows in `s` are computed for the call, not taken from the cache
-__global__ __launch_bounds__(64 * kOvWaves) void k_q_overlap_exhaustive(uint32_t pass, uint32_t count, uint32_t include, OverlapScene s, const float4* __restrict__ vShape,
+template <bool kBoxesOnly> __global__ __launch_bounds__(64 * kOvWaves) void k_q_overlap_exhaustive(uint32_t pass, uint32_t count, uint32_t include, OverlapScene s, const float4* __restrict__ vShape,
                                                                         const float4* __restrict__ vMin, const float4* __restrict__ vMax, const uint32_t* __restrict__ vRange,
                                                                         uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets, uint4* __restrict__ hits,
                                                                         uint32_t capacity, uint32_t* __restrict__ total) {
@@ -249,9 +252,9 @@ __global__ __launch_bounds__(64 * kOvWaves) void k_q_overlap_exhaustive(uint32_t
     if (v >= count) return;
     const OverlapVolume q = ovLoadVolume(vShape, vMin, vMax, vRange, v, include);
     if (pass == 0u) {
-        const uint32_t n = q.valid ? ovLinear(s, q, v, lane, false, nullptr, 0u, 0u) : 0u;
+        const uint32_t n = q.valid ? ovLinear<kBoxesOnly>(s, q, v, lane, false, nullptr, 0u, 0u) : 0u;
         if (lane == 0u) counts[v] = n;
-    } else if (q.valid && offsets[v] < capacity) ovLinear(s, q, v, lane, true, hits, capacity, offsets[v]);
+    } else if (q.valid && offsets[v] < capacity) ovLinear<kBoxesOnly>(s, q, v, lane, true, hits, capacity, offsets[v]);
 }
 
 }  // namespace mi

@@ -33,6 +33,7 @@
 #include "knobs.hpp"
 #include "kernels_query.hpp"
 #include "kernels_overlap.hpp"
+#include "kernels_contacts_query.hpp"
 
 using namespace mi;
 
@@ -434,10 +435,20 @@ struct mi_world {
         DeviceScan<uint32_t> scan2;
         DBuf<float4> xShape, xMn, xMx; DBuf<QPartial> xPartials;   // the exhaustive yardstick's own collider rows, computed per call
         DBuf<uint32_t> volumes, vOffsets, vTotal; DBuf<uint4> vHits;   // staging of the blocking variants
+        // contact queries (mi_world_volume_contacts*): candidates (boxes-only overlap records) and their offsets, one 96-byte slot and one flag per candidate,
+        // the GJK queue, the scan over the flags; candCap = the candidates all of them hold (mi_world_volume_contacts_reserve)
+        uint32_t candCap = 0;
+        DBuf<uint4> cCand, cSlots; DBuf<uint32_t> cOffsets, cFlags, cScan, cQueue, cQueueN;
+        DeviceScan<uint32_t> scan3;
+        DBuf<uint32_t> cOutOffsets, cTotals; DBuf<uint4> cOut;   // staging of the blocking variants
+        hipEvent_t cEv[4] = {};   // before k_vc_narrow / before k_vc_gjk / behind it / behind k_vc_write: recorded under mi_world_set_stage_timing only
+        bool cTimed = false;      // the last call recorded them (mi_debug_volume_contacts_times)
     } query;
     int queryBuild();
     int overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t include, const uint32_t* rangesDev, uint32_t* offsetsDev, uint4* hitsDev, uint32_t capacity,
-                       uint32_t* totalDev, bool exhaustive, bool countOnly);
+                       uint32_t* totalDev, bool exhaustive, uint32_t passes, bool boxesOnly);
+    int contactsReserve(uint32_t maxCandidates);
+    int contactsEnqueue(uint32_t count, uint32_t bound, uint32_t capacity, uint4* contactsDev, uint32_t* offsetsDev, uint32_t* totals2Dev, bool exhaustive);
 };
 
 int mi_world::init(int dev) {
@@ -512,6 +523,7 @@ mi_world::~mi_world() {
     if (graphDebug) std::fprintf(stderr, "[mi_physics] step graphs: %u replayed, %u captured, %u plain speculative steps, %llu steps in total\n", graphHits, graphCaptures, graphPlain, (unsigned long long)totalSteps);
     dropStepGraphs();
     if (stream) (void)hipStreamDestroy(stream);
+    for (hipEvent_t& e : query.cEv) if (e) (void)hipEventDestroy(e);
     for (auto& e : profEvents) (void)hipEventDestroy(e);
     for (auto& set : evSets) for (auto& e : set) if (e) (void)hipEventDestroy(e);
     delete heightmap;

@@ -340,6 +340,50 @@ MI_API int mi_debug_overlap_exhaustive(mi_world* world, uint32_t count, const mi
                                        const uint32_t* entity_ranges2, uint32_t* out_offsets, mi_overlap_hit* out_hits,
                                        uint32_t capacity, uint32_t* out_total);
 
+/*
+ * Batched contact-manifold queries: where a shape touches the world, along which normal and how deep (what PhysX calls
+ * computePenetration and Bullet contactTest).  The volumes, their validation (an invalid one yields an empty segment), the include
+ * flags, entity_ranges2, the pose read (physics_transform1, pending edits included), the CSR result in ascending world collider index
+ * and the capacity protocol are those of mi_world_overlap; a sharded world returns MI_ERR_UNSUPPORTED.
+ *   - World collider k is reported for volume v when it passes (1) the object-type filter, (2) the entity-range test and (3) the closed
+ *     world-AABB test of mi_world_overlap, and the step's narrow phase, run on (A, B), returns at least one contact.  A is the one of
+ *     the two with the smaller world type (sphere < capsule < cylinder < AABB < OBB < hull); for equal types A is the volume.
+ *   - A record holds the narrow phase's own bits for that (A, B): the manifold a rigid body of the volume's shape at the volume's pose
+ *     would get from one step against that collider as (A, B).  Nothing is negated or re-ordered; bit 8 of count_flags says which of
+ *     the two the volume was.
+ *   - The normal is a unit vector pointing from A to B, as the reference's (sphereSphere: normalize(centre B - centre A)); points[i] =
+ *     (world contact point, penetration depth >= 0).  To separate the volume from the collider move the VOLUME along -normal when it
+ *     was A (bit 8 clear) and along +normal when it was B (bit 8 set), by the largest depth of the record.
+ *   - Not reported: the terrain (MI_QUERY_TERRAIN is accepted and ignored, as by mi_world_overlap) and cloth.
+ */
+typedef struct mi_volume_contact {   /* 96 bytes, 16-byte aligned rows: usable from the host and as a device buffer */
+    uint32_t entity, collider, object_type, volume;   /* as mi_overlap_hit */
+    float normal[3]; uint32_t count_flags;            /* bits 0..2: contacts (1..4); bit 8: the volume was B of the pair */
+    float points[4][4];                               /* world point xyz + penetration depth; unused rows are 0 */
+} mi_volume_contact;
+MI_API int mi_world_volume_contacts(mi_world* world, uint32_t count, const mi_query_volume* volumes, uint32_t include,
+                                    const uint32_t* entity_ranges2, uint32_t* out_offsets, mi_volume_contact* out_contacts,
+                                    uint32_t capacity, uint32_t* out_total);
+/* Sizes the library's candidate staging (about 150 bytes per candidate; a candidate = a collider that passes tests (1)-(3)).  The
+ * host call grows it by itself; the device call uses what was reserved.  Grow-only; synchronises the world's stream. */
+MI_API int mi_world_volume_contacts_reserve(mi_world* world, uint32_t max_candidates);
+/* Device buffers (16-byte aligned), only enqueued on the world's stream: no host synchronisation.  totals2_dev[0] receives the
+ * records, totals2_dev[1] the candidates found.  When the candidates exceed the reservation, only the first reserved candidates (in
+ * result order) are evaluated: totals2_dev[1] > the reservation tells the consumer that records, offsets and totals2_dev[0] are those
+ * of that prefix.  Nothing is written at or past contacts_dev[capacity].  With nothing reserved the call returns MI_ERR_CAPACITY. */
+MI_API int mi_world_volume_contacts_device_async(mi_world* world, uint32_t count, const mi_query_volume* volumes_dev, uint32_t include,
+                                                 const uint32_t* ranges2_dev, uint32_t* offsets_dev, mi_volume_contact* contacts_dev,
+                                                 uint32_t capacity, uint32_t* totals2_dev);
+/* Device times of the narrow phase of the last contact query made while mi_world_set_stage_timing was on (0 otherwise), milliseconds:
+ * out_ms3 = { the primitive / box kernel, the GJK kernel, all of narrow phase + compaction }.  The candidate passes before them are not
+ * included.  Synchronises with that query. */
+MI_API int mi_debug_volume_contacts_times(mi_world* world, float* out_ms3);
+/* The same result with the candidates taken from every collider against every volume, without the grid and from collider rows
+ * computed for the call: byte for byte equal. */
+MI_API int mi_debug_volume_contacts_exhaustive(mi_world* world, uint32_t count, const mi_query_volume* volumes, uint32_t include,
+                                               const uint32_t* entity_ranges2, uint32_t* out_offsets, mi_volume_contact* out_contacts,
+                                               uint32_t capacity, uint32_t* out_total);
+
 /* physicsStep(scene, arena, timer, settings, dt) (src/physics/physics.cpp:1364-1413). */
 MI_API int mi_world_step(mi_world* world, const mi_step_settings* settings, float dt);
 /* n × physicsStepInternal(scene, arena, settings, dt) (src/physics/physics.cpp:1180-1362); no interpolation. */

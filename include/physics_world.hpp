@@ -157,6 +157,20 @@ public:
         if (total) check(mi_world_overlap(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, r.offsets.data(), r.hits.data(), total, &total), "mi_world_overlap");
         return r;
     }
+    // Where each volume touches the world (mi_world_volume_contacts): CSR offsets [volumes + 1] and one manifold per (volume, collider) in ascending
+    // collider index; normal from A to B, bit 8 of count_flags set when the volume was B (include/mi_physics.h); read-only.
+    struct volume_contacts_result { std::vector<uint32_t> offsets; std::vector<mi_volume_contact> contacts; };
+    volume_contacts_result volumeContacts(const std::vector<mi_query_volume>& volumes, uint32_t include = MI_QUERY_DEFAULT, const std::vector<uint32_t>& entityRanges = {}) {
+        volume_contacts_result r; r.offsets.assign(volumes.size() + 1, 0u);
+        if (volumes.empty()) return r;
+        if (!entityRanges.empty() && entityRanges.size() != 2 * volumes.size()) throw std::invalid_argument("volumeContacts: entityRanges needs one [lo, hi) pair per volume");
+        const uint32_t* ranges = entityRanges.empty() ? nullptr : entityRanges.data();
+        uint32_t total = 0;   // count first, then fetch
+        check(mi_world_volume_contacts(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, r.offsets.data(), nullptr, 0, &total), "mi_world_volume_contacts");
+        r.contacts.resize(total);
+        if (total) check(mi_world_volume_contacts(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, r.offsets.data(), r.contacts.data(), total, &total), "mi_world_volume_contacts");
+        return r;
+    }
     std::vector<mi_overlap_hit> overlapSphere(vec3 center, float radius, uint32_t include = MI_QUERY_DEFAULT) {
         mi_query_volume v{}; v.type = MI_COLLIDER_SPHERE; v.rotation[3] = 1.f;
         v.shape[0] = center.x; v.shape[1] = center.y; v.shape[2] = center.z; v.shape[3] = radius;
