@@ -97,10 +97,10 @@ __device__ uint32_t g_dbgKnock = 0u;
 // Sum-only counters are sharded over 16 cache lines: a same-address global atomic sustains only ~90 ops/us on this
 // chip (one L2 channel), so thousands of workgroups adding to ONE word serialise a whole kernel behind it.
 constexpr uint32_t kShards = 16;
-struct ShardCounters { uint32_t numOverlaps; uint32_t bucketHist[24]; uint32_t owned[3]; uint32_t boxHits; uint32_t pad[3]; };   // one 128-byte line per shard; owned: sharded world (bodies / manifolds / contacts of this rank);
-                                                                                                                                   // boxHits: box pairs that passed the SAT, per queue (k_narrow -> k_narrow_clip; queue q = shard q — its own line: the 16 counters side by side in
+struct ShardCounters { uint32_t numOverlaps; uint32_t bucketHist[24]; uint32_t owned[3]; unsigned long long boxHits; uint32_t pad[2]; };   // one 128-byte line per shard; owned: sharded world (bodies / manifolds / contacts of this rank);
+                                                                                                                                   // boxHits: box pairs that passed the SAT, per queue: face hits | edge hits << 32 (k_narrow -> k_narrow_clip; queue q = shard q — its own line: the 16 counters side by side in
                                                                                                                                    // ONE line of StepScalars took every workgroup's returning atomic through one L2 line)
-static_assert(sizeof(ShardCounters) == 128 && kShards == 16, "one line per shard; the box queues use the shards' lines");
+static_assert(sizeof(ShardCounters) == 128 && offsetof(ShardCounters, boxHits) == 112 && kShards == 16, "one line per shard; the box queues use the shards' lines");
 struct Shards { ShardCounters c[kShards]; uint32_t extentHist[kShards][256]; };
 
 // Sharded world, "a rank pays for what it simulates" (round 5): the per-body and per-collider passes of a step visit BLOCKS of 256 bodies / colliders, and skip the blocks

@@ -184,30 +184,42 @@ __device__ inline bool clipAndBuild(Poly& poly, Poly& clipped, const P4* planes,
 // and writes of the ping-pong planes may alias for all it knows), then walks it with static indices and writes the surviving vertices back IN PLACE
 // (everything a pass needs is already in registers, so one [vertex][lane] plane per lane suffices: 32 KiB per workgroup instead of 64).  The
 // arithmetic per vertex, and the order of the vertices, are exactly clipPolygon's / clipAndBuild's / reduceManifold's above.
-__device__ inline void clipPolygonLds(LdsPoly& poly, const P4* planes, uint32_t numPlanes) {
-    for (uint32_t ci = 0; ci < numPlanes; ++ci) {
-        const uint32_t n = poly.n;
-        if (n == 0) break;
-        const P4 pl = planes[ci];
-        ClipVert v[kLdsPolyVerts];
+//
+// A pass makes one clipEdge per slot — an edge that crosses the plane yields the crossing point (whichever way it crosses), an end point inside follows it: the
+// vertices and their order are clipPolygon's three cases.  A convex polygon gains at most one vertex per plane, so pass k of a quad's four reads at most
+// 4 + k vertices (MaxIn): the later slots of the 8-vertex plane are not instantiated.  The first pass (Exact) takes the quad from the registers it was built in.
+template <uint32_t MaxIn, bool Exact>
+__device__ __forceinline__ void clipWalkLds(LdsPoly& poly, const ClipVert* v, uint32_t n, ClipVert start, const P4 pl) {
+    float sd = planeDist(start.v, pl);
+    uint32_t on = 0;
 #pragma unroll
-        for (uint32_t i = 0; i < kLdsPolyVerts; ++i) if (i < n) v[i] = poly.get(i);
-        ClipVert start = poly.get(n - 1);
-        uint32_t on = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < kLdsPolyVerts; ++i) {
-            if (i < n) {
-                const ClipVert end = v[i];
-                const float sd = planeDist(start.v, pl), ed = planeDist(end.v, pl);
-                const bool sIn = sd > 0.f, eIn = ed > 0.f;
-                if (sIn && eIn) poly.put(on++, end);
-                else if (sIn) poly.put(on++, clipEdge(start, end, sd, ed));
-                else if (!sIn && eIn) { poly.put(on++, clipEdge(start, end, sd, ed)); poly.put(on++, end); }
-                start = end;
-            }
+    for (uint32_t i = 0; i < MaxIn; ++i) {
+        if (Exact || i < n) {
+            const ClipVert end = v[i];
+            const float ed = planeDist(end.v, pl);
+            const bool sIn = sd > 0.f, eIn = ed > 0.f;
+            if (sIn != eIn) poly.put(on++, clipEdge(start, end, sd, ed));
+            if (eIn) poly.put(on++, end);
+            start = end; sd = ed;
         }
-        poly.n = on;
     }
+    poly.n = on;
+}
+template <uint32_t MaxIn>
+__device__ __forceinline__ void clipPassLds(LdsPoly& poly, const P4 pl) {
+    const uint32_t n = poly.n;
+    if (n == 0) return;
+    ClipVert v[MaxIn];
+#pragma unroll
+    for (uint32_t i = 0; i < MaxIn; ++i) if (i < n) v[i] = poly.get(i);
+    clipWalkLds<MaxIn, false>(poly, v, n, poly.get(n - 1), pl);
+}
+// the incident quad against the four side planes of the reference face
+__device__ inline void clipQuadLds(LdsPoly& poly, const ClipVert* quad, const P4* planes) {
+    clipWalkLds<4, true>(poly, quad, 4u, quad[3], planes[0]);
+    clipPassLds<5>(poly, planes[1]);
+    clipPassLds<6>(poly, planes[2]);
+    clipPassLds<7>(poly, planes[3]);
 }
 __device__ inline void reduceManifoldLds(const LdsPoly& poly, uint32_t n, V3 normal, Manifold& out) {
     ClipVert v[kLdsPolyVerts];
@@ -252,8 +264,8 @@ __device__ inline void reduceManifoldLds(const LdsPoly& poly, uint32_t n, V3 nor
         for (uint32_t i = 0; i < 4; ++i) if (i < n) setc(out, i, v[i].v, v[i].depth);
     }
 }
-__device__ inline bool clipAndBuildLds(LdsPoly& poly, const P4* planes, uint32_t numPlanes, P4 ref, Manifold& out) {
-    clipPolygonLds(poly, planes, numPlanes);
+__device__ inline bool clipAndBuildLds(LdsPoly& poly, const ClipVert* quad, const P4* planes, P4 ref, Manifold& out) {
+    clipQuadLds(poly, quad, planes);
     if (poly.n > 0) {
         V3 rn(ref.x, ref.y, ref.z);
         for (uint32_t i = 0; i < poly.n; ++i) {       // (swap-and-pop: the order of the survivors is part of the result)
@@ -502,96 +514,70 @@ __device__ inline bool obbSat(Q4 arot, V3 acen, V3 arad, Q4 brot, V3 bcen, V3 br
     res.normal = normal; res.faceHit = faceHit; res.bFace = bFace;
     return true;
 }
-template <class Poly>
-__device__ inline bool obbContacts(Q4 arot, V3 acen, V3 arad, Q4 brot, V3 bcen, V3 brad, const ObbSat& res, Poly& poly, Poly& clipped, Manifold& out) {
-    const V3 normal = res.normal;
-    const bool faceHit = res.faceHit, bFace = res.bFace;
-    out.n = normal;
-    if (faceHit) {
-        V3 cp[4], cn[4], quad[4];
-        P4 plane;
-        if (!bFace) {
-            boxClipPlanes(arad, rotate(conj(arot), normal), cp, cn);
-            boxIncidentFace(brad, rotate(conj(brot), normal), quad);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                cp[i] = rotate(arot, cp[i]) + acen;
-                cn[i] = rotate(arot, cn[i]);
-                quad[i] = rotate(brot, quad[i]) + bcen;
-            }
-            plane = makePlane(obbSupport(arot, acen, arad, normal), normal);
-        } else {
-            boxClipPlanes(brad, rotate(conj(brot), -normal), cp, cn);
-            boxIncidentFace(arad, rotate(conj(arot), -normal), quad);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                cp[i] = rotate(brot, cp[i]) + bcen;
-                cn[i] = rotate(brot, cn[i]);
-                quad[i] = rotate(arot, quad[i]) + acen;
-            }
-            plane = makePlane(obbSupport(brot, bcen, brad, -normal), -normal);
-        }
-        P4 planes[4];
-        poly.n = 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            planes[i] = makePlane(cp[i], cn[i]);
-            ClipVert c; c.v = quad[i]; c.depth = -planeDist(quad[i], plane);
-            poly.put(i, c);
-        }
-        if (!clipAndBuild(poly, clipped, planes, 4, plane, out)) return false;
-    } else {
-        V3 a0, a1, b0, b1;
-        boxIncidentEdge(arad, rotate(conj(arot), normal), a0, a1);
-        boxIncidentEdge(brad, rotate(conj(brot), -normal), b0, b1);
-        a0 = rotate(arot, a0) + acen; a1 = rotate(arot, a1) + acen;
-        b0 = rotate(brot, b0) + bcen; b1 = rotate(brot, b1) + bcen;
-        V3 pa, pb;
-        float sq = closestSegmentSegment(a0, a1, b0, b1, pa, pb);
-        out.count = 1;
-        out.d[0] = sqrtf(sq);
-        out.p[0] = (pa + pb) * 0.5f;
-    }
-    return true;
-}
-// obbContacts for k_narrow_clip: the face case clips in place in one LDS polygon (clipAndBuildLds); everything else is obbContacts itself
-__device__ inline bool obbContactsLds(Q4 arot, V3 acen, V3 arad, Q4 brot, V3 bcen, V3 brad, const ObbSat& res, LdsPoly& poly, Manifold& out) {
-    if (!res.faceHit) { LdsPoly none{poly.p, 0u}; return obbContacts(arot, acen, arad, brot, bcen, brad, res, poly, none, out); }   // (edge case: no polygon involved)
-    const V3 normal = res.normal;
-    const bool bFace = res.bFace;
-    out.n = normal;
+// Face contact set-up, shared by obbContacts and obbContactsLds: the box whose face carries the normal is the REFERENCE box (A, or B with the normal reversed), the
+// other one the INCIDENT box.  The two are selected once and everything after runs on the selection — per lane the operations, operands and their order are those of
+// the reference's two branches.  Gives the four side planes of the reference face, the reference plane and the incident quad with its depths.
+struct ObbFace { P4 planes[4]; P4 plane; ClipVert quad[4]; };
+__device__ __forceinline__ void obbFaceSetup(Q4 arot, V3 acen, V3 arad, Q4 brot, V3 bcen, V3 brad, V3 normal, bool bFace, ObbFace& f) {
+    const Q4 rrot = bFace ? brot : arot, irot = bFace ? arot : brot;
+    const V3 rcen = bFace ? bcen : acen, icen = bFace ? acen : bcen;
+    const V3 rrad = bFace ? brad : arad, irad = bFace ? arad : brad;
+    const V3 n = bFace ? -normal : normal;
     V3 cp[4], cn[4], quad[4];
-    P4 plane;
-    if (!bFace) {
-        boxClipPlanes(arad, rotate(conj(arot), normal), cp, cn);
-        boxIncidentFace(brad, rotate(conj(brot), normal), quad);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            cp[i] = rotate(arot, cp[i]) + acen;
-            cn[i] = rotate(arot, cn[i]);
-            quad[i] = rotate(brot, quad[i]) + bcen;
-        }
-        plane = makePlane(obbSupport(arot, acen, arad, normal), normal);
-    } else {
-        boxClipPlanes(brad, rotate(conj(brot), -normal), cp, cn);
-        boxIncidentFace(arad, rotate(conj(arot), -normal), quad);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            cp[i] = rotate(brot, cp[i]) + bcen;
-            cn[i] = rotate(brot, cn[i]);
-            quad[i] = rotate(arot, quad[i]) + acen;
-        }
-        plane = makePlane(obbSupport(brot, bcen, brad, -normal), -normal);
-    }
-    P4 planes[4];
-    poly.n = 4;
+    boxClipPlanes(rrad, rotate(conj(rrot), n), cp, cn);
+    boxIncidentFace(irad, rotate(conj(irot), n), quad);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        planes[i] = makePlane(cp[i], cn[i]);
-        ClipVert c; c.v = quad[i]; c.depth = -planeDist(quad[i], plane);
-        poly.put(i, c);
+        cp[i] = rotate(rrot, cp[i]) + rcen;
+        cn[i] = rotate(rrot, cn[i]);
+        quad[i] = rotate(irot, quad[i]) + icen;
     }
-    return clipAndBuildLds(poly, planes, 4, plane, out);
+    f.plane = makePlane(obbSupport(rrot, rcen, rrad, n), n);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f.planes[i] = makePlane(cp[i], cn[i]);
+        f.quad[i].v = quad[i]; f.quad[i].depth = -planeDist(quad[i], f.plane);
+    }
+}
+// Edge contact: the closest points of the two incident edges (one contact, no polygon)
+__device__ inline void obbEdgeContact(Q4 arot, V3 acen, V3 arad, Q4 brot, V3 bcen, V3 brad, V3 normal, Manifold& out) {
+    V3 a0, a1, b0, b1;
+    boxIncidentEdge(arad, rotate(conj(arot), normal), a0, a1);
+    boxIncidentEdge(brad, rotate(conj(brot), -normal), b0, b1);
+    a0 = rotate(arot, a0) + acen; a1 = rotate(arot, a1) + acen;
+    b0 = rotate(brot, b0) + bcen; b1 = rotate(brot, b1) + bcen;
+    V3 pa, pb;
+    float sq = closestSegmentSegment(a0, a1, b0, b1, pa, pb);
+    out.count = 1;
+    out.d[0] = sqrtf(sq);
+    out.p[0] = (pa + pb) * 0.5f;
+}
+template <class Poly>
+__device__ inline bool obbContacts(Q4 arot, V3 acen, V3 arad, Q4 brot, V3 bcen, V3 brad, const ObbSat& res, Poly& poly, Poly& clipped, Manifold& out) {
+    out.n = res.normal;
+    if (res.faceHit) {
+        ObbFace f;
+        obbFaceSetup(arot, acen, arad, brot, bcen, brad, res.normal, res.bFace, f);
+        poly.n = 4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) poly.put(i, f.quad[i]);
+        if (!clipAndBuild(poly, clipped, f.planes, 4, f.plane, out)) return false;
+    } else obbEdgeContact(arot, acen, arad, brot, bcen, brad, res.normal, out);
+    return true;
+}
+// The face case with the polygon in LDS, clipped in place (clipAndBuildLds): k_narrow_clip's face waves
+__device__ inline bool obbFaceContactsLds(Q4 arot, V3 acen, V3 arad, Q4 brot, V3 bcen, V3 brad, V3 normal, bool bFace, LdsPoly& poly, Manifold& out) {
+    out.n = normal;
+    ObbFace f;
+    obbFaceSetup(arot, acen, arad, brot, bcen, brad, normal, bFace, f);
+    return clipAndBuildLds(poly, f.quad, f.planes, f.plane, out);
+}
+// obbContacts with the face case's polygon in LDS, for lanes of either class (the contact queries)
+__device__ inline bool obbContactsLds(Q4 arot, V3 acen, V3 arad, Q4 brot, V3 bcen, V3 brad, const ObbSat& res, LdsPoly& poly, Manifold& out) {
+    if (res.faceHit) return obbFaceContactsLds(arot, acen, arad, brot, bcen, brad, res.normal, res.bFace, poly, out);
+    out.n = res.normal;
+    obbEdgeContact(arot, acen, arad, brot, bcen, brad, res.normal, out);
+    return true;
 }
 template <class Poly>
 __device__ inline bool obbOBB(Q4 arot, V3 acen, V3 arad, Q4 brot, V3 bcen, V3 brad, Poly& poly, Poly& clipped, Manifold& out) {
