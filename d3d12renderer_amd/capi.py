@@ -345,40 +345,44 @@ class World:
         self.L.check(self.L.fn("world_raycast_device_async")(self.h, C.c_uint32(n), C.c_void_p(rays_ptr), C.c_uint32(include),
                                                               C.c_void_p(ranges_ptr or None), C.c_void_p(out_ptr)), "world_raycast_device_async")
 
-    # --- volume-overlap scene queries (which colliders touch a shape; read-only)
-    def _overlap(self, name, volumes, include, entity_ranges, capacity=None):
+    # --- volume scene queries (overlaps and contact manifolds; read-only): one call-with-capacity protocol
+    def _volume_query(self, name, record_dtype, volumes, include, entity_ranges, capacity, estimate=0, fill=0, null_at_zero=True):
+        """One volume query in CSR form -> (status, offsets[count + 1], records[capacity], total): the capacity protocol as the C caller sees it.
+        capacity = None: max(16, estimate x count) records first, and once more with the exact number when MI_ERR_CAPACITY tells it.
+        The records start out as bytes of `fill`; a zero capacity passes a null record pointer unless told otherwise."""
         v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
         r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
         offsets = np.zeros(len(v) + 1, np.uint32)
         total = C.c_uint32(0)
-        cap = max(16, 8 * len(v)) if capacity is None else int(capacity)   # an estimate; MI_ERR_CAPACITY tells the exact number
+        cap = max(16, estimate * len(v)) if capacity is None else int(capacity)
         f = self.L.fn(name)
         while True:
-            hits = np.zeros(cap, dtype=overlap_hit_dtype)
-            rc = f(self.h, C.c_uint32(len(v)), _ptr(v), C.c_uint32(include), _ptr(r), _ptr(offsets), _ptr(hits) if cap else None, C.c_uint32(cap), C.byref(total))
+            recs = np.frombuffer(bytearray([fill]) * (record_dtype.itemsize * cap), dtype=record_dtype)
+            rc = f(self.h, C.c_uint32(len(v)), _ptr(v), C.c_uint32(include), _ptr(r), _ptr(offsets), None if null_at_zero and not cap else _ptr(recs),
+                   C.c_uint32(cap), C.byref(total))
             if rc == MI_ERR_CAPACITY and capacity is None:
                 cap = total.value
                 continue
-            self.L.check(rc, name)
-            return offsets, hits[:total.value]
+            return rc, offsets, recs, total.value
+
+    def _volume_query_all(self, name, record_dtype, estimate, volumes, include, entity_ranges):
+        """(offsets, records): every record, by estimate and retry."""
+        rc, offsets, recs, total = self._volume_query(name, record_dtype, volumes, include, entity_ranges, None, estimate)
+        self.L.check(rc, name)
+        return offsets, recs[:total]
 
     def overlap(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):
         """mi_world_overlap: (offsets[count + 1], hits) in CSR form, `overlap_hit_dtype` records in ascending world collider index per volume.
         Calls with an estimated capacity and once more with the exact one when that was too small."""
-        return self._overlap("world_overlap", volumes, include, entity_ranges)
+        return self._volume_query_all("world_overlap", overlap_hit_dtype, 8, volumes, include, entity_ranges)
 
     def debug_overlap_exhaustive(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):
         """mi_debug_overlap_exhaustive: the same result from every collider against every volume (byte for byte what overlap returns)."""
-        return self._overlap("debug_overlap_exhaustive", volumes, include, entity_ranges)
+        return self._volume_query_all("debug_overlap_exhaustive", overlap_hit_dtype, 8, volumes, include, entity_ranges)
 
     def overlap_raw(self, volumes, include, entity_ranges, capacity, name="world_overlap"):
         """One call with a fixed capacity: (status, offsets, hits[capacity], total) — the capacity protocol as the C caller sees it."""
-        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
-        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
-        offsets = np.zeros(len(v) + 1, np.uint32); hits = np.zeros(capacity, dtype=overlap_hit_dtype); total = C.c_uint32(0)
-        rc = self.L.fn(name)(self.h, C.c_uint32(len(v)), _ptr(v), C.c_uint32(include), _ptr(r), _ptr(offsets), _ptr(hits) if capacity else None,
-                             C.c_uint32(capacity), C.byref(total))
-        return rc, offsets, hits, total.value
+        return self._volume_query(name, overlap_hit_dtype, volumes, include, entity_ranges, capacity)
 
     def overlap_device_async(self, n, volumes_ptr, offsets_ptr, hits_ptr, capacity, total_ptr, include=QUERY_DEFAULT, ranges_ptr=0):
         """mi_world_overlap_device_async: device buffers (volumes: n x 96 bytes; offsets: n + 1 uint32; hits: capacity x 16 bytes; total: 1 uint32),
@@ -388,40 +392,18 @@ class World:
                      "world_overlap_device_async")
 
     # --- contact-manifold scene queries (where a shape touches the world, along which normal, how deep; read-only)
-    def _volume_contacts(self, name, volumes, include, entity_ranges):
-        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
-        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
-        offsets = np.zeros(len(v) + 1, np.uint32)
-        total = C.c_uint32(0)
-        cap = max(16, 4 * len(v))   # an estimate; MI_ERR_CAPACITY tells the exact number
-        f = self.L.fn(name)
-        while True:
-            recs = np.zeros(cap, dtype=volume_contact_dtype)
-            rc = f(self.h, C.c_uint32(len(v)), _ptr(v), C.c_uint32(include), _ptr(r), _ptr(offsets), _ptr(recs), C.c_uint32(cap), C.byref(total))
-            if rc == MI_ERR_CAPACITY:
-                cap = total.value
-                continue
-            self.L.check(rc, name)
-            return offsets, recs[:total.value]
-
     def volume_contacts(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):
         """mi_world_volume_contacts: (offsets[count + 1], records) in CSR form, `volume_contact_dtype` records in ascending world collider index per
         volume: the narrow phase's manifold of (A, B), A = the smaller world type (the volume for equal types); normal from A to B."""
-        return self._volume_contacts("world_volume_contacts", volumes, include, entity_ranges)
+        return self._volume_query_all("world_volume_contacts", volume_contact_dtype, 4, volumes, include, entity_ranges)
 
     def debug_volume_contacts_exhaustive(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):
         """mi_debug_volume_contacts_exhaustive: the same result with every collider a candidate (byte for byte what volume_contacts returns)."""
-        return self._volume_contacts("debug_volume_contacts_exhaustive", volumes, include, entity_ranges)
+        return self._volume_query_all("debug_volume_contacts_exhaustive", volume_contact_dtype, 4, volumes, include, entity_ranges)
 
     def volume_contacts_raw(self, volumes, include, entity_ranges, capacity, name="world_volume_contacts", fill=0):
         """One call with a fixed capacity: (status, offsets, records[capacity], total); the records start out as bytes of `fill`."""
-        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
-        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
-        offsets = np.zeros(len(v) + 1, np.uint32); total = C.c_uint32(0)
-        recs = np.frombuffer(bytearray([fill]) * (96 * capacity), dtype=volume_contact_dtype)
-        rc = self.L.fn(name)(self.h, C.c_uint32(len(v)), _ptr(v), C.c_uint32(include), _ptr(r), _ptr(offsets), _ptr(recs) if capacity else None,
-                             C.c_uint32(capacity), C.byref(total))
-        return rc, offsets, recs, total.value
+        return self._volume_query(name, volume_contact_dtype, volumes, include, entity_ranges, capacity, fill=fill)
 
     def debug_volume_contacts_times(self):
         """mi_debug_volume_contacts_times: (primitive / box kernel, GJK kernel, narrow phase + compaction) of the last contact query in ms; zeros unless

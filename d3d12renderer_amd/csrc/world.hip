@@ -425,26 +425,45 @@ struct mi_world {
     // ray-cast queries (world_query.inc): anything that moves or changes a collider bumps the pose epoch; the query structure is rebuilt for a new one
     uint64_t poseEpoch = 0;
     struct QueryCache {
-        uint64_t builtEpoch = ~0ull; uint32_t nc = 0;
-        DBuf<float4> shape, mn, mx; DBuf<QueryGrid> grid; DBuf<QPartial> partials; DBuf<uint32_t> count, start, entries, large;
-        DeviceScan<uint32_t> scan; Launcher L;
-        DBuf<float> rays; DBuf<uint32_t> ranges, hits;   // staging of the blocking variants
-        // overlap queries (mi_world_overlap*): the volumes' world rows, counts, and the scan between the count and the write pass
-        DBuf<float4> vShape, vMn, vMx; DBuf<uint32_t> vRange, vCount;
-        DBuf<uint32_t> vcTypeBody, vcObject; DBuf<float4> vcShape, vcPos, vcRot;   // the volumes as static colliders: what worldCollider reads
-        DeviceScan<uint32_t> scan2;
-        DBuf<float4> xShape, xMn, xMx; DBuf<QPartial> xPartials;   // the exhaustive yardstick's own collider rows, computed per call
-        DBuf<uint32_t> volumes, vOffsets, vTotal; DBuf<uint4> vHits;   // staging of the blocking variants
-        // contact queries (mi_world_volume_contacts*): candidates (boxes-only overlap records) and their offsets, one 96-byte slot and one flag per candidate,
-        // the GJK queue, the scan over the flags; candCap = the candidates all of them hold (mi_world_volume_contacts_reserve)
-        uint32_t candCap = 0;
-        DBuf<uint4> cCand, cSlots; DBuf<uint32_t> cOffsets, cFlags, cScan, cQueue, cQueueN;
-        DeviceScan<uint32_t> scan3;
-        DBuf<uint32_t> cOutOffsets, cTotals; DBuf<uint4> cOut;   // staging of the blocking variants
-        hipEvent_t cEv[4] = {};   // before k_vc_narrow / before k_vc_gjk / behind it / behind k_vc_write: recorded under mi_world_set_stage_timing only
-        bool cTimed = false;      // the last call recorded them (mi_debug_volume_contacts_times)
+        Launcher L;
+        // The grid structure (world rows of every collider, uniform grid, large list), shared by all three families.  Sized by the collider count; queryBuild()
+        // alone grows and writes it, once per pose epoch.
+        struct Built {
+            uint64_t epoch = ~0ull; uint32_t nc = 0;
+            DBuf<float4> shape, mn, mx; DBuf<QueryGrid> grid; DBuf<QPartial> partials; DBuf<uint32_t> count, start, entries, large;
+            DeviceScan<uint32_t> scan;
+        } built;
+        // The volume rows of the current overlap / contact call: world rows and counts, the volumes as static colliders (what worldCollider reads), the scan
+        // between the count and the write pass.  Sized by the call's volume count; overlapEnqueue() alone grows them.  candOffsets = the candidate offsets of a
+        // contact call (boxes-only overlap offsets), grown by the contact entry points before they enqueue.
+        struct VolumeRows {
+            DBuf<float4> shape, mn, mx; DBuf<uint32_t> range, count;
+            DBuf<uint32_t> cTypeBody, cObject; DBuf<float4> cShape, cPos, cRot;
+            DeviceScan<uint32_t> scan;
+            DBuf<uint32_t> candOffsets;
+        } vol;
+        // The exhaustive yardstick's own collider rows, computed per call (it does not trust `built`).  Sized by the collider count; overlapEnqueue() grows them
+        // when called with exhaustive = true.
+        struct Exhaustive { DBuf<float4> shape, mn, mx; DBuf<QPartial> partials; } exh;
+        // Contact queries: candidates (boxes-only overlap records), one 96-byte slot and one flag per candidate, the GJK queue, the scan over the flags.
+        // Sized by `cap` candidates; contactsReserve() alone grows them (mi_world_volume_contacts_reserve, or a blocking call once it knows its candidate total).
+        struct Candidates {
+            uint32_t cap = 0;
+            DBuf<uint4> pairs, slots; DBuf<uint32_t> flags, scanned, queue, queueN;
+            DeviceScan<uint32_t> scan;
+            hipEvent_t ev[4] = {};   // before k_vc_narrow / before k_vc_gjk / behind it / behind k_vc_write: recorded under mi_world_set_stage_timing only
+            bool timed = false;      // the last call recorded them (mi_debug_volume_contacts_times)
+        } cand;
+        // Staging of the blocking variants: inputs copied in, results copied out.  Sized by the call's ray / volume count and record capacity; the blocking
+        // entry points grow it.  One set serves every family: a blocking call synchronises before it returns, so two never use it at once.
+        struct Blocking {
+            DBuf<float> rays; DBuf<uint32_t> hits;   // ray casts
+            DBuf<uint32_t> ranges;                   // the optional entity ranges of any family
+            DBuf<uint32_t> volumes, offsets, totals; DBuf<uint4> records;   // volume queries: mi_overlap_hit is one row of 16 bytes, mi_volume_contact six
+        } host;
     } query;
     int queryBuild();
+    OverlapScene overlapScene(bool exhaustive) const;
     int overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t include, const uint32_t* rangesDev, uint32_t* offsetsDev, uint4* hitsDev, uint32_t capacity,
                        uint32_t* totalDev, bool exhaustive, uint32_t passes, bool boxesOnly);
     int contactsReserve(uint32_t maxCandidates);
@@ -523,7 +542,7 @@ mi_world::~mi_world() {
     if (graphDebug) std::fprintf(stderr, "[mi_physics] step graphs: %u replayed, %u captured, %u plain speculative steps, %llu steps in total\n", graphHits, graphCaptures, graphPlain, (unsigned long long)totalSteps);
     dropStepGraphs();
     if (stream) (void)hipStreamDestroy(stream);
-    for (hipEvent_t& e : query.cEv) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t& e : query.cand.ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : profEvents) (void)hipEventDestroy(e);
     for (auto& set : evSets) for (auto& e : set) if (e) (void)hipEventDestroy(e);
     delete heightmap;

@@ -147,28 +147,16 @@ public:
     struct overlap_result { std::vector<uint32_t> offsets; std::vector<mi_overlap_hit> hits; };
     // entityRanges: empty = the whole scene, otherwise one [lo, hi) pair of entity ids per volume (2 x volumes.size() words)
     overlap_result overlap(const std::vector<mi_query_volume>& volumes, uint32_t include = MI_QUERY_DEFAULT, const std::vector<uint32_t>& entityRanges = {}) {
-        overlap_result r; r.offsets.assign(volumes.size() + 1, 0u);
-        if (volumes.empty()) return r;
-        if (!entityRanges.empty() && entityRanges.size() != 2 * volumes.size()) throw std::invalid_argument("overlap: entityRanges needs one [lo, hi) pair per volume");
-        const uint32_t* ranges = entityRanges.empty() ? nullptr : entityRanges.data();
-        uint32_t total = 0;   // count first, then fetch: the count-only call costs one pass
-        check(mi_world_overlap(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, r.offsets.data(), nullptr, 0, &total), "mi_world_overlap");
-        r.hits.resize(total);
-        if (total) check(mi_world_overlap(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, r.offsets.data(), r.hits.data(), total, &total), "mi_world_overlap");
+        overlap_result r;
+        countThenFetch(mi_world_overlap, "mi_world_overlap", "overlap", volumes, include, entityRanges, r.offsets, r.hits);
         return r;
     }
     // Where each volume touches the world (mi_world_volume_contacts): CSR offsets [volumes + 1] and one manifold per (volume, collider) in ascending
     // collider index; normal from A to B, bit 8 of count_flags set when the volume was B (include/mi_physics.h); read-only.
     struct volume_contacts_result { std::vector<uint32_t> offsets; std::vector<mi_volume_contact> contacts; };
     volume_contacts_result volumeContacts(const std::vector<mi_query_volume>& volumes, uint32_t include = MI_QUERY_DEFAULT, const std::vector<uint32_t>& entityRanges = {}) {
-        volume_contacts_result r; r.offsets.assign(volumes.size() + 1, 0u);
-        if (volumes.empty()) return r;
-        if (!entityRanges.empty() && entityRanges.size() != 2 * volumes.size()) throw std::invalid_argument("volumeContacts: entityRanges needs one [lo, hi) pair per volume");
-        const uint32_t* ranges = entityRanges.empty() ? nullptr : entityRanges.data();
-        uint32_t total = 0;   // count first, then fetch
-        check(mi_world_volume_contacts(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, r.offsets.data(), nullptr, 0, &total), "mi_world_volume_contacts");
-        r.contacts.resize(total);
-        if (total) check(mi_world_volume_contacts(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, r.offsets.data(), r.contacts.data(), total, &total), "mi_world_volume_contacts");
+        volume_contacts_result r;
+        countThenFetch(mi_world_volume_contacts, "mi_world_volume_contacts", "volumeContacts", volumes, include, entityRanges, r.offsets, r.contacts);
         return r;
     }
     std::vector<mi_overlap_hit> overlapSphere(vec3 center, float radius, uint32_t include = MI_QUERY_DEFAULT) {
@@ -295,6 +283,19 @@ public:
 private:
     mi_world* w_ = nullptr;
     static void check(int rc, const char* what) { if (rc != MI_OK) throw std::runtime_error(std::string(what) + ": " + mi_last_error()); }
+    // The blocking volume queries (overlap, volumeContacts): count first, then fetch — the count-only call costs one pass.  Empty input gives offsets = {0}.
+    template <class Record>
+    void countThenFetch(int (*query)(mi_world*, uint32_t, const mi_query_volume*, uint32_t, const uint32_t*, uint32_t*, Record*, uint32_t, uint32_t*), const char* symbol, const char* method,
+                        const std::vector<mi_query_volume>& volumes, uint32_t include, const std::vector<uint32_t>& entityRanges, std::vector<uint32_t>& offsets, std::vector<Record>& records) {
+        offsets.assign(volumes.size() + 1, 0u);
+        if (volumes.empty()) return;
+        if (!entityRanges.empty() && entityRanges.size() != 2 * volumes.size()) throw std::invalid_argument(std::string(method) + ": entityRanges needs one [lo, hi) pair per volume");
+        const uint32_t* ranges = entityRanges.empty() ? nullptr : entityRanges.data();
+        uint32_t total = 0;
+        check(query(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, offsets.data(), nullptr, 0, &total), symbol);
+        records.resize(total);
+        if (total) check(query(w_, (uint32_t)volumes.size(), volumes.data(), include, ranges, offsets.data(), records.data(), total, &total), symbol);
+    }
     scene_entity addEntity(const trs& t, uint32_t kind, const rigid_body_component* rb, const std::vector<collider_component>& colliders) {
         mi_entity_desc d{};
         d.position[0] = t.position.x; d.position[1] = t.position.y; d.position[2] = t.position.z;

@@ -6,7 +6,7 @@ world types: the query makes the volume A; the step makes A whichever AABB start
 world index; pairKey in csrc/kernels_broad.hpp).  Equal-type pairs whose A is the scene collider are "reversed": no comparison uses them.
 
 Also here: the volume sets of the GPU tests (those of overlap_ref plus probes placed on the scene's hulls and on the corner of its ground,
-for the type pairs random volumes hardly ever give), and the edge volumes of the accelerated-versus-exhaustive test."""
+for the type pairs random volumes hardly ever give)."""
 from dataclasses import replace
 
 import numpy as np
@@ -130,42 +130,6 @@ def compare_with_oracle(offsets, recs, expected, reversed_pairs):
             problems.append(f"{key}: got flags {int(r['count_flags']):#x} entity {int(r['entity'])} normal {r['normal']} points {r['points'][:max(n, 1)]}; "
                             f"oracle B={e['volume_is_b']} entity {e['entity']} normal {e['normal']} points {e['points']}")
     return problems
-
-
-# ---- the edge volumes of the accelerated-versus-exhaustive test
-def edge_volumes(rng, lo, hi, hull_ok):
-    """Inside the grid, partly outside, wholly outside, larger than the whole grid, zero-radius spheres, every invalid kind (last).
-    Returns (volumes, number of invalid ones)."""
-    lo = np.asarray(lo, float); hi = np.asarray(hi, float); span = hi - lo
-    parts = [R.make_volumes(int(rng.integers(1 << 30)), 24, lo, hi, 0.15, 0.04 * float(span.max()) + 1.0),
-             R.make_volumes(int(rng.integers(1 << 30)), 6, lo - 0.1 * span, hi + 0.1 * span, 0.5, 0.3 * float(span.max())),
-             R.make_volumes(int(rng.integers(1 << 30)), 2, hi + 2.0 * span, hi + 3.0 * span, 0.5, 3.0)]
-    big = [capi.sphere_volume((lo + hi) / 2, 4.0 * float(span.max())), capi.box_volume((lo + hi) / 2, 3.0 * span),
-           capi.box_volume(lo, 2.5 * span, rotation=(0.1, 0.2, 0.3, 0.9)), capi.capsule_volume(lo - span, hi + span, 0.5 * float(span.max()))]
-    zero = [capi.sphere_volume(rng.uniform(lo, hi), 0.0) for _ in range(8)] + [capi.box_volume(rng.uniform(lo, hi), (0, 0, 0)) for _ in range(4)]
-    bad = [capi.sphere_volume((np.nan, 0, 0), 1.0), capi.sphere_volume((0, 1, 0), -1.0), capi.sphere_volume((0, 1, 0), np.inf),
-           capi.make_volume(9, [0, 0, 0, 1]), capi.make_volume(0xFF, [0, 0, 0, 1]), capi.hull_volume(99), capi.box_volume((0, 1, 0), (-1, 1, 1)),
-           capi.box_volume((0, 1, 0), (1, -1, 1), rotation=(0, 0, 0, 1)), capi.capsule_volume((0, 0, 0), (0, 1, 0), -0.5),
-           capi.make_volume(capi.SPHERE, [0, 1, 0, 50.0], position=(np.inf, 0, 0)), capi.make_volume(capi.SPHERE, [0, 1, 0, 50.0], rotation=(0, np.nan, 0, 1)),
-           capi.make_volume(capi.SPHERE, [0, 1, 0, 50.0], position=(3e38, 3e38, 0), rotation=(0, 0, 1, 0))]
-    vols = np.concatenate(parts + big + zero + bad)
-    if not hull_ok:
-        vols = vols[vols["type"] != capi.HULL]
-    return vols, len([b for b in bad if hull_ok or b["type"][0] != capi.HULL])
-
-
-def dense_cluster():
-    """3000 static spheres in a unit cube (many per grid cell) and a sparse ring of bodies that keeps the cells small: a volume over the
-    cube walks a few hundred cells and has far more candidates than the LDS sort bound of the ordered write (1024)."""
-    rng = np.random.default_rng(77)
-    n, m = 3000, 64
-    e = np.concatenate([scenes.make_entities(m), scenes.make_entities(n, capi.ENTITY_STATIC)])
-    ang = np.linspace(0, 2 * np.pi, m, endpoint=False)
-    e["position"][:m] = np.stack([12 * np.cos(ang), np.full(m, 1.0), 12 * np.sin(ang)], axis=1)
-    e["position"][m:] = rng.uniform(0.0, 1.0, (n, 3)) + (0, 0.5, 0)
-    c = scenes.make_colliders(n + m, capi.SPHERE)
-    c["shape"][:, 3] = 0.1
-    return scenes.Scene("dense_cluster", e, np.arange(n + m, dtype=np.uint32), c, 10)
 
 
 def sunk_sphere_case():

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import overlap_ref as R
+import query_helpers as Q
 
 pytestmark = pytest.mark.gpu
 
@@ -15,37 +16,8 @@ RIGID, ALL = 1, 31
 SORT_BOUND = 1024   # kOvSortMax: the longest segment a wave sorts in LDS
 
 
-def _world(mi, sc, steps=0):
-    w = sc.populate(mi.create_world(0))
-    if steps:
-        w.step_fixed(sc.settings(), sc.dt, steps)
-    return w
-
-
-def _bodies(sc):
-    from d3d12renderer_amd import capi
-    return np.flatnonzero((sc.entities["kind"] == capi.ENTITY_DYNAMIC) | (sc.entities["kind"] == capi.ENTITY_KINEMATIC)).astype(np.uint32)
-
-
-def _check_result(offsets, hits, count, what=""):
-    """CSR shape, the volume column, and every segment strictly ascending in collider index."""
-    assert len(offsets) == count + 1 and offsets[0] == 0 and offsets[-1] == len(hits), what
-    assert (np.diff(offsets.astype(np.int64)) >= 0).all(), what
-    assert np.array_equal(hits["volume"], np.repeat(np.arange(count, dtype=np.uint32), np.diff(offsets.astype(np.int64)))), what
-    if len(hits) > 1:
-        same = hits["volume"][1:] == hits["volume"][:-1]
-        assert (hits["collider"][1:][same] > hits["collider"][:-1][same]).all(), what
-
-
 def _accel_equals_exhaustive(w, vols, include, ranges=None, what=""):
-    ao, ah = w.overlap(vols, include, ranges)
-    eo, eh = w.debug_overlap_exhaustive(vols, include, ranges)
-    assert ao.tobytes() == eo.tobytes(), f"{what}: offsets differ (first at {np.flatnonzero(ao != eo)[:4]})"
-    if ah.tobytes() != eh.tobytes():
-        bad = [i for i in range(len(ah)) if ah[i].tobytes() != eh[i].tobytes()]
-        raise AssertionError(f"{what}: {len(bad)} of {len(ah)} records differ; first {bad[:4]}: {ah[bad[:2]]} vs {eh[bad[:2]]}")
-    _check_result(ao, ah, len(vols), what)
-    return ao, ah
+    return Q.accel_equals_exhaustive(w.overlap, w.debug_overlap_exhaustive, Q.check_csr, vols, include, ranges, what)
 
 
 # ---- 1. against the reference's trigger path
@@ -55,13 +27,13 @@ def test_sandwiched_by_the_reference_trigger_path(mi_lib, oracle_mod, name, sett
     """shrunk-oracle <= query <= grown-oracle per volume, as entity sets, with no budget: wherever the reference's answer does not depend
     on a relative 1e-3 of the volume's size, the query gives exactly it."""
     sc = R.query_scene(name)
-    w = _world(mi_lib, sc, 300 if settled else 0)
+    w = Q.world(mi_lib, sc, 300 if settled else 0)
     vols = R.volume_set(name, settled)
-    ents = _bodies(sc)
+    ents = Q.bodies(sc)
     states = (ents, w.get_body_states(ents)) if settled else None
     shrunk, grown, (subset, both, ambiguous) = R.oracle_sandwich(oracle_mod, sc, vols, states)
     offsets, hits = w.overlap(vols, include=RIGID)
-    _check_result(offsets, hits, len(vols))
+    Q.check_csr(offsets, hits, len(vols))
     assert (hits["object_type"] == 0).all()
     got = R.entity_sets(offsets, hits, len(vols))
     print(f"{name} settled={settled}: {sum(map(len, shrunk))} shrunk / {sum(map(len, got))} query / {sum(map(len, grown))} grown; both non-empty {both:.0%}, ambiguous {ambiguous:.2%}")
@@ -78,10 +50,10 @@ def test_sandwiched_by_the_reference_trigger_path(mi_lib, oracle_mod, name, sett
 @pytest.mark.parametrize("name", ["shape_zoo", "zones"])
 def test_closed_form_pairs_match_numpy_gaps(mi_lib, name):
     sc = R.query_scene(name)
-    w = _world(mi_lib, sc, 40)
+    w = Q.world(mi_lib, sc, 40)
     vols = np.concatenate([R.volume_set(name, False, per_type=24), R.volume_set(name, True, per_type=8)])
     offsets, hits = w.overlap(vols, include=ALL)
-    _check_result(offsets, hits, len(vols))
+    Q.check_csr(offsets, hits, len(vols))
     shapes = R.scene_world_shapes(sc, *w.physics_transforms())
     compared = skipped = overlapping = 0
     wrong = []
@@ -111,43 +83,6 @@ def test_closed_form_pairs_match_numpy_gaps(mi_lib, name):
 
 
 # ---- 3. accelerated equals exhaustive
-def _edge_volumes(rng, lo, hi, hull_ok):
-    """Inside the grid, partly outside, wholly outside, larger than the whole grid, zero-radius spheres, invalid volumes."""
-    from d3d12renderer_amd import capi
-    lo = np.asarray(lo, float); hi = np.asarray(hi, float); span = hi - lo
-    parts = [R.make_volumes(int(rng.integers(1 << 30)), 40, lo, hi, 0.15, 0.04 * float(span.max()) + 1.0),            # inside
-             R.make_volumes(int(rng.integers(1 << 30)), 8, lo - 0.1 * span, hi + 0.1 * span, 0.5, 0.3 * float(span.max())),   # partly outside, many cells
-             R.make_volumes(int(rng.integers(1 << 30)), 4, hi + 2.0 * span, hi + 3.0 * span, 0.5, 3.0)]                  # wholly outside
-    big = [capi.sphere_volume((lo + hi) / 2, 4.0 * float(span.max())), capi.box_volume((lo + hi) / 2, 3.0 * span),
-           capi.box_volume(lo, 2.5 * span, rotation=(0.1, 0.2, 0.3, 0.9)), capi.capsule_volume(lo - span, hi + span, 0.5 * float(span.max()))]
-    zero = [capi.sphere_volume(rng.uniform(lo, hi), 0.0) for _ in range(16)]
-    bad = [capi.sphere_volume((np.nan, 0, 0), 1.0), capi.sphere_volume((0, 1, 0), -1.0), capi.sphere_volume((0, 1, 0), np.inf),
-           capi.make_volume(9, [0, 0, 0, 1]), capi.make_volume(0xFF, [0, 0, 0, 1]), capi.hull_volume(99), capi.box_volume((0, 1, 0), (-1, 1, 1)),
-           capi.box_volume((0, 1, 0), (1, -1, 1), rotation=(0, 0, 0, 1)), capi.capsule_volume((0, 0, 0), (0, 1, 0), -0.5),
-           capi.make_volume(capi.SPHERE, [0, 1, 0, 50.0], position=(np.inf, 0, 0)), capi.make_volume(capi.SPHERE, [0, 1, 0, 50.0], rotation=(0, np.nan, 0, 1)),
-           capi.make_volume(capi.SPHERE, [0, 1, 0, 50.0], position=(3e38, 3e38, 0), rotation=(0, 0, 1, 0))]
-    vols = np.concatenate(parts + big + zero + bad)
-    if not hull_ok:
-        vols = vols[vols["type"] != capi.HULL]
-    n_bad = len([b for b in bad if hull_ok or b["type"][0] != capi.HULL])
-    return vols, n_bad
-
-
-def _dense_cluster():
-    """3000 static spheres in a unit cube (many per grid cell) and a sparse ring of bodies that keeps the cells small: a volume over the
-    cube walks a few hundred cells and reports far more than the LDS sort bound."""
-    from d3d12renderer_amd import capi, scenes
-    rng = np.random.default_rng(77)
-    n, m = 3000, 64
-    e = np.concatenate([scenes.make_entities(m), scenes.make_entities(n, capi.ENTITY_STATIC)])
-    ang = np.linspace(0, 2 * np.pi, m, endpoint=False)
-    e["position"][:m] = np.stack([12 * np.cos(ang), np.full(m, 1.0), 12 * np.sin(ang)], axis=1)
-    e["position"][m:] = rng.uniform(0.0, 1.0, (n, 3)) + (0, 0.5, 0)
-    c = scenes.make_colliders(n + m, capi.SPHERE)
-    c["shape"][:, 3] = 0.1
-    return scenes.Scene("dense_cluster", e, np.arange(n + m, dtype=np.uint32), c, 10)
-
-
 def test_accelerated_equals_exhaustive(mi_lib):
     from d3d12renderer_amd import capi, scenes
     rng = np.random.default_rng(15)
@@ -155,8 +90,8 @@ def test_accelerated_equals_exhaustive(mi_lib):
              (scenes.obb_pile(128, 4, 128), 60, (-100, -1, -100), (100, 8, 100), False),
              (scenes.terrain_field(), 30, (-18, -1, -18), (18, 10, 18), False)]
     for sc, steps, lo, hi, hull_ok in cases:
-        w = _world(mi_lib, sc, steps)
-        vols, n_bad = _edge_volumes(rng, lo, hi, hull_ok)
+        w = Q.world(mi_lib, sc, steps)
+        vols, n_bad = Q.edge_volumes(rng, lo, hi, hull_ok, (40, 8, 4), 16, 0)
         offsets, hits = _accel_equals_exhaustive(w, vols, ALL, what=sc.name)
         counts = np.diff(offsets.astype(np.int64))
         assert (counts[-n_bad:] == 0).all(), f"{sc.name}: an invalid volume reported something"
@@ -179,8 +114,8 @@ def test_accelerated_equals_exhaustive(mi_lib):
                 assert len(mh) == 0
         w.close()
     # segments beyond the LDS sort bound out of a walk over few cells
-    sc = _dense_cluster()
-    w = _world(mi_lib, sc)
+    sc = Q.dense_cluster()
+    w = Q.world(mi_lib, sc)
     vols = np.concatenate([capi.box_volume((0.5, 1.0, 0.5), (0.6, 0.6, 0.6)), capi.sphere_volume((0.5, 1.0, 0.5), 0.45), capi.sphere_volume((0.2, 0.8, 0.3), 0.3),
                            capi.box_volume((0.5, 1.0, 0.5), (0.7, 0.7, 0.7), rotation=(0.0, 0.38268343, 0.0, 0.92387953)), capi.sphere_volume((12.0, 1.0, 0.0), 0.2),
                            R.make_volumes(5, 6, (0, 0.5, 0), (1, 1.5, 1), 0.05, 0.5)])
@@ -195,7 +130,7 @@ def test_capacity_protocol(mi_lib):
     from d3d12renderer_amd import capi
     import torch
     sc = R.query_scene("shape_zoo")
-    w = _world(mi_lib, sc, 20)
+    w = Q.world(mi_lib, sc, 20)
     vols = R.volume_set("shape_zoo", False)
     offsets, hits = w.overlap(vols, include=ALL)
     total = len(hits)
@@ -228,7 +163,7 @@ def test_capacity_protocol(mi_lib):
 def test_device_variant_equals_host_variant(mi_lib):
     import torch
     sc = R.query_scene("shape_zoo")
-    w = _world(mi_lib, sc, 10)
+    w = Q.world(mi_lib, sc, 10)
     rng = np.random.default_rng(4)
     vols = np.concatenate([R.volume_set("shape_zoo", False), R.volume_set("shape_zoo", True)])
     cap = 16384
@@ -265,7 +200,7 @@ def test_cache_follows_every_change(mi_lib):
     from d3d12renderer_amd import capi, scenes
     import torch
     sc = scenes.shape_zoo(3, 2, 3)
-    w = _world(mi_lib, sc, 5)
+    w = Q.world(mi_lib, sc, 5)
     vols = np.concatenate([R.make_volumes(9, 16, (-4, 0, -4), (4, 5, 4), 0.2, 3.0),
                            R.make_volumes(10, 2, (-45, 0, -45), (45, 6, 45), 1.0, 4.0)])
     rng = np.random.default_rng(2)
@@ -316,10 +251,10 @@ def test_cache_follows_every_change(mi_lib):
 # ---- 7. queries change nothing
 def test_queries_change_nothing(mi_lib):
     sc = R.query_scene("shape_zoo")
-    a = _world(mi_lib, sc); b = _world(mi_lib, sc)
+    a = Q.world(mi_lib, sc); b = Q.world(mi_lib, sc)
     vols = np.concatenate([R.volume_set("shape_zoo", False), R.volume_set("shape_zoo", True)])
     s = sc.settings()
-    ents = _bodies(sc)
+    ents = Q.bodies(sc)
     for i in range(100):
         a.step_fixed(s, sc.dt, 1); b.step_fixed(s, sc.dt, 1)
         b.overlap(vols, include=ALL)
@@ -334,7 +269,7 @@ def test_queries_change_nothing(mi_lib):
 def test_errors(mi_lib):
     from d3d12renderer_amd import capi, scenes, sharding
     sc = scenes.shape_zoo(2, 1, 2)
-    w = _world(mi_lib, sc)
+    w = Q.world(mi_lib, sc)
     p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
     vol = capi.sphere_volume((0, 1, 0), 5.0); off = np.zeros(2, np.uint32); hits = np.zeros(64, capi.overlap_hit_dtype); total = C.c_uint32(7)
     u = C.c_uint32
@@ -355,7 +290,7 @@ def test_errors(mi_lib):
     o, h = w.overlap(np.zeros(0, capi.query_volume_dtype))
     assert len(o) == 1 and o[0] == 0 and len(h) == 0
     w.close()
-    w = _world(mi_lib, sc)
+    w = Q.world(mi_lib, sc)
     w.shard_enable(sharding._desc_for(sharding.tile_grid(sc, 1), 0))
     for name in ("world_overlap", "debug_overlap_exhaustive"):
         assert w.L.fn(name)(w.h, u(1), p(vol), u(ALL), None, p(off), p(hits), u(64), C.byref(total)) == -6

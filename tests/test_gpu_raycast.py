@@ -6,19 +6,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import query_helpers as Q
 from raycast_ref import SceneRef
 
 pytestmark = pytest.mark.gpu
 
 ALL = 31
-
-
-def _world(mi, sc, steps=0):
-    w = sc.populate(mi.create_world(0))
-    s = sc.settings()
-    if steps:
-        w.step_fixed(s, sc.dt, steps)
-    return w
 
 
 def _ref(w, sc):
@@ -82,7 +75,7 @@ def _compare_to_ref(hits, ref, o, d, what, budget=0.002):
 def test_zoo_matches_numpy_reference(mi_lib):
     from d3d12renderer_amd import scenes
     sc = scenes.shape_zoo()
-    w = _world(mi_lib, sc, 30)
+    w = Q.world(mi_lib, sc, 30)
     ref = _ref(w, sc)
     rng = np.random.default_rng(11)
     o, d = _random_rays(rng, 4096, (-7, -1, -7), (7, 8, 7))
@@ -97,7 +90,7 @@ def test_directions_of_any_length(mi_lib):
     match the numpy reference, and the grid still equals the exhaustive scan."""
     from d3d12renderer_amd import scenes
     sc = scenes.shape_zoo()
-    w = _world(mi_lib, sc, 30)
+    w = Q.world(mi_lib, sc, 30)
     ref = _ref(w, sc)
     rng = np.random.default_rng(12)
     o, d = _random_rays(rng, 2048, (-7, -1, -7), (7, 8, 7))
@@ -129,7 +122,7 @@ def test_accelerated_equals_exhaustive(mi_lib):
              (scenes.obb_pile(128, 4, 128), 60, (-100, -1, -100), (100, 8, 100)),
              (scenes.terrain_field(), 30, (-18, -1, -18), (18, 10, 18))]
     for sc, steps, lo, hi in cases:
-        w = _world(mi_lib, sc, steps)
+        w = Q.world(mi_lib, sc, steps)
         o, d, max_t = _edge_rays(rng, 4096, lo, hi)
         h = _check_accel_equals_exhaustive(w, o, d, max_t)
         assert (h["entity"] == 0xFFFFFFFF).any() and (h["entity"] != 0xFFFFFFFF).any(), sc.name
@@ -153,7 +146,7 @@ def _terrain_scene(holes=()):
 
 def test_terrain(mi_lib):
     sc = _terrain_scene(holes=((1, 1),))
-    w = _world(mi_lib, sc)
+    w = Q.world(mi_lib, sc)
     hm = sc.heightmap
     s = hm["chunk_size"] / 128.0
     corner = np.asarray(hm["min_corner"], np.float64)
@@ -197,7 +190,7 @@ def test_rigid_hits_are_what_the_poke_pushes(mi_lib):
         target = pos[rng.integers(0, 18)] + rng.uniform(-0.2, 0.2, 3)
         o = (target + np.float32([rng.uniform(-2, 2), 6.0, rng.uniform(-2, 2)])).astype(np.float32)
         d = (target - o) / np.linalg.norm(target - o)
-        a = _world(mi_lib, sc); b = _world(mi_lib, sc)
+        a = Q.world(mi_lib, sc); b = Q.world(mi_lib, sc)
         hit = a.raycast(o[None], d[None].astype(np.float32), include=1)[0]
         b.test_interactions(o[None], d[None].astype(np.float32))
         a.step_fixed(sc.settings(), sc.dt, 1); b.step_fixed(sc.settings(), sc.dt, 1)
@@ -214,7 +207,7 @@ def test_cache_follows_every_change(mi_lib):
     from d3d12renderer_amd import capi, scenes
     import torch
     sc = scenes.shape_zoo(3, 2, 3)
-    w = _world(mi_lib, sc, 5)
+    w = Q.world(mi_lib, sc, 5)
     rng = np.random.default_rng(2)
     o, d, max_t = _edge_rays(rng, 1024, (-4, -1, -4), (4, 6, 4))
 
@@ -257,7 +250,7 @@ def test_cache_follows_every_change(mi_lib):
     w.close()
     # the heightmap
     sc = _terrain_scene()
-    w = _world(mi_lib, sc)
+    w = Q.world(mi_lib, sc)
     p = np.float32([[1.3, 30.0, -2.1]]); dn = np.float32([[0, -1, 0]])
     y0 = 30.0 - float(w.raycast(p, dn, include=4)["t"][0])
     w.update_heightmap(np.asarray(sc.heightmap["min_corner"]) + np.float32([0, 3.0, 0]), sc.heightmap["amplitude"])
@@ -270,7 +263,7 @@ def test_device_variant_equals_host_variant(mi_lib):
     from d3d12renderer_amd import capi, scenes
     import torch
     sc = scenes.shape_zoo()
-    w = _world(mi_lib, sc, 10)
+    w = Q.world(mi_lib, sc, 10)
     rng = np.random.default_rng(4)
     o, d, max_t = _edge_rays(rng, 2048, (-7, -1, -7), (7, 8, 7))
     rays = np.zeros((len(o), 8), np.float32); rays[:, :3] = o; rays[:, 3:6] = d; rays[:, 6] = max_t
@@ -299,7 +292,7 @@ def test_device_variant_equals_host_variant(mi_lib):
 def test_queries_change_nothing(mi_lib):
     from d3d12renderer_amd import scenes
     sc = scenes.shape_zoo()
-    a = _world(mi_lib, sc); b = _world(mi_lib, sc)
+    a = Q.world(mi_lib, sc); b = Q.world(mi_lib, sc)
     rng = np.random.default_rng(6)
     o, d = _random_rays(rng, 512, (-7, -1, -7), (7, 8, 7))
     s = sc.settings()
@@ -315,7 +308,7 @@ def test_queries_change_nothing(mi_lib):
 def test_errors(mi_lib):
     from d3d12renderer_amd import capi, scenes, sharding
     sc = scenes.shape_zoo(2, 1, 2)
-    w = _world(mi_lib, sc)
+    w = Q.world(mi_lib, sc)
     assert len(w.raycast(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32))) == 0
     f = w.L.fn("world_raycast")
     out = np.zeros(1, capi.ray_hit_dtype); v = np.zeros(3, np.float32)
@@ -328,7 +321,7 @@ def test_errors(mi_lib):
     h = w.raycast(np.float32([[0, 5, 0], [0, 5, 0], [0, 5, 0]]), np.float32([[0, 0, 0], [np.nan, -1, 0], [0, -1, 0]]))
     assert h["entity"][0] == 0xFFFFFFFF and h["entity"][1] == 0xFFFFFFFF and h["entity"][2] != 0xFFFFFFFF   # zero / NaN direction: a miss
     w.close()
-    w = _world(mi_lib, sc)
+    w = Q.world(mi_lib, sc)
     w.shard_enable(sharding._desc_for(sharding.tile_grid(sc, 1), 0))
     assert f(w.h, C.c_uint32(1), p(v), p(v), None, C.c_uint32(7), None, p(out)) == -6
     w.close()

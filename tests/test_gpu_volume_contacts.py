@@ -1,7 +1,8 @@
 """Contact-manifold scene queries on the GPU (mi_world_volume_contacts, ..._device_async, ..._reserve, mi_debug_volume_contacts_exhaustive):
 bit for bit against the reference's narrow phase (tests/contact_ref.py: the volumes as rigid bodies of an oracle world, one step), the
 accelerated candidates against the exhaustive ones byte for byte, the capacity protocol, the device variant with and without enough
-staging, that queries change nothing a step computes and follow every pose change, and the sharded world's refusal."""
+staging, that queries change nothing a step computes and follow every pose change, overlaps, contacts and rays interleaved on one world
+(they share the blocking variants' staging), and the sharded world's refusal."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 
 import contact_ref as CR
 import overlap_ref as R
+import query_helpers as Q
 
 pytestmark = pytest.mark.gpu
 
@@ -16,27 +18,9 @@ RIGID_STATIC, ALL = 3, 31
 ERR_CAPACITY, ERR_UNSUPPORTED = -5, -6
 
 
-def _world(mi, sc, steps=0):
-    w = sc.populate(mi.create_world(0))
-    if steps:
-        w.step_fixed(sc.settings(), sc.dt, steps)
-    return w
-
-
-def _bodies(sc):
-    from d3d12renderer_amd import capi
-    return np.flatnonzero((sc.entities["kind"] == capi.ENTITY_DYNAMIC) | (sc.entities["kind"] == capi.ENTITY_KINEMATIC)).astype(np.uint32)
-
-
 def _check_result(offsets, recs, count, what=""):
-    """CSR shape, the volume column, every segment strictly ascending in collider index, counts 1..4, rows past the count all zero."""
-    assert len(offsets) == count + 1 and offsets[0] == 0 and offsets[-1] == len(recs), what
-    sizes = np.diff(offsets.astype(np.int64))
-    assert (sizes >= 0).all(), what
-    assert np.array_equal(recs["volume"], np.repeat(np.arange(count, dtype=np.uint32), sizes)), what
-    if len(recs) > 1:
-        same = recs["volume"][1:] == recs["volume"][:-1]
-        assert (recs["collider"][1:][same] > recs["collider"][:-1][same]).all(), what
+    """The CSR checks, and of the records: counts 1..4, no flag bits but the volume-was-B one, rows past the count all zero."""
+    Q.check_csr(offsets, recs, count, what)
     n = recs["count_flags"] & 7
     assert ((n >= 1) & (n <= 4)).all() and ((recs["count_flags"] & ~np.uint32(0x107)) == 0).all(), what
     unused = np.arange(4)[None, :] >= n[:, None]
@@ -44,14 +28,7 @@ def _check_result(offsets, recs, count, what=""):
 
 
 def _accel_equals_exhaustive(w, vols, include, ranges=None, what=""):
-    ao, ar = w.volume_contacts(vols, include, ranges)
-    eo, er = w.debug_volume_contacts_exhaustive(vols, include, ranges)
-    assert ao.tobytes() == eo.tobytes(), f"{what}: offsets differ (first at {np.flatnonzero(ao != eo)[:4]})"
-    if ar.tobytes() != er.tobytes():
-        bad = [i for i in range(len(ar)) if ar[i].tobytes() != er[i].tobytes()]
-        raise AssertionError(f"{what}: {len(bad)} of {len(ar)} records differ; first {bad[:4]}: {ar[bad[:2]]} vs {er[bad[:2]]}")
-    _check_result(ao, ar, len(vols), what)
-    return ao, ar
+    return Q.accel_equals_exhaustive(w.volume_contacts, w.debug_volume_contacts_exhaustive, _check_result, vols, include, ranges, what)
 
 
 # ---- 1. against the reference's narrow phase
@@ -61,8 +38,8 @@ def test_bit_equal_to_the_reference_narrow_phase(mi_lib, oracle_mod, name, settl
     """The non-reversed (volume, collider) records are exactly the oracle's manifolds, with its bits in the normal, the contact count, every
     point and every depth, the right entity, object type and volume-was-B flag.  No tolerance."""
     sc = R.query_scene(name)
-    w = _world(mi_lib, sc, 300 if settled else 0)
-    ents = _bodies(sc)
+    w = Q.world(mi_lib, sc, 300 if settled else 0)
+    ents = Q.bodies(sc)
     states = (ents, w.get_body_states(ents)) if settled else None
     vols = CR.contact_volume_set(name, settled, sc, *w.physics_transforms())
     expected, reversed_pairs, info = CR.oracle_manifolds(oracle_mod, sc, vols, states)
@@ -82,8 +59,8 @@ def test_accelerated_equals_exhaustive(mi_lib):
     rng = np.random.default_rng(15)
     cases = [(R.query_scene("shape_zoo"), 30, (-7, -1, -7), (7, 8, 7)), (R.query_scene("zones"), 30, (-6, -1, -6), (8, 7, 6))]
     for sc, steps, lo, hi in cases:
-        w = _world(mi_lib, sc, steps)
-        vols, n_bad = CR.edge_volumes(rng, lo, hi, True)
+        w = Q.world(mi_lib, sc, steps)
+        vols, n_bad = Q.edge_volumes(rng, lo, hi, True, (24, 6, 2), 8, 4)
         offsets, recs = _accel_equals_exhaustive(w, vols, ALL, what=sc.name)
         counts = np.diff(offsets.astype(np.int64))
         assert (counts[-n_bad:] == 0).all(), f"{sc.name}: an invalid volume reported something"
@@ -106,8 +83,8 @@ def test_accelerated_equals_exhaustive(mi_lib):
                 assert len(mr) == 0
         w.close()
     # candidate segments beyond the LDS sort bound of the ordered write, out of a walk over few cells
-    sc = CR.dense_cluster()
-    w = _world(mi_lib, sc)
+    sc = Q.dense_cluster()
+    w = Q.world(mi_lib, sc)
     vols = np.concatenate([capi.box_volume((0.5, 1.0, 0.5), (0.6, 0.6, 0.6)), capi.sphere_volume((0.5, 1.0, 0.5), 0.45), capi.sphere_volume((0.2, 0.8, 0.3), 0.3),
                            capi.box_volume((0.5, 1.0, 0.5), (0.7, 0.7, 0.7), rotation=(0.0, 0.38268343, 0.0, 0.92387953)), capi.sphere_volume((12.0, 1.0, 0.0), 0.2),
                            R.make_volumes(5, 6, (0, 0.5, 0), (1, 1.5, 1), 0.05, 0.5)])
@@ -120,7 +97,7 @@ def test_accelerated_equals_exhaustive(mi_lib):
 # ---- 3. capacity protocol
 def test_capacity_protocol(mi_lib):
     sc = R.query_scene("shape_zoo")
-    w = _world(mi_lib, sc, 20)
+    w = Q.world(mi_lib, sc, 20)
     vols = CR.contact_volume_set("shape_zoo", False, sc, *CR.start_poses(sc), per_type=16)
     offsets, recs = w.volume_contacts(vols, include=ALL)
     total = len(recs)
@@ -165,12 +142,12 @@ def test_device_variant(mi_lib):
     import torch
     sc = R.query_scene("shape_zoo")
     vols = CR.contact_volume_set("shape_zoo", False, sc, *CR.start_poses(sc), per_type=16)
-    ref = _world(mi_lib, sc, 10)
+    ref = Q.world(mi_lib, sc, 10)
     offsets, recs = ref.volume_contacts(vols, include=ALL)
     total = len(recs)
     ref.close()
     assert total > 50
-    w = _world(mi_lib, sc, 10)
+    w = Q.world(mi_lib, sc, 10)
     cap = total + 8
     vols_d = torch.tensor(np.frombuffer(vols.tobytes(), np.uint8).copy(), device="cuda")
 
@@ -193,7 +170,7 @@ def test_device_variant(mi_lib):
     assert rc == 0 and int(t[0]) == total and int(t[1]) == candidates and o.tobytes() == offsets.tobytes() and r.tobytes() == recs[: total // 2].tobytes()
     w.close()
     # a reservation below the candidates: the first reserved candidates are evaluated, totals[1] still tells the full number
-    w = _world(mi_lib, sc, 10)
+    w = Q.world(mi_lib, sc, 10)
     reserved = candidates // 2
     w.volume_contacts_reserve(reserved)
     rc, o, r, t = run(cap)
@@ -208,10 +185,10 @@ def test_device_variant(mi_lib):
 def test_queries_change_nothing_and_follow_the_poses(mi_lib):
     from d3d12renderer_amd import capi
     sc = R.query_scene("shape_zoo")
-    a = _world(mi_lib, sc); b = _world(mi_lib, sc)
+    a = Q.world(mi_lib, sc); b = Q.world(mi_lib, sc)
     vols = CR.contact_volume_set("shape_zoo", False, sc, *CR.start_poses(sc), per_type=8)
     s = sc.settings()
-    ents = _bodies(sc)
+    ents = Q.bodies(sc)
     previous = None
     for i in range(40):
         a.step_fixed(s, sc.dt, 1); b.step_fixed(s, sc.dt, 1)
@@ -236,11 +213,49 @@ def test_queries_change_nothing_and_follow_the_poses(mi_lib):
     a.close(); b.close()
 
 
-# ---- 6. errors
+# ---- 6. one world, every family: the blocking variants share their staging
+def test_families_interleaved_on_one_world(mi_lib):
+    """Overlaps, contacts and rays in turn on one world, with growing and shrinking volume counts and a call without entity ranges behind one
+    with them: a repeated call returns the bytes of its first occurrence, and every call the bytes a fresh world gives for it alone."""
+    sc = R.query_scene("shape_zoo")
+    full = R.volume_set("shape_zoo", False); small = full[:8]
+    assert len(full) == 96
+    rng = np.random.default_rng(23)
+    o = rng.uniform((-7, -1, -7), (7, 8, 7), (64, 3)).astype(np.float32)
+    d = rng.normal(size=(64, 3)); d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    half = len(sc.entities) // 2
+    ray_ranges = np.stack([np.zeros(64), np.full(64, half)], axis=1).astype(np.uint32); ray_ranges[::2] += half
+    vol_ranges = np.stack([np.zeros(96), np.full(96, half)], axis=1).astype(np.uint32); vol_ranges[1::2] += half
+    calls = {"overlap small": lambda w: w.overlap(small, include=ALL),
+             "contacts full": lambda w: w.volume_contacts(full, include=ALL),
+             "rays ranged": lambda w: (w.raycast(o, d, include=ALL, entity_ranges=ray_ranges),),
+             "contacts small": lambda w: w.volume_contacts(small, include=ALL),
+             "overlap full ranged": lambda w: w.overlap(full, include=ALL, entity_ranges=vol_ranges)}
+    order = ["overlap small", "contacts full", "overlap small", "rays ranged", "contacts small", "overlap full ranged", "contacts full"]
+
+    def run(w, name):
+        return tuple(a.tobytes() for a in calls[name](w))
+
+    alone = {}
+    for name in calls:
+        w = Q.world(mi_lib, sc, 10)
+        alone[name] = run(w, name)
+        w.close()
+    assert len(alone["contacts full"][1]) > 0 and len(alone["overlap full ranged"][1]) > 0, "the full sets report nothing"
+    w = Q.world(mi_lib, sc, 10)
+    first = {}
+    for i, name in enumerate(order):
+        got = run(w, name)
+        assert got == first.setdefault(name, got), f"call {i} ({name}) differs from its first occurrence"
+        assert got == alone[name], f"call {i} ({name}) differs from the same call on a fresh world"
+    w.close()
+
+
+# ---- 7. errors
 def test_errors_and_sharded_world(mi_lib):
     from d3d12renderer_amd import capi, scenes, sharding
     sc = scenes.shape_zoo(2, 1, 2)
-    w = _world(mi_lib, sc)
+    w = Q.world(mi_lib, sc)
     p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
     vol = capi.sphere_volume((0, 1, 0), 5.0); off = np.zeros(2, np.uint32); recs = np.zeros(64, capi.volume_contact_dtype); total = C.c_uint32(7)
     u = C.c_uint32
@@ -254,7 +269,7 @@ def test_errors_and_sharded_world(mi_lib):
     o, r = w.volume_contacts(np.zeros(0, capi.query_volume_dtype))
     assert len(o) == 1 and o[0] == 0 and len(r) == 0
     w.close()
-    w = _world(mi_lib, sc)
+    w = Q.world(mi_lib, sc)
     w.shard_enable(sharding._desc_for(sharding.tile_grid(sc, 1), 0))
     for name in ("world_volume_contacts", "debug_volume_contacts_exhaustive"):
         assert w.L.fn(name)(w.h, u(1), p(vol), u(ALL), None, p(off), p(recs), u(64), C.byref(total)) == ERR_UNSUPPORTED

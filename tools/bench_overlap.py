@@ -10,13 +10,11 @@ steps/s figures are host wall time.  `count_pass_share` = the blocking count-onl
 volumes: how much of a query is the first of the two passes that both run the predicate."""
 import argparse
 import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from query_bench_common import settled_world, stream_timer
 
 CAPACITY = 1 << 22   # records (64 MiB); `truncated` says when a workload needed more
 
@@ -38,21 +36,9 @@ def volumes_for(kind, n, lo, hi, rng):
 def measure(mi, sc, settle, reps, lo, hi):
     import torch
     from d3d12renderer_amd import capi
-    w = sc.populate(mi.create_world(0))
-    s = sc.settings()
-    w.step_fixed(s, sc.dt, settle)
-    st = torch.cuda.ExternalStream(w.stream_ptr())
+    w, s, st = settled_world(mi, sc, settle)
+    timed = stream_timer(st, reps)
     rng = np.random.default_rng(1)
-    ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
-
-    def timed(fn, n=reps):
-        a, b = ev(), ev()
-        a.record(st)
-        for _ in range(n):
-            fn()
-        b.record(st)
-        b.synchronize()
-        return a.elapsed_time(b) / n
 
     hits = torch.zeros(CAPACITY * 16, dtype=torch.uint8, device="cuda")
     total = torch.zeros(1, dtype=torch.int32, device="cuda")

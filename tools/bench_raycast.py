@@ -8,13 +8,11 @@ HIP events on the world's stream (torch.cuda.ExternalStream), the exhaustive sca
 figures are host wall time."""
 import argparse
 import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from query_bench_common import settled_world, stream_timer
 
 
 def rays_for(kind, n, lo, hi, rng):
@@ -39,21 +37,9 @@ def rays_for(kind, n, lo, hi, rng):
 def measure(mi, sc, settle, reps, lo, hi):
     import torch
     from d3d12renderer_amd import capi
-    w = sc.populate(mi.create_world(0))
-    s = sc.settings()
-    w.step_fixed(s, sc.dt, settle)
-    st = torch.cuda.ExternalStream(w.stream_ptr())
+    w, s, st = settled_world(mi, sc, settle)
+    timed = stream_timer(st, reps)
     rng = np.random.default_rng(1)
-    ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
-
-    def timed(fn, n=reps):
-        a, b = ev(), ev()
-        a.record(st)
-        for _ in range(n):
-            fn()
-        b.record(st)
-        b.synchronize()
-        return a.elapsed_time(b) / n
 
     out = {}
     bufs = {}

@@ -10,12 +10,10 @@ pairs (mi_debug_volume_contacts_times, under set_stage_timing) in one extra call
 exhaustive ratio compares the two blocking count-only calls on (at most) 256 of the volumes, so that their copies are alike."""
 import argparse
 import json
-import sys
-from pathlib import Path
 
 import numpy as np
 
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from query_bench_common import settled_world, stream_timer
 
 RESERVE = 1 << 20    # candidates (about 150 MiB of staging); `truncated` says when a workload found more
 CAPACITY = 1 << 19   # records (48 MiB)
@@ -44,20 +42,9 @@ def mixed_volumes(n, lo, hi, rng, hulls):
 def measure(mi, sc, settle, reps, n, lo, hi):
     import torch
     from d3d12renderer_amd import capi
-    w = sc.populate(mi.create_world(0))
-    w.step_fixed(sc.settings(), sc.dt, settle)
-    st = torch.cuda.ExternalStream(w.stream_ptr())
+    w, _, st = settled_world(mi, sc, settle)
+    timed = stream_timer(st, reps)
     rng = np.random.default_rng(1)
-    ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
-
-    def timed(fn, k=reps):
-        a, b = ev(), ev()
-        a.record(st)
-        for _ in range(k):
-            fn()
-        b.record(st)
-        b.synchronize()
-        return a.elapsed_time(b) / k
 
     host = mixed_volumes(n, lo, hi, rng, bool(sc.hulls))
     vols = torch.tensor(np.frombuffer(host.tobytes(), np.uint8).copy(), device="cuda")
