@@ -46,6 +46,9 @@ volume_contact_dtype = np.dtype([("entity", "<u4"), ("collider", "<u4"), ("objec
                                  ("points", "<f4", (4, 4))])
 assert volume_contact_dtype.itemsize == 96
 VOLUME_CONTACT_COUNT_MASK, VOLUME_CONTACT_VOLUME_IS_B = 7, 1 << 8
+# mi_terrain_contact (mi_world_terrain_contacts): one record per contact of a volume with the heightmap terrain, in the reference's emission order
+terrain_contact_dtype = np.dtype([("point", "<f4", 3), ("depth", "<f4"), ("normal", "<f4", 3), ("volume", "<u4")])
+assert terrain_contact_dtype.itemsize == 32
 MI_ERR_CAPACITY = -5
 QUERY_ALL = QUERY_RIGID_BODIES | QUERY_STATIC | QUERY_TERRAIN | QUERY_TRIGGERS | QUERY_FORCE_FIELDS
 
@@ -425,6 +428,37 @@ class World:
         if rc != MI_ERR_CAPACITY:
             self.L.check(rc, "world_volume_contacts_device_async")
         return rc
+
+    # --- terrain contact scene queries (where a shape touches the heightmap terrain; read-only): no include flags, no entity ranges
+    def terrain_contacts_raw(self, volumes, capacity, fill=0, null_at_zero=True):
+        """One mi_world_terrain_contacts call -> (status, offsets[count + 1], records[capacity], total).  capacity = None: max(16, 4 x count)
+        records first, and once more with the exact number when MI_ERR_CAPACITY tells it.  The records start out as bytes of `fill`."""
+        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
+        offsets = np.zeros(len(v) + 1, np.uint32)
+        total = C.c_uint32(0)
+        cap = max(16, 4 * len(v)) if capacity is None else int(capacity)
+        f = self.L.fn("world_terrain_contacts")
+        while True:
+            recs = np.frombuffer(bytearray([fill]) * (terrain_contact_dtype.itemsize * cap), dtype=terrain_contact_dtype)
+            rc = f(self.h, C.c_uint32(len(v)), _ptr(v), _ptr(offsets), None if null_at_zero and not cap else _ptr(recs), C.c_uint32(cap), C.byref(total))
+            if rc == MI_ERR_CAPACITY and capacity is None:
+                cap = total.value
+                continue
+            return rc, offsets, recs, total.value
+
+    def terrain_contacts(self, volumes):
+        """mi_world_terrain_contacts: (offsets[count + 1], records) in CSR form, `terrain_contact_dtype` records per volume in the reference's
+        emission order: what a rigid body of the volume's shape at its pose would get from the terrain in one step."""
+        rc, offsets, recs, total = self.terrain_contacts_raw(volumes, None)
+        self.L.check(rc, "world_terrain_contacts")
+        return offsets, recs[:total]
+
+    def terrain_contacts_device_async(self, n, volumes_ptr, offsets_ptr, contacts_ptr, capacity, total_ptr):
+        """mi_world_terrain_contacts_device_async: device buffers (volumes: n x 96 bytes; offsets: n + 1 uint32; contacts: capacity x 32 bytes; total:
+        1 uint32), enqueued on the world's stream without a host synchronisation; nothing is written past `capacity` records."""
+        self.L.check(self.L.fn("world_terrain_contacts_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_void_p(offsets_ptr),
+                                                                       C.c_void_p(contacts_ptr or None), C.c_uint32(capacity), C.c_void_p(total_ptr)),
+                     "world_terrain_contacts_device_async")
 
     def update_constraints(self, ctype, ids, pods):
         """getConstraint(scene, handle) = ... for many constraints of one type."""

@@ -256,9 +256,20 @@ __device__ __forceinline__ bool hmActive(uint32_t tag, uint32_t& type) {
     // behaviour); what it evidently means — their lowest point against the surface, like every other type, no triangle routine — is what runs here
     return ((tag >> 8) & 0xFFu) == OBJ_RIGID_BODY;
 }
-struct HmOut {   // where the WRITE passes put contact j of collider i
+// What differs between the two users of the pipeline below is a compile-time policy, the `Out` argument of its kernels: who is active, what a collider's count
+// is kept as (Packed: the word the scan sums), whether the WRITE passes may run, where a collider's contacts start and where contact j goes.  HmOut = the step (the
+// world's rigid-body colliders, contacts appended to the pair list as manifolds); HmQueryOut (kernels_terrain_query.hpp) = mi_world_terrain_contacts (query volumes,
+// 32-byte caller records).  Everything else — windows, order, stash, the triangle tests — is one code.
+struct HmOut {   // the step: where the WRITE passes put contact j of collider i
     StepScalars* sc; uint32_t pairCap; uint64_t* pairsA; uint64_t* pairsB; uint64_t* npPacked; float4* npNormal; float4* npPoints;
+    typedef unsigned long long Packed;   // contacts | (touches the terrain) << 32
+    static __device__ __forceinline__ bool active(const float4& mn, const float4& mx, uint32_t& type) {
+        return hmActive(__float_as_uint(mn.w), type) && !(mx.x < mn.x);   // (inverted box: sharded world, a body this rank does not simulate this step)
+    }
+    static __device__ __forceinline__ Packed pack(uint32_t found) { return (unsigned long long)found | (found ? 1ull << 32 : 0ull); }
     __device__ bool ready() const { return !sc->specOverflow && sc->numPairs + sc->numHmContacts <= pairCap; }
+    __device__ __forceinline__ uint32_t first(const Packed* __restrict__ hmScan, uint32_t i) const { return sc->numPairs + (uint32_t)hmScan[i]; }
+    __device__ __forceinline__ uint32_t total(const Packed* __restrict__, uint32_t) const { return sc->numHmContacts; }
     // Contact j of the collider's `count` goes to pair record first + j (one record per contact: point, depth, ITS normal).  Four consecutive records are ONE manifold
     // (round 6): the record of contact 4 g is the manifold's head (flag 1, contacts min(4, count - 4 g), key (collider, virtual index base + g)), the other three carry
     // (flag 0, 0 contacts) and only lend their point and normal — k_contact_init reads contact k of a terrain manifold from record head + k.  A box resting on eight
@@ -279,23 +290,23 @@ struct HmOut {   // where the WRITE passes put contact j of collider i
 constexpr uint32_t kHmLowBit = 2u;          // hmSlow[i]: bit 0 = large window (set by the plain count pass), bit 1 = the lowest point is under the surface (k_hm_lowest, for the count passes)
 constexpr uint32_t kHmStashLowest = 0xFFFFFFFFu;
 constexpr uint32_t kHmStash = 16;
-template <bool WRITE, bool LARGE>
+template <bool WRITE, bool LARGE, class Out>
 __device__ __forceinline__ void hmCollider(const uint32_t i, const uint32_t lane, uint32_t nc, const HeightmapParams& hm, const float4* __restrict__ wShape, const float4* __restrict__ aabbMin,
-                                           const float4* __restrict__ aabbMax, unsigned long long* __restrict__ hmPacked, uint8_t* __restrict__ hmSlow,
-                                           const unsigned long long* __restrict__ hmScan, const HmOut& out, const HullSet& hulls, uint32_t* __restrict__ stash) {
+                                           const float4* __restrict__ aabbMax, typename Out::Packed* __restrict__ hmPacked, uint8_t* __restrict__ hmSlow,
+                                           const typename Out::Packed* __restrict__ hmScan, const Out& out, const HullSet& hulls, uint32_t* __restrict__ stash) {
     if (i >= nc) return;
     const float4 mn = aabbMin[i], mx = aabbMax[i];
     const bool low = !WRITE && (hmSlow[i] & kHmLowBit) != 0;                       // k_hm_lowest's answer for this collider (count passes)
     uint32_t type;
-    const bool active = hmActive(__float_as_uint(mn.w), type) && !(mx.x < mn.x);   // (inverted box: sharded world, a body this rank does not simulate this step)
+    const bool active = Out::active(mn, mx, type);
     uint32_t count = 0, first = 0;
     if (WRITE) {
         count = active ? (uint32_t)hmPacked[i] : 0u;
         if (!count || (hmSlow[i] != 0) != LARGE || !out.ready()) return;
-        first = out.sc->numPairs + (uint32_t)hmScan[i];
+        first = out.first(hmScan, i);
         if (!LARGE && count <= kHmStash && hm.chunksPerDim <= 256u) return;   // every hit of this collider is in the stash: k_hm_write_stashed recomputes just those
     } else if (LARGE) { if (!active || !hmSlow[i]) return; }                            // (the flags are the plain instance's, launched before this one)
-    else if (!active) { if (lane == 0) { hmPacked[i] = 0ull; hmSlow[i] = 0; } return; }
+    else if (!active) { if (lane == 0) { hmPacked[i] = 0; hmSlow[i] = 0; } return; }
     auto keep = [&](uint32_t j, uint32_t id) { if (!LARGE && j < kHmStash) stash[(size_t)i * kHmStash + j] = id; };
     const Shape s = loadShape(wShape, i, type);
     const TriShape ts(s);
@@ -386,20 +397,21 @@ __device__ __forceinline__ void hmCollider(const uint32_t i, const uint32_t lane
         if (found < count && hmLowestPoint(hm, s, hulls, t)) out.put(first, i, found, count, t);
         return;
     }
-    if (slow) { hmPacked[i] = 0ull; hmSlow[i] = (uint8_t)(1u | (low ? kHmLowBit : 0u)); return; }
+    if (slow) { hmPacked[i] = 0; hmSlow[i] = (uint8_t)(1u | (low ? kHmLowBit : 0u)); return; }
     if (low && found < kHmMaxContacts) { keep(found, kHmStashLowest); ++found; }
-    hmPacked[i] = (unsigned long long)found | (found ? 1ull << 32 : 0ull);
+    hmPacked[i] = Out::pack(found);
     if (!LARGE) hmSlow[i] = 0;
 }
 // The lowest-point test of every collider (heightmap_collision.cpp:572-580), one LANE per collider, ahead of the count passes: its support point and its two dependent round
 // trips (chunk slot, four heights) used to sit at the end of every wave of the count pass, on one lane.
+template <class Out>
 __global__ __launch_bounds__(256) void k_hm_lowest(uint32_t nc, HeightmapParams hm, const float4* __restrict__ wShape, const float4* __restrict__ aabbMin, const float4* __restrict__ aabbMax,
                                                    uint8_t* __restrict__ hmSlow, HullSet hulls) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nc) return;
     const float4 mn = aabbMin[i], mx = aabbMax[i];
     uint32_t type, r = 0;
-    if (hmActive(__float_as_uint(mn.w), type) && !(mx.x < mn.x)) {
+    if (Out::active(mn, mx, type)) {
         const Shape s = loadShape(wShape, i, type);
         TriContact t;
         if (hmLowestPoint(hm, s, hulls, t)) r = kHmLowBit;
@@ -407,12 +419,12 @@ __global__ __launch_bounds__(256) void k_hm_lowest(uint32_t nc, HeightmapParams 
     hmSlow[i] = (uint8_t)r;
 }
 constexpr uint32_t kHmScanBlocks = 512;   // the flag-scanning launches (LARGE or WRITE): at most this many workgroups, whatever the collider count
-template <bool WRITE, bool LARGE>
+template <bool WRITE, bool LARGE, class Out>
 __global__ __launch_bounds__(256) void k_hm_contacts(uint32_t nc, HeightmapParams hm, const float4* __restrict__ wShape, const float4* __restrict__ aabbMin,
-                                                     const float4* __restrict__ aabbMax, unsigned long long* __restrict__ hmPacked, uint8_t* __restrict__ hmSlow,
-                                                     const unsigned long long* __restrict__ hmScan, HmOut out, HullSet hulls, uint32_t* __restrict__ stash) {
+                                                     const float4* __restrict__ aabbMax, typename Out::Packed* __restrict__ hmPacked, uint8_t* __restrict__ hmSlow,
+                                                     const typename Out::Packed* __restrict__ hmScan, Out out, HullSet hulls, uint32_t* __restrict__ stash) {
     const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if (!WRITE && !LARGE) { hmCollider<false, false>(wave, lane, nc, hm, wShape, aabbMin, aabbMax, hmPacked, hmSlow, hmScan, out, hulls, stash); return; }
+    if (!WRITE && !LARGE) { hmCollider<false, false, Out>(wave, lane, nc, hm, wShape, aabbMin, aabbMax, hmPacked, hmSlow, hmScan, out, hulls, stash); return; }
     // Every other instance has work for a few colliders only (the flagged ones; in the WRITE passes those with more hits than the stash holds): a wave reads what decides
     // that for 64 colliders at a time and takes the ones that are its business one after the other.  (As launches of a wave per collider, all but a few of which left at once,
     // these cost the 65 536-body terrain scene 8-35 us each: three waves of 216-243 registers per SIMD, sixteen thousand workgroups.)
@@ -424,16 +436,17 @@ __global__ __launch_bounds__(256) void k_hm_contacts(uint32_t nc, HeightmapParam
             mine = count && (LARGE || !(count <= kHmStash && hm.chunksPerDim <= 256u));
         }
         for (unsigned long long m = __ballot(mine); m; m &= m - 1ull)
-            hmCollider<WRITE, LARGE>(base + (uint32_t)__ffsll((long long)m) - 1u, lane, nc, hm, wShape, aabbMin, aabbMax, hmPacked, hmSlow, hmScan, out, hulls, stash);
+            hmCollider<WRITE, LARGE, Out>(base + (uint32_t)__ffsll((long long)m) - 1u, lane, nc, hm, wShape, aabbMin, aabbMax, hmPacked, hmSlow, hmScan, out, hulls, stash);
     }
 }
 // WRITE pass for the stashed colliders: one LANE per terrain contact.  Contact t belongs to the collider i with offset(i) <= t < offset(i) + count(i) (binary search
 // over the scanned counts) and is its hit number j = t - offset(i): the lane recomputes that one triangle (or the lowest point) and writes the contact to its final slot.
+template <class Out>
 __global__ __launch_bounds__(256) void k_hm_write_stashed(uint32_t nc, HeightmapParams hm, const float4* __restrict__ wShape, const float4* __restrict__ aabbMin,
-                                                          const float4* __restrict__ aabbMax, const unsigned long long* __restrict__ hmPacked, const uint8_t* __restrict__ hmSlow,
-                                                          const unsigned long long* __restrict__ hmScan, HmOut out, HullSet hulls, const uint32_t* __restrict__ stash) {
+                                                          const float4* __restrict__ aabbMax, const typename Out::Packed* __restrict__ hmPacked, const uint8_t* __restrict__ hmSlow,
+                                                          const typename Out::Packed* __restrict__ hmScan, Out out, HullSet hulls, const uint32_t* __restrict__ stash) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= out.sc->numHmContacts || !out.ready() || hm.chunksPerDim > 256u) return;
+    if (t >= out.total(hmScan, nc) || !out.ready() || hm.chunksPerDim > 256u) return;
     uint32_t lo = 0, hi = nc;                       // the last collider whose offset is <= t (colliders without contacts share their successor's offset)
     while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((uint32_t)hmScan[mid] <= t) lo = mid; else hi = mid; }
     const uint32_t i = lo, count = (uint32_t)hmPacked[i], j = t - (uint32_t)hmScan[i];
@@ -453,7 +466,7 @@ __global__ __launch_bounds__(256) void k_hm_write_stashed(uint32_t nc, Heightmap
         const V3 pe = tri ? hmVertex(hm, heights, chunkMin, qx + 1u, qz + 1u) : hmVertex(hm, heights, chunkMin, qx, qz);
         ok = tri ? ts.test(pc, pb, pe, tc) : ts.test(pe, pb, pc, tc);
     }
-    if (ok) out.put(out.sc->numPairs + (uint32_t)hmScan[i], i, j, count, tc);
+    if (ok) out.put(out.first(hmScan, i), i, j, count, tc);
 }
 __global__ void k_hm_totals(uint32_t nc, const unsigned long long* __restrict__ hmPacked, const unsigned long long* __restrict__ hmScan, StepScalars* sc) {
     const unsigned long long t = nc ? hmScan[nc - 1u] + hmPacked[nc - 1u] : 0ull;

@@ -34,6 +34,7 @@
 #include "kernels_query.hpp"
 #include "kernels_overlap.hpp"
 #include "kernels_contacts_query.hpp"
+#include "kernels_terrain_query.hpp"
 
 using namespace mi;
 
@@ -141,6 +142,7 @@ static void hostParallelFor(uint32_t n, F&& fn) {
 namespace mi {
 template <> inline void sigMix<InterSink>(Launcher& L, const InterSink& v) { L.pod(v.keys); L.pod(v.cap); L.pod(v.count); }
 template <> inline void sigMix<HmOut>(Launcher& L, const HmOut& v) { L.pod(v.sc); L.pod(v.pairCap); L.pod(v.pairsA); L.pod(v.pairsB); L.pod(v.npPacked); L.pod(v.npNormal); L.pod(v.npPoints); }
+template <> inline void sigMix<HmQueryOut>(Launcher& L, const HmQueryOut& v) { L.pod(v.capacity); L.pod(v.records); }
 template <> inline void sigMix<HeightmapParams>(Launcher& L, const HeightmapParams& v) {
     L.pod(v.heights); L.pod(v.mips); L.pod(v.chunkSlot); L.pod(v.chunksPerDim); L.pod(v.chunkSize); L.pod(v.invChunkSize); L.pod(v.chunkScale); L.pod(v.heightScale);
     L.pod(v.invAmplitudeScale); L.pod(v.minX); L.pod(v.minY); L.pod(v.minZ); L.pod(v.restitution); L.pod(v.friction);
@@ -426,15 +428,15 @@ struct mi_world {
     uint64_t poseEpoch = 0;
     struct QueryCache {
         Launcher L;
-        // The grid structure (world rows of every collider, uniform grid, large list), shared by all three families.  Sized by the collider count; queryBuild()
+        // The grid structure (world rows of every collider, uniform grid, large list), shared by the ray, overlap and contact families.  Sized by the collider count; queryBuild()
         // alone grows and writes it, once per pose epoch.
         struct Built {
             uint64_t epoch = ~0ull; uint32_t nc = 0;
             DBuf<float4> shape, mn, mx; DBuf<QueryGrid> grid; DBuf<QPartial> partials; DBuf<uint32_t> count, start, entries, large;
             DeviceScan<uint32_t> scan;
         } built;
-        // The volume rows of the current overlap / contact call: world rows and counts, the volumes as static colliders (what worldCollider reads), the scan
-        // between the count and the write pass.  Sized by the call's volume count; overlapEnqueue() alone grows them.  candOffsets = the candidate offsets of a
+        // The volume rows of the current overlap / contact / terrain-contact call: world rows and counts, the volumes as static colliders (what worldCollider reads), the scan
+        // between the count and the write pass.  Sized by the call's volume count; volumeRowsEnqueue() alone grows them (the counts: overlapEnqueue()).  candOffsets = the candidate offsets of a
         // contact call (boxes-only overlap offsets), grown by the contact entry points before they enqueue.
         struct VolumeRows {
             DBuf<float4> shape, mn, mx; DBuf<uint32_t> range, count;
@@ -454,16 +456,24 @@ struct mi_world {
             hipEvent_t ev[4] = {};   // before k_vc_narrow / before k_vc_gjk / behind it / behind k_vc_write: recorded under mi_world_set_stage_timing only
             bool timed = false;      // the last call recorded them (mi_debug_volume_contacts_times)
         } cand;
+        // Terrain contact queries: the step's terrain pipeline over the volume rows (heightmap.hpp with HmQueryOut): the counts the scan turns into the caller's
+        // offsets, the large-window / lowest-point flags, the stash of the first kHmStash hits per volume.  Sized by the call's volume count; terrainEnqueue() alone grows them.
+        struct Terrain {
+            DBuf<uint32_t> counts, stash; DBuf<uint8_t> slow;
+            DeviceScan<uint32_t> scan;
+        } terrain;
         // Staging of the blocking variants: inputs copied in, results copied out.  Sized by the call's ray / volume count and record capacity; the blocking
         // entry points grow it.  One set serves every family: a blocking call synchronises before it returns, so two never use it at once.
         struct Blocking {
             DBuf<float> rays; DBuf<uint32_t> hits;   // ray casts
             DBuf<uint32_t> ranges;                   // the optional entity ranges of any family
-            DBuf<uint32_t> volumes, offsets, totals; DBuf<uint4> records;   // volume queries: mi_overlap_hit is one row of 16 bytes, mi_volume_contact six
+            DBuf<uint32_t> volumes, offsets, totals; DBuf<uint4> records;   // volume queries: mi_overlap_hit is one row of 16 bytes, mi_terrain_contact two, mi_volume_contact six
         } host;
     } query;
     int queryBuild();
     OverlapScene overlapScene(bool exhaustive) const;
+    int volumeRowsEnqueue(uint32_t count, const uint32_t* volumesDev, const uint32_t* rangesDev);
+    int terrainEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t* offsetsDev, float4* recordsDev, uint32_t capacity, uint32_t* totalDev);
     int overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t include, const uint32_t* rangesDev, uint32_t* offsetsDev, uint4* hitsDev, uint32_t capacity,
                        uint32_t* totalDev, bool exhaustive, uint32_t passes, bool boxesOnly);
     int contactsReserve(uint32_t maxCandidates);

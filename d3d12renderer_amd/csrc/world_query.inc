@@ -1,6 +1,7 @@
 // Part of world.hip (one translation unit; #included there, after world_state.inc): batched scene queries (include/mi_physics.h): ray casts
 // (mi_world_raycast*; kernels in kernels_query.hpp), volume overlaps (mi_world_overlap*; kernels in kernels_overlap.hpp) and the contact manifolds of
-// query volumes (mi_world_volume_contacts*; kernels in kernels_contacts_query.hpp).
+// query volumes (mi_world_volume_contacts*; kernels in kernels_contacts_query.hpp) and their terrain contacts (mi_world_terrain_contacts*; the step's terrain
+// kernels of heightmap.hpp under the policy of kernels_terrain_query.hpp).
 //
 // The query structure (world AABBs, uniform grid, large list) is built lazily on the world's stream and cached per pose epoch: every
 // internal step, upload (any topology or heightmap edit), body-state write, checkpoint load and shard import bumps mi_world::poseEpoch,
@@ -121,6 +122,19 @@ OverlapScene mi_world::overlapScene(bool exhaustive) const {
     else { s.shape = query.built.shape.p; s.mn = query.built.mn.p; s.mx = query.built.mx.p; }
     return s;
 }
+// The volumes of a call as collider rows (two launches on the begun launcher): what every volume family tests with.
+int mi_world::volumeRowsEnqueue(uint32_t count, const uint32_t* volumesDev, const uint32_t* rangesDev) {
+    QueryCache::VolumeRows& v = query.vol;
+    HIP_TRY(v.shape.ensure(3 * (size_t)count)); HIP_TRY(v.mn.ensure(count)); HIP_TRY(v.mx.ensure(count)); HIP_TRY(v.range.ensure(2 * (size_t)count));
+    HIP_TRY(v.cTypeBody.ensure(2 * (size_t)count)); HIP_TRY(v.cObject.ensure(count)); HIP_TRY(v.cShape.ensure(3 * (size_t)count)); HIP_TRY(v.cPos.ensure(count)); HIP_TRY(v.cRot.ensure(count));
+    Launcher& L = query.L;
+    L.launch(k_ov_unpack, dim3(divUp(count, 256)), dim3(256), 0, stream, count, volumesDev, rangesDev, (uint32_t)hulls.size(), v.cTypeBody.p, v.cObject.p, v.cShape.p,
+             v.cPos.p, v.cRot.p, v.range.p);
+    ColliderRows volumes = colliderRows(nullptr, nullptr /* (no bodies) */, v.shape.p, v.mn.p, v.mx.p);   // the volumes as static colliders; the world's hulls
+    volumes.cTypeBody = v.cTypeBody.p; volumes.cObject = v.cObject.p; volumes.cShape = v.cShape.p; volumes.cStaticPos = v.cPos.p; volumes.cStaticRot = v.cRot.p; volumes.nb = 0u;
+    L.launch(k_ov_prepare, dim3(divUp(count, 256)), dim3(256), 0, stream, count, volumes);
+    return MI_OK;
+}
 // passes: kOvPassCount = volume rows, count pass and scan; kOvPassWrite = the write pass over what a count pass of the same arguments left (nothing else
 // enqueued in between).  boxesOnly: ovTest without overlapCheck — the candidates of the contact query.
 int mi_world::overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t include, const uint32_t* rangesDev, uint32_t* offsetsDev, uint4* hitsDev,
@@ -129,9 +143,7 @@ int mi_world::overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_
     const uint32_t nc = (uint32_t)colliders.size();
     const bool first = (passes & kOvPassCount) != 0u;
     if (!exhaustive && first) { int rc = queryBuild(); if (rc != MI_OK) return rc; }
-    HIP_TRY(v.shape.ensure(3 * (size_t)count)); HIP_TRY(v.mn.ensure(count)); HIP_TRY(v.mx.ensure(count));
-    HIP_TRY(v.range.ensure(2 * (size_t)count)); HIP_TRY(v.count.ensure((size_t)count + 1));
-    HIP_TRY(v.cTypeBody.ensure(2 * (size_t)count)); HIP_TRY(v.cObject.ensure(count)); HIP_TRY(v.cShape.ensure(3 * (size_t)count)); HIP_TRY(v.cPos.ensure(count)); HIP_TRY(v.cRot.ensure(count));
+    HIP_TRY(v.count.ensure((size_t)count + 1));
     Launcher& L = query.L;
     L.begin(false, false);
     if (exhaustive) {   // its own world rows at the current poses: the yardstick does not trust the cache
@@ -141,13 +153,7 @@ int mi_world::overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_
     }
     const OverlapScene s = overlapScene(exhaustive);
     const dim3 grid(divUp(count, kOvWaves)), block(64 * kOvWaves);
-    if (first) {
-        L.launch(k_ov_unpack, dim3(divUp(count, 256)), dim3(256), 0, stream, count, volumesDev, rangesDev, (uint32_t)hulls.size(), v.cTypeBody.p, v.cObject.p, v.cShape.p,
-                 v.cPos.p, v.cRot.p, v.range.p);
-        ColliderRows volumes = colliderRows(nullptr, nullptr /* (no bodies) */, v.shape.p, v.mn.p, v.mx.p);   // the volumes as static colliders; the world's hulls
-        volumes.cTypeBody = v.cTypeBody.p; volumes.cObject = v.cObject.p; volumes.cShape = v.cShape.p; volumes.cStaticPos = v.cPos.p; volumes.cStaticRot = v.cRot.p; volumes.nb = 0u;
-        L.launch(k_ov_prepare, dim3(divUp(count, 256)), dim3(256), 0, stream, count, volumes);
-    }
+    if (first) { int rc = volumeRowsEnqueue(count, volumesDev, rangesDev); if (rc != MI_OK) return rc; }
     for (uint32_t pass = 0; pass < 2u; ++pass) {
         if (!(passes & (pass ? kOvPassWrite : kOvPassCount))) continue;
         if (exhaustive)
@@ -200,7 +206,43 @@ int mi_world::contactsEnqueue(uint32_t count, uint32_t bound, uint32_t capacity,
     return MI_OK;
 }
 
-// ---- the blocking volume queries (mi_world_overlap, mi_world_volume_contacts and their exhaustive yardsticks): one protocol.  Argument check, prepare,
+// ---- terrain contacts of query volumes.  The step's terrain pipeline (heightmap.hpp) with the volume rows as its colliders and HmQueryOut as its policy: volume
+// rows (two launches), lowest-point pass, count pass and its large-window instance, the scan of the counts into the caller's offsets, the total, then the three write
+// passes straight into the caller's records — no read-back between them.  capacity 0: no write passes.  A world without a heightmap: all-zero offsets.
+int mi_world::terrainEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t* offsetsDev, float4* recordsDev, uint32_t capacity, uint32_t* totalDev) {
+    QueryCache::Terrain& t = query.terrain; const QueryCache::VolumeRows& v = query.vol;
+    Launcher& L = query.L;
+    L.begin(false, false);
+    if (!heightmap) {
+        HIP_TRY(L.memsetAsync(offsetsDev, 0, ((size_t)count + 1) * sizeof(uint32_t), stream));
+        if (totalDev) HIP_TRY(L.memsetAsync(totalDev, 0, sizeof(uint32_t), stream));
+        return MI_OK;
+    }
+    HIP_TRY(t.counts.ensure((size_t)count + 1)); HIP_TRY(t.slow.ensure(count)); HIP_TRY(t.stash.ensure((size_t)count * kHmStash));
+    int rc = volumeRowsEnqueue(count, volumesDev, nullptr); if (rc != MI_OK) return rc;
+    const HullSet hs{hullVerts.p, hullRanges.p};
+    const HmQueryOut out{capacity, recordsDev};
+    const dim3 B(256), perWave(divUp(count, 4)), scanning(std::min(divUp(count, 256), kHmScanBlocks));
+    const float4 *shape = v.shape.p, *mn = v.mn.p, *mx = v.mx.p;
+    L.launch(k_hm_lowest<HmQueryOut>, dim3(divUp(count, 256)), B, 0, stream, count, hmParams, shape, mn, mx, t.slow.p, hs);
+    L.launch(k_hm_contacts<false, false, HmQueryOut>, perWave, B, 0, stream, count, hmParams, shape, mn, mx, t.counts.p, t.slow.p, nullptr, out, hs, t.stash.p);
+    L.launch(k_hm_contacts<false, true, HmQueryOut>, scanning, B, 0, stream, count, hmParams, shape, mn, mx, t.counts.p, t.slow.p, nullptr, out, hs, t.stash.p);
+    HIP_TRY(L.memsetAsync(t.counts.p + count, 0, sizeof(uint32_t), stream));   // (the scan's last input: offsets[count] = the total)
+    HIP_TRY(t.scan.run(L, t.counts.p, offsetsDev, count + 1u, stream, false));
+    if (totalDev) L.launch(k_tq_total, dim3(1), dim3(1), 0, stream, count, (const uint32_t*)offsetsDev, totalDev);
+    if (capacity) {
+        const uint32_t* offsets = offsetsDev;
+        L.launch(k_hm_contacts<true, false, HmQueryOut>, scanning, B, 0, stream, count, hmParams, shape, mn, mx, t.counts.p, t.slow.p, offsets, out, hs, t.stash.p);
+        L.launch(k_hm_contacts<true, true, HmQueryOut>, scanning, B, 0, stream, count, hmParams, shape, mn, mx, t.counts.p, t.slow.p, offsets, out, hs, t.stash.p);
+        const uint32_t lanes = (uint32_t)std::min<uint64_t>(capacity, (uint64_t)kHmMaxContacts * count);   // one lane per contact that has a record
+        L.launch(k_hm_write_stashed<HmQueryOut>, dim3(divUp(lanes, 256)), B, 0, stream, count, hmParams, shape, mn, mx, (const uint32_t*)t.counts.p, (const uint8_t*)t.slow.p, offsets, out, hs,
+                 (const uint32_t*)t.stash.p);
+    }
+    if (L.firstError != hipSuccess) return fail(MI_ERR_DEVICE, std::string("terrain contact query: ") + hipGetErrorString(L.firstError));
+    return MI_OK;
+}
+
+// ---- the blocking volume queries (mi_world_overlap, mi_world_volume_contacts, mi_world_terrain_contacts and the exhaustive yardsticks): one protocol.  Argument check, prepare,
 // zeroed outputs, volumes and ranges staged, the family's own work, then offsets, total and min(total, capacity) records read back.  What a family brings:
 // the bytes of its record, the noun of the capacity error, and the step that enqueues its work on the staged inputs and leaves count + 1 offsets and up to
 // `capacity` records in the blocking staging it is handed.
@@ -223,9 +265,13 @@ static int contactsStep(mi_world* w, uint32_t count, const uint32_t* volumesDev,
     if (candidates) { rc = w->overlapEnqueue(count, volumesDev, include, rangesDev, qc.vol.candOffsets.p, qc.cand.pairs.p, candidates, nullptr, exhaustive, kOvPassWrite, true); if (rc != MI_OK) return rc; }
     return w->contactsEnqueue(count, candidates, capacity, recordsDev, offsetsDev, qc.host.totals.p, exhaustive);
 }
+static int terrainStep(mi_world* w, uint32_t count, const uint32_t* volumesDev, uint32_t, const uint32_t*, uint32_t* offsetsDev, uint4* recordsDev, uint32_t capacity, bool) {
+    return w->terrainEnqueue(count, volumesDev, offsetsDev, reinterpret_cast<float4*>(recordsDev), capacity, nullptr);
+}
 static const VolumeFamily kOverlapFamily{sizeof(mi_overlap_hit), "overlap", overlapStep};
 static const VolumeFamily kContactFamily{sizeof(mi_volume_contact), "contact", contactsStep};
-static_assert(sizeof(mi_overlap_hit) == sizeof(uint4) && sizeof(mi_volume_contact) == kVcSlotRows * sizeof(uint4), "the blocking staging holds records as rows of 16 bytes");
+static const VolumeFamily kTerrainFamily{sizeof(mi_terrain_contact), "terrain contact", terrainStep};
+static_assert(sizeof(mi_overlap_hit) == sizeof(uint4) && sizeof(mi_volume_contact) == kVcSlotRows * sizeof(uint4) && sizeof(mi_terrain_contact) == kTqRecordRows * sizeof(uint4), "the blocking staging holds records as rows of 16 bytes");
 
 static int volumeQueryHost(mi_world* w, const VolumeFamily& family, uint32_t count, const mi_query_volume* volumes, uint32_t include, const uint32_t* ranges, uint32_t* outOffsets,
                            void* outRecords, uint32_t capacity, uint32_t* outTotal, bool exhaustive) {
@@ -320,6 +366,19 @@ MI_API int mi_world_volume_contacts_device_async(mi_world* w, uint32_t count, co
     rc = w->overlapEnqueue(count, reinterpret_cast<const uint32_t*>(volumesDev), include, ranges2Dev, qc.vol.candOffsets.p, qc.cand.pairs.p, qc.cand.cap, nullptr, false, kOvPassCount | kOvPassWrite, true);
     if (rc != MI_OK) return rc;
     return w->contactsEnqueue(count, qc.cand.cap, capacity, reinterpret_cast<uint4*>(contactsDev), offsetsDev, totals2Dev, false);
+}
+
+
+MI_API int mi_world_terrain_contacts(mi_world* w, uint32_t count, const mi_query_volume* volumes, uint32_t* outOffsets, mi_terrain_contact* outContacts, uint32_t capacity,
+                                     uint32_t* outTotal) {
+    return volumeQueryHost(w, kTerrainFamily, count, volumes, 0u, nullptr, outOffsets, outContacts, capacity, outTotal, false);
+}
+MI_API int mi_world_terrain_contacts_device_async(mi_world* w, uint32_t count, const mi_query_volume* volumesDev, uint32_t* offsetsDev, mi_terrain_contact* contactsDev,
+                                                  uint32_t capacity, uint32_t* totalDev) {
+    if (!w || (count && (!volumesDev || !offsetsDev || !totalDev || (capacity && !contactsDev)))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = queryPrepare(w); if (rc != MI_OK) return rc;
+    if (!count) return MI_OK;
+    return w->terrainEnqueue(count, reinterpret_cast<const uint32_t*>(volumesDev), offsetsDev, reinterpret_cast<float4*>(contactsDev), capacity, totalDev);
 }
 
 }  // extern "C"

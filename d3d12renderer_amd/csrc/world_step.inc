@@ -447,9 +447,9 @@ int mi_world::stagePrepare(StepAttempt& a) {
         L.launch(k_world_colliders, dim3(divUp(nc, B)), dim3(B), 0, st, nc, colliderRows(bPos.p, bRot.p, wShape.p, aabbMin.p, aabbMax.p), sc, sapAxis, shard.enabled ? shard.axisDev.p : nullptr);
     if (heightmap) {   // terrain contacts per collider, their offsets and totals (they join the pair list after the collider-pair narrow phase)
         const HullSet hmHulls{hullVerts.p, hullRanges.p};
-        L.launch(k_hm_lowest, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmSlow.p, hmHulls);
-        L.launch(k_hm_contacts<false, false>, dim3(divUp(nc, 4)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, nullptr, HmOut{}, hmHulls, hmStash.p);
-        L.launch(k_hm_contacts<false, true>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, nullptr, HmOut{}, hmHulls, hmStash.p);   // (the colliders the first pass flagged: a cell window beyond 64 cells)
+        L.launch(k_hm_lowest<HmOut>, dim3(divUp(nc, 256)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmSlow.p, hmHulls);
+        L.launch(k_hm_contacts<false, false, HmOut>, dim3(divUp(nc, 4)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, nullptr, HmOut{}, hmHulls, hmStash.p);
+        L.launch(k_hm_contacts<false, true, HmOut>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, nullptr, HmOut{}, hmHulls, hmStash.p);   // (the colliders the first pass flagged: a cell window beyond 64 cells)
         HIP_TRY(scanTerrain.run(L, hmPacked.p, hmScan.p, nc, st));
         L.launch(k_hm_totals, dim3(1), dim3(1), 0, st, nc, hmPacked.p, hmScan.p, sc);
     }
@@ -581,9 +581,9 @@ int mi_world::stageNarrow(StepAttempt& a) {
     }
     if (heightmap) {
         const HmOut hmOut{sc, pairBound, pairKeys.p, pairKeysS.p, npPacked.p, npNormal.p, npPoints.p};
-        L.launch(k_hm_contacts<true, false>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
-        L.launch(k_hm_contacts<true, true>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
-        L.launch(k_hm_write_stashed, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);   // (sized for all pairs: the terrain contacts are among them)
+        L.launch(k_hm_contacts<true, false, HmOut>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
+        L.launch(k_hm_contacts<true, true, HmOut>, dim3(std::min(divUp(nc, 256), kHmScanBlocks)), dim3(256), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);
+        L.launch(k_hm_write_stashed<HmOut>, dim3(divUp(pairBound, B)), dim3(B), 0, st, nc, hmParams, wShape.p, aabbMin.p, aabbMax.p, hmPacked.p, hmSlow.p, hmScan.p, hmOut, hset, hmStash.p);   // (sized for all pairs: the terrain contacts are among them)
         L.launch(k_hm_finish, dim3(1), dim3(1), 0, st, sc, pairBound);
     }
     HIP_TRY(scanPairs.run(L, reinterpret_cast<unsigned long long*>(npPacked.p), reinterpret_cast<unsigned long long*>(npScan.p), pairBound, st));

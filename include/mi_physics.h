@@ -309,8 +309,9 @@ MI_API int mi_debug_raycast_exhaustive(mi_world* world, uint32_t count, const fl
  *     passes them; for equal types A is the volume.  This is the test a trigger of that shape runs, reference quirks included (its
  *     sphere-vs-cylinder cap test compares a squared distance with a radius; the hull and segment-vs-box pairs are GJK with its error
  *     paths reading as "no overlap").
- *   - Not reported: the terrain (the reference has no boolean test against the heightmap; MI_QUERY_TERRAIN is accepted and ignored)
- *     and cloth.  A sharded world returns MI_ERR_UNSUPPORTED.
+ *   - Not reported: the terrain (the reference has no boolean test against the heightmap; MI_QUERY_TERRAIN is accepted and ignored;
+ *     mi_world_terrain_contacts below reports where a volume touches the terrain, and its count-only call whether it does) and cloth.
+ *     A sharded world returns MI_ERR_UNSUPPORTED.
  *   - An invalid volume (a non-finite number among the words its type reads or in its pose, a type out of range, an unknown hull
  *     geometry, a negative radius or half-extent, an AABB with max < min, a world AABB that overflows) reports nothing: an empty
  *     segment, never an error.
@@ -354,7 +355,8 @@ MI_API int mi_debug_overlap_exhaustive(mi_world* world, uint32_t count, const mi
  *   - The normal is a unit vector pointing from A to B, as the reference's (sphereSphere: normalize(centre B - centre A)); points[i] =
  *     (world contact point, penetration depth >= 0).  To separate the volume from the collider move the VOLUME along -normal when it
  *     was A (bit 8 clear) and along +normal when it was B (bit 8 set), by the largest depth of the record.
- *   - Not reported: the terrain (MI_QUERY_TERRAIN is accepted and ignored, as by mi_world_overlap) and cloth.
+ *   - Not reported: the terrain (MI_QUERY_TERRAIN is accepted and ignored, as by mi_world_overlap; a volume's terrain contacts come from
+ *     mi_world_terrain_contacts below) and cloth.
  */
 typedef struct mi_volume_contact {   /* 96 bytes, 16-byte aligned rows: usable from the host and as a device buffer */
     uint32_t entity, collider, object_type, volume;   /* as mi_overlap_hit */
@@ -383,6 +385,44 @@ MI_API int mi_debug_volume_contacts_times(mi_world* world, float* out_ms3);
 MI_API int mi_debug_volume_contacts_exhaustive(mi_world* world, uint32_t count, const mi_query_volume* volumes, uint32_t include,
                                                const uint32_t* entity_ranges2, uint32_t* out_offsets, mi_volume_contact* out_contacts,
                                                uint32_t capacity, uint32_t* out_total);
+
+/*
+ * Batched terrain contact queries: where a shape touches the heightmap terrain (the ground under a character's capsule, a foot probe,
+ * a spawn test).  The volumes, their validation (an invalid one yields an empty segment) and their pose handling (an AABB under a
+ * rotation that is not exactly (0,0,0,1) is an OBB) are those of mi_world_overlap; like every query it reads the current scene
+ * (pending host edits, heightmap edits included, are uploaded first) and changes nothing a step computes.  A sharded world returns
+ * MI_ERR_UNSUPPORTED.  There are no include flags and no entity ranges: the terrain is one object.
+ *   - Volume v reports exactly the contacts a rigid body of that shape at that pose would get from the terrain in one step
+ *     (the reference's heightmapCollision), with the same bits in point, depth and normal, in the reference's emission order: the
+ *     triangle contacts in the order of its walk down the min/max quadtree (a stack: descending Morton code of the cell with x as the
+ *     high bit, a cell's first triangle before its second; chunk rows z ascending, x ascending within a row), then the lowest-point
+ *     contact.  At most 255 contacts per volume (the reference's limit); what would follow is dropped.
+ *   - Per shape: spheres, capsules, AABBs and OBBs test the triangles of their cell window and add the lowest-point contact; cylinders
+ *     and hulls get the lowest-point contact only, as in the step.  The lowest-point contact: the volume's support point along
+ *     (0,-1,0) lies under the bilinear surface; point = that support point, depth = surface height - point.y, normal = (0,-1,0).
+ *   - The normal is a unit vector from the volume towards the terrain: move the volume along -normal by depth to separate it.
+ *   - Holes and map edges: a chunk without heights is a hole and reports nothing; a world without a heightmap reports nothing (all
+ *     offsets 0) and returns MI_OK.  The cell window of a volume, the extension of its world AABB by 10 upwards before the window and
+ *     the height range are taken, and the clamping of the window at the map's edge are the step's own (one code runs both).
+ *   - Result (CSR): out_offsets[count + 1], and the records of volume v at [out_offsets[v], out_offsets[v + 1]) in emission order.
+ *     The order is part of the contract.
+ *   - Capacity: exactly the protocol of mi_world_overlap.  out_total always receives the full number of records and out_offsets the
+ *     full offsets; the first `capacity` records in result order are written (a cut may fall inside a volume's segment), nothing at
+ *     or past out_contacts[capacity]; a truncated result returns MI_ERR_CAPACITY; out_contacts NULL with capacity 0 is the count-only
+ *     call and returns MI_OK.
+ */
+typedef struct mi_terrain_contact {   /* 32 bytes, 16-byte aligned rows: usable from the host and as a device buffer */
+    float point[3]; float depth;      /* world contact point, penetration depth */
+    float normal[3]; uint32_t volume; /* unit, from the volume towards the terrain (lowest-point contact: (0,-1,0)); index of the volume */
+} mi_terrain_contact;
+MI_API int mi_world_terrain_contacts(mi_world* world, uint32_t count, const mi_query_volume* volumes, uint32_t* out_offsets,
+                                     mi_terrain_contact* out_contacts, uint32_t capacity, uint32_t* out_total);
+/* Device buffers (16-byte aligned), only enqueued on the world's stream: no host synchronisation, and no reservation (the staging
+ * per volume is sized from count by the call).  total_dev[0] receives the full count, offsets_dev the full offsets, and nothing is
+ * written at or past contacts_dev[capacity]; contacts_dev may be NULL when capacity is 0. */
+MI_API int mi_world_terrain_contacts_device_async(mi_world* world, uint32_t count, const mi_query_volume* volumes_dev,
+                                                  uint32_t* offsets_dev, mi_terrain_contact* contacts_dev, uint32_t capacity,
+                                                  uint32_t* total_dev);
 
 /* physicsStep(scene, arena, timer, settings, dt) (src/physics/physics.cpp:1364-1413). */
 MI_API int mi_world_step(mi_world* world, const mi_step_settings* settings, float dt);

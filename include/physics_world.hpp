@@ -159,6 +159,19 @@ public:
         countThenFetch(mi_world_volume_contacts, "mi_world_volume_contacts", "volumeContacts", volumes, include, entityRanges, r.offsets, r.contacts);
         return r;
     }
+    // Where each volume touches the heightmap terrain (mi_world_terrain_contacts): CSR offsets [volumes + 1] and one record per contact in the reference's
+    // emission order — what a rigid body of that shape at that pose would get from the terrain in one step; normal from the volume towards the terrain; read-only.
+    struct terrain_contacts_result { std::vector<uint32_t> offsets; std::vector<mi_terrain_contact> contacts; };
+    terrain_contacts_result terrainContacts(const std::vector<mi_query_volume>& volumes) {
+        terrain_contacts_result r;
+        r.offsets.assign(volumes.size() + 1, 0u);
+        if (volumes.empty()) return r;
+        uint32_t total = 0;   // count first, then fetch, as the other volume queries
+        check(mi_world_terrain_contacts(w_, (uint32_t)volumes.size(), volumes.data(), r.offsets.data(), nullptr, 0, &total), "mi_world_terrain_contacts");
+        r.contacts.resize(total);
+        if (total) check(mi_world_terrain_contacts(w_, (uint32_t)volumes.size(), volumes.data(), r.offsets.data(), r.contacts.data(), total, &total), "mi_world_terrain_contacts");
+        return r;
+    }
     std::vector<mi_overlap_hit> overlapSphere(vec3 center, float radius, uint32_t include = MI_QUERY_DEFAULT) {
         mi_query_volume v{}; v.type = MI_COLLIDER_SPHERE; v.rotation[3] = 1.f;
         v.shape[0] = center.x; v.shape[1] = center.y; v.shape[2] = center.z; v.shape[3] = radius;
