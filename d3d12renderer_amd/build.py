@@ -31,22 +31,33 @@ def needs_build():
 
 
 LEARNING_LIB = HERE / "libPhysics-Lib.so"      # the reference's learning DLL ("Physics-Lib.dll") over libmi_physics.so
-LEARNING_SRC = CSRC / "learning.cpp"
+LEARNING_SRC = CSRC / "learning.cpp"            # the host path and the C ABI: g++, HOST_FLAGS
+LEARNING_DEVICE_SRC = CSRC / "learning_device.hip"   # the device-resident step and its kernels: hipcc, the physics library's FLAGS
+LEARNING_HEADERS = [CSRC / "learning_shared.hpp", CSRC / "learning_device.hpp"] + [HERE.parent / "include" / n for n in ("mi_learning.h", "mi_physics.h", "mi_constraints.h")]
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-ffp-contract=off", "-fno-fast-math", "-fopenmp"]
+OBJ_DIR = HERE / "build"
 
 
-def build_learning(force=False, verbose=False):
-    """libPhysics-Lib.so: host-only C++ (g++) linked against libmi_physics.so next to it ($ORIGIN rpath)."""
-    deps = [LEARNING_SRC, LIB] + HEADERS[-2:]
-    if not force and LEARNING_LIB.exists() and all(p.stat().st_mtime <= LEARNING_LIB.stat().st_mtime for p in deps):
-        return LEARNING_LIB
-    cmd = [os.environ.get("CXX", "g++"), *HOST_FLAGS, str(LEARNING_SRC), "-o", str(LEARNING_LIB), "-L", str(HERE), "-l:libmi_physics.so", "-Wl,-rpath,$ORIGIN"]
+def _run(cmd, verbose, what):
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
-        raise RuntimeError("g++ failed (learning library)")
+        raise RuntimeError(f"{what} failed (learning library)")
+
+
+def build_learning(force=False, verbose=False):
+    """libPhysics-Lib.so: learning.cpp (g++, host flags: the host path's bits depend on them) + learning_device.hip (hipcc, the physics
+    library's flags), linked once against libmi_physics.so next to it ($ORIGIN rpath) and OpenMP's runtime."""
+    deps = [LEARNING_SRC, LEARNING_DEVICE_SRC, LIB] + LEARNING_HEADERS
+    if not force and LEARNING_LIB.exists() and all(p.stat().st_mtime <= LEARNING_LIB.stat().st_mtime for p in deps):
+        return LEARNING_LIB
+    OBJ_DIR.mkdir(exist_ok=True)
+    host_o, dev_o = OBJ_DIR / "learning.o", OBJ_DIR / "learning_device.o"
+    _run([os.environ.get("CXX", "g++"), *[f for f in HOST_FLAGS if f != "-shared"], "-c", str(LEARNING_SRC), "-o", str(host_o)], verbose, "g++")
+    _run([hipcc(), *[f for f in FLAGS if f != "-shared"], "-I", str(HERE.parent / "include"), "-c", str(LEARNING_DEVICE_SRC), "-o", str(dev_o)], verbose, "hipcc")
+    _run([hipcc(), "-shared", "-fPIC", str(host_o), str(dev_o), "-o", str(LEARNING_LIB), "-L", str(HERE), "-l:libmi_physics.so", "-Wl,-rpath,$ORIGIN", "-lgomp"], verbose, "link")
     return LEARNING_LIB
 
 

@@ -873,6 +873,35 @@ class World:
         self.L.check(self.L.fn("world_set_body_states_device_async")(self.h, C.c_uint32(n), C.c_void_p(body_ids_ptr), C.c_void_p(in_ptr)),
                      "world_set_body_states_device_async")
 
+    # --- device-side access for a controller on the same GPU: device pointers (e.g. torch tensors' data_ptr()), enqueued on the world's stream
+    def get_transforms_device_async(self, positions_ptr=0, rotations_ptr=0, linear_ptr=0, angular_ptr=0, physics=False):
+        """mi_world_get_transforms_device_async: the rows of transforms() (physics=True: physics_transforms()) and velocities() in entity order
+        ([n][3], [n][4], [n][3], [n][3] float32; any pointer may be 0).  Rows of entities without a rigid body are not written."""
+        self.L.check(self.L.fn("world_get_transforms_device_async")(self.h, C.c_uint32(1 if physics else 0), C.c_void_p(positions_ptr or None), C.c_void_p(rotations_ptr or None),
+                                                                     C.c_void_p(linear_ptr or None), C.c_void_p(angular_ptr or None)), "world_get_transforms_device_async")
+
+    def constraints_to_device_indices(self, ctype, ids):
+        """mi_constraints_to_device_indices: positions of the constraints in the type's device POD array (valid until one of that type is created or destroyed)."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        out = np.zeros(len(ids), np.uint32)
+        self.L.check(self.L.fn("constraints_to_device_indices")(self.h, C.c_uint32(ctype), C.c_uint32(len(ids)), _ptr(ids), _ptr(out)), "constraints_to_device_indices")
+        return out
+
+    def update_constraints_device_async(self, ctype, n, indices_ptr, pods_ptr):
+        """mi_constraints_update_device_async: n whole PODs (CONSTRAINT_DTYPES[ctype], packed) from device memory to the positions indices_ptr names."""
+        self.L.check(self.L.fn("constraints_update_device_async")(self.h, C.c_uint32(ctype), C.c_uint32(n), C.c_void_p(indices_ptr), C.c_void_p(pods_ptr),
+                                                                   C.c_uint32(CONSTRAINT_DTYPES[ctype].itemsize)), "constraints_update_device_async")
+
+    def test_interactions_device_async(self, n, rays_ptr, ranges_ptr=0):
+        """mi_world_test_interactions_device_async: rays n x 8 float32 (origin, direction, strength, pad), ranges n x 2 uint32 or 0 = the whole scene;
+        a ray with an empty range hits nothing."""
+        self.L.check(self.L.fn("world_test_interactions_device_async")(self.h, C.c_uint32(n), C.c_void_p(rays_ptr), C.c_void_p(ranges_ptr or None)), "world_test_interactions_device_async")
+
+    def set_body_states_masked_device_async(self, n, body_ids_ptr, in_ptr, mask_ptr, group):
+        """mi_world_set_body_states_masked_device_async: row i is written iff mask[i // group] != 0 (uint32 flags)."""
+        self.L.check(self.L.fn("world_set_body_states_masked_device_async")(self.h, C.c_uint32(n), C.c_void_p(body_ids_ptr), C.c_void_p(in_ptr), C.c_void_p(mask_ptr), C.c_uint32(group)),
+                     "world_set_body_states_masked_device_async")
+
     def stream_ptr(self):
         """The world's hipStream_t as an integer (for torch.cuda.ExternalStream)."""
         out = C.c_void_p()

@@ -444,7 +444,8 @@ __global__ __launch_bounds__(256) void k_ray_interactions(uint32_t nc, const flo
     const uint32_t r = blockIdx.x;
     const V3 ro(rays[8 * r], rays[8 * r + 1], rays[8 * r + 2]), rd(rays[8 * r + 3], rays[8 * r + 4], rays[8 * r + 5]);
     const float strength = rays[8 * r + 6];
-    const uint32_t lo = ranges[2 * r], hi = ranges[2 * r + 1];
+    const uint32_t lo = ranges ? ranges[2 * r] : 0u, hi = ranges ? ranges[2 * r + 1] : 0xFFFFFFFFu;   // (null: the whole scene)
+    if (lo >= hi) { if (threadIdx.x == 0) outBody[r] = 0xFFFFFFFFu; return; }   // an empty range hits nothing: the whole workgroup leaves before the scan (a caller with one slot per environment and few live rays)
     unsigned long long mine = ~0ull;   // (t bits << 32 | collider): t >= 0, so the bit pattern orders like the value
     for (uint32_t k = threadIdx.x; k < nc; k += blockDim.x) {
         const uint32_t body = cTypeBody[2 * k + 1], ent = cEntity[k];

@@ -1019,6 +1019,7 @@ struct JointType {
         return hipSuccess;
     }
     bool podsDirty = false;   // mi_constraint_update since the last upload: only the POD array changed (motors, limits), not the topology
+    bool deviceNewer = false; // mi_constraints_update_device_async since the last pull: dPods holds PODs the host mirror has not seen (JointSet::pullDeviceWrites)
     hipError_t uploadPods(hipStream_t st) {
         podsDirty = false;
         if (pods.empty() || !dPods) return hipSuccess;
@@ -1071,6 +1072,10 @@ struct JointSet {
     }
     bool podsDirty() const { return distance.podsDirty || ball.podsDirty || fixed.podsDirty || hinge.podsDirty || cone.podsDirty || slider.podsDirty; }
     int uploadPods(hipStream_t st);
+    // mi_constraints_update_device_async writes PODs on the device only.  The ONE invariant that comes with it: before the host mirror (`pods`) of a type
+    // is read (get, checkpoint), written (update, create, destroy) or re-sent (upload), the device array is pulled back — pullDeviceWrites, called there.
+    hipStream_t mirrorStream = nullptr; int mirrorDevice = 0;   // the world's stream / device, as of the last upload (dPods exists from then on)
+    int pullDeviceWrites();
     int initialize(mi_world& w, float dt, hipStream_t st);
     void solveIteration(mi_world& w, hipStream_t st);
     int solveIterationReference(mi_world& w, hipStream_t st);   // mi_debug_set_solve_order: sequentially, type by type, pool order

@@ -176,4 +176,47 @@ __global__ __launch_bounds__(256) void k_scatter_states(uint32_t n, const uint32
     bLinVel[b] = make_float4(s[7], s[8], s[9], 0.f); bAngVel[b] = make_float4(s[10], s[11], s[12], 0.f);
 }
 
+// k_scatter_states for a caller that decides on the device which rows count: row i is written iff mask[i / group] != 0 (e.g. `group` bodies per
+// environment, one flag per environment); every other body is left untouched.
+__global__ __launch_bounds__(256) void k_scatter_states_masked(uint32_t n, const uint32_t* __restrict__ ids, const float* __restrict__ in, const uint32_t* __restrict__ mask, uint32_t group,
+                                                               uint32_t nb, float4* __restrict__ bPos, float4* __restrict__ bRot, float4* __restrict__ bLinVel, float4* __restrict__ bAngVel) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || mask[i / group] == 0u) return;
+    uint32_t b = ids[i];
+    if (b >= nb) return;
+    const float* s = in + 13 * (size_t)i;
+    bPos[b] = make_float4(s[0], s[1], s[2], 0.f); bRot[b] = make_float4(s[3], s[4], s[5], s[6]);
+    bLinVel[b] = make_float4(s[7], s[8], s[9], 0.f); bAngVel[b] = make_float4(s[10], s[11], s[12], 0.f);
+}
+// Whole constraint PODs (`words` 32-bit words each) from a caller's device array into the type's POD array: one lane per word, pod i -> position idx[i].
+__global__ __launch_bounds__(256) void k_scatter_pods(uint32_t count, uint32_t words, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ src, uint32_t numPods, uint32_t* __restrict__ dst) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)count * words) return;
+    const uint32_t i = (uint32_t)(t / words), k = (uint32_t)(t % words);
+    const uint32_t d = idx[i];
+    if (d < numPods) dst[(size_t)d * words + k] = src[t];
+}
+
+// k_add_forces (world_capi.inc) for a list that is mostly misses (one slot per environment, few live): 1024 lanes look at 1024 entries at a time, lane 0 then adds the hits
+// of that stretch in index order — the same sums in the same order as the one-lane loop, without a dependent load per dead entry.
+__global__ __launch_bounds__(1024) void k_add_forces_sparse(uint32_t n, const uint32_t* __restrict__ bodies, const float* __restrict__ ft, float4* __restrict__ bForce, float4* __restrict__ bTorque) {
+    __shared__ unsigned long long hits[16];
+    for (uint32_t base = 0; base < n; base += 1024u) {
+        const uint32_t i = base + threadIdx.x;
+        const bool hit = i < n && bodies[i] != 0xFFFFFFFFu;
+        const unsigned long long m = __ballot(hit);
+        if ((threadIdx.x & 63u) == 0u) hits[threadIdx.x >> 6] = m;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (uint32_t w = 0; w < 16u; ++w)
+                for (unsigned long long rest = hits[w]; rest; rest &= rest - 1ull) {
+                    const uint32_t j = base + 64u * w + (uint32_t)__builtin_ctzll(rest), b = bodies[j];
+                    float4 f = bForce[b], t = bTorque[b];
+                    f.x += ft[6 * (size_t)j]; f.y += ft[6 * (size_t)j + 1]; f.z += ft[6 * (size_t)j + 2]; t.x += ft[6 * (size_t)j + 3]; t.y += ft[6 * (size_t)j + 4]; t.z += ft[6 * (size_t)j + 5];
+                    bForce[b] = f; bTorque[b] = t;
+                }
+        __syncthreads();
+    }
+}
+
 }  // namespace mi

@@ -9,7 +9,9 @@
 // own ground slab, entities [15 e, 15 e + 15), rays of the random pushes are restricted to that range.
 //
 // Host side only (no kernels here): it talks to the physics library through the C ABI of include/mi_physics.h (a test build
-// may put another implementation of those calls behind the same names: "The physics backend" below).
+// may put another implementation of those calls behind the same names: "The physics backend" below).  The device-resident step
+// (resetPhysicsBatchDevice / updatePhysicsBatchDevice) is learning_device.hip; this file keeps the world, the host's copy of the
+// environments and which of the two paths steps the batch.
 //
 // Stated deviations: resetPhysics also WRITES the initial state to outState (the reference leaves the buffer untouched);
 // the push RNG is seeded with a fixed default instead of time(0) (setPhysicsSeed changes it); an episode reset puts the
@@ -27,6 +29,7 @@
 
 #include "../../include/mi_physics.h"
 #include "../../include/mi_constraints.h"
+#include "learning_shared.hpp"
 
 // The physics backend.  The product build talks to libmi_physics.so through include/mi_physics.h.  A build may supply another implementation of the same calls through
 // a header of its own (-DMI_LEARNING_BACKEND_HEADER='"path"'; the parity tests do, to run this environment code over their checker): that header defines PHYS(name),
@@ -34,6 +37,7 @@
 #ifdef MI_LEARNING_BACKEND_HEADER
 #include MI_LEARNING_BACKEND_HEADER
 #else
+#include "learning_device.hpp"   // the device path (learning_device.hip): what the two units know of each other
 #define PHYS(name) mi_##name
 typedef mi_world phys_world;
 static inline int physCreateWorld(int device, phys_world** out) { mi_world_desc desc{}; desc.device = device; return mi_world_create(&desc, out); }
@@ -44,98 +48,14 @@ static inline const char* physLastError() { return mi_last_error(); }
 
 namespace {
 
-// ---- the little math the environment needs (src/core/math.h; operation order kept) ---------------------------------------
-struct v3 { float x, y, z; };
-struct q4 { float x, y, z, w; };
-inline v3 operator+(v3 a, v3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-inline v3 operator-(v3 a, v3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline v3 operator*(v3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-inline v3 operator*(float s, v3 a) { return a * s; }
-inline float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-inline v3 cross(v3 a, v3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-inline float length(v3 a) { return std::sqrt(dot(a, a)); }
-inline v3 normalize(v3 a) { float l = length(a); return a * (1.f / l); }
-inline q4 conjugate(q4 a) { return {-a.x, -a.y, -a.z, a.w}; }
-inline q4 operator*(q4 a, q4 b) {   // math.h:627-633
-    v3 av{a.x, a.y, a.z}, bv{b.x, b.y, b.z};
-    float w = a.w * b.w - dot(av, bv);
-    v3 v = av * b.w + bv * a.w + cross(av, bv);
-    return {v.x, v.y, v.z, w};
-}
-inline v3 operator*(q4 q, v3 v) { q4 p{v.x, v.y, v.z, 0.f}; q4 r = q * p * conjugate(q); return {r.x, r.y, r.z}; }   // math.h:642-646
+// the little math, the xorshift64 generator, the humanoid's tables and the environment arithmetic (state, part points, reward, push draw):
+// learning_shared.hpp, which the device path's kernels compile too
+using namespace learn;
 inline q4 axisAngle(v3 axis, float angle) {   // quat(vec3 axis, float angle), math.h:335-343
     float h = angle * 0.5f, s = std::sin(h);
     return {axis.x * s, axis.y * s, axis.z * s, std::cos(h)};
 }
-inline float lerpf(float l, float u, float t) { return l + t * (u - l); }
-inline float clampf(float v, float l, float u) { float r = l > v ? l : v; return u < r ? u : r; }
-constexpr float kPi = 3.14159265359f;
 inline float deg2rad(float d) { return d * (kPi / 180.f); }
-
-// random_number_generator (src/core/random.h:5-52): xorshift64
-struct Rng {
-    uint64_t state;
-    uint64_t next64() { uint64_t x = state; x ^= x << 13; x ^= x >> 7; x ^= x << 17; state = x; return x; }
-    uint32_t next32() { return (uint32_t)next64(); }
-    uint32_t between(uint32_t lo, uint32_t hi) { return next32() % (hi - lo) + lo; }
-    float float01() { return (float)next32() / (float)0xFFFFFFFFu; }
-    float floatBetween(float lo, float hi) { return lerpf(lo, hi, (float01() - 0.f) / (1.f - 0.f)); }
-};
-
-// ---- the humanoid (src/physics/ragdoll.cpp:9-123) ------------------------------------------------------------------------
-constexpr int kParts = 14, kCone = 7, kHinge = 6;
-constexpr int kActionFloats = kCone * 3 + kHinge;          // learning_action: 27
-constexpr int kStateFloats = 13 * 3 + kActionFloats;       // learning_state: 66
-constexpr int kEntitiesPerEnv = kParts + 1;                // ground + body parts
-constexpr float kScale = 0.42f;
-enum Part { TORSO, HEAD, L_UPPER_ARM, L_LOWER_ARM, R_UPPER_ARM, R_LOWER_ARM, L_UPPER_LEG, L_LOWER_LEG, L_FOOT, L_TOES, R_UPPER_LEG, R_LOWER_LEG, R_FOOT, R_TOES };
-const int kParent[kParts] = {-1, TORSO, TORSO, L_UPPER_ARM, TORSO, R_UPPER_ARM, TORSO, L_UPPER_LEG, L_LOWER_LEG, L_FOOT, TORSO, R_UPPER_LEG, R_LOWER_LEG, R_FOOT};
-struct PartDef { v3 pos; float zDeg; };
-const PartDef kPartDefs[kParts] = {
-    {{0.f, 0.f, 0.f}, 0.f}, {{0.f, 1.45f, 0.f}, 0.f},
-    {{-0.6f, 0.75f, 0.f}, -30.f}, {{-0.884f, 0.044f, -0.043f}, -20.f}, {{0.6f, 0.75f, 0.f}, 30.f}, {{0.884f, 0.044f, -0.043f}, 20.f},
-    {{-0.371f, -0.812f, 0.f}, -10.f}, {{-0.452f, -1.955f, 0.f}, -3.5f}, {{-0.498f, -2.585f, -0.18f}, 0.f}, {{-0.498f, -2.585f, -0.637f}, 0.f},
-    {{0.371f, -0.812f, 0.f}, 10.f}, {{0.452f, -1.955f, 0.f}, 3.5f}, {{0.498f, -2.585f, -0.18f}, 0.f}, {{0.498f, -2.585f, -0.637f}, 0.f}};
-struct ColDef { int part; bool box; v3 a, b; float r; };   // capsule (a, b, r) or AABB (centre a = 0, half extents b), before `scale *`
-const ColDef kColDefs[] = {
-    {TORSO, false, {-0.2f, 0.f, 0.f}, {0.2f, 0.f, 0.f}, 0.25f}, {TORSO, false, {-0.16f, 0.32f, 0.f}, {0.16f, 0.32f, 0.f}, 0.2f},
-    {TORSO, false, {-0.14f, 0.62f, 0.f}, {0.14f, 0.62f, 0.f}, 0.22f}, {TORSO, false, {-0.14f, 0.92f, 0.f}, {0.14f, 0.92f, 0.f}, 0.2f},
-    {HEAD, false, {0.f, -0.075f, 0.f}, {0.f, 0.075f, 0.f}, 0.25f},
-    {L_UPPER_ARM, false, {0.f, -0.2f, 0.f}, {0.f, 0.2f, 0.f}, 0.15f}, {L_LOWER_ARM, false, {0.f, -0.2f, 0.f}, {0.f, 0.2f, 0.f}, 0.15f},
-    {R_UPPER_ARM, false, {0.f, -0.2f, 0.f}, {0.f, 0.2f, 0.f}, 0.15f}, {R_LOWER_ARM, false, {0.f, -0.2f, 0.f}, {0.f, 0.2f, 0.f}, 0.15f},
-    {L_UPPER_LEG, false, {0.f, -0.3f, 0.f}, {0.f, 0.3f, 0.f}, 0.25f}, {L_LOWER_LEG, false, {0.f, -0.3f, 0.f}, {0.f, 0.3f, 0.f}, 0.18f},
-    {L_FOOT, true, {0.f, 0.f, 0.f}, {0.1587f, 0.1f, 0.3424f}, 0.f}, {L_TOES, false, {-0.0587f, 0.f, 0.f}, {0.0587f, 0.f, 0.f}, 0.1f},
-    {R_UPPER_LEG, false, {0.f, -0.3f, 0.f}, {0.f, 0.3f, 0.f}, 0.25f}, {R_LOWER_LEG, false, {0.f, -0.3f, 0.f}, {0.f, 0.3f, 0.f}, 0.18f},
-    {R_FOOT, true, {0.f, 0.f, 0.f}, {0.1587f, 0.1f, 0.3424f}, 0.f}, {R_TOES, false, {-0.0587f, 0.f, 0.f}, {0.0587f, 0.f, 0.f}, 0.1f}};
-constexpr int kNumCols = sizeof(kColDefs) / sizeof(kColDefs[0]);
-// joints in creation order (ragdoll.cpp:100-116); coneIndex / hingeIndex = slot in humanoid_ragdoll::coneTwistConstraints / hingeConstraints
-struct JointDef { bool cone; int slot, a, b, anchorPart; v3 anchor; int axisPart; v3 axis; bool normalizeAxis; float l0, l1; };
-const JointDef kJointDefs[] = {
-    {true, 0, TORSO, HEAD, TORSO, {0.f, 1.2f, 0.f}, -1, {0.f, 1.f, 0.f}, false, 50.f, 90.f},
-    {true, 1, TORSO, L_UPPER_ARM, TORSO, {-0.4f, 1.f, 0.f}, -1, {-1.f, 0.f, 0.f}, false, 130.f, 90.f},
-    {false, 0, L_UPPER_ARM, L_LOWER_ARM, L_UPPER_ARM, {0.f, -0.42f, 0.f}, -1, {1.f, 0.f, 1.f}, true, -5.f, 85.f},
-    {true, 2, TORSO, R_UPPER_ARM, TORSO, {0.4f, 1.f, 0.f}, -1, {1.f, 0.f, 0.f}, false, 130.f, 90.f},
-    {false, 1, R_UPPER_ARM, R_LOWER_ARM, R_UPPER_ARM, {0.f, -0.42f, 0.f}, -1, {1.f, 0.f, -1.f}, true, -5.f, 85.f},
-    {true, 3, TORSO, L_UPPER_LEG, TORSO, {-0.3f, -0.25f, 0.f}, L_UPPER_LEG, {0.f, -1.f, 0.f}, false, -1000.f, 30.f},
-    {false, 2, L_UPPER_LEG, L_LOWER_LEG, L_UPPER_LEG, {0.f, -0.6f, 0.f}, -1, {1.f, 0.f, 0.f}, false, -90.f, 5.f},
-    {true, 4, L_LOWER_LEG, L_FOOT, L_LOWER_LEG, {0.f, -0.52f, 0.f}, L_LOWER_LEG, {0.f, -1.f, 0.f}, false, 75.f, 20.f},
-    {false, 3, L_FOOT, L_TOES, L_FOOT, {0.f, 0.f, -0.36f}, -1, {1.f, 0.f, 0.f}, false, -45.f, 45.f},
-    {true, 5, TORSO, R_UPPER_LEG, TORSO, {0.3f, -0.25f, 0.f}, R_UPPER_LEG, {0.f, -1.f, 0.f}, false, -1000.f, 30.f},
-    {false, 4, R_UPPER_LEG, R_LOWER_LEG, R_UPPER_LEG, {0.f, -0.6f, 0.f}, -1, {1.f, 0.f, 0.f}, false, -90.f, 5.f},
-    {true, 6, R_LOWER_LEG, R_FOOT, R_LOWER_LEG, {0.f, -0.52f, 0.f}, R_LOWER_LEG, {0.f, -1.f, 0.f}, false, 75.f, 20.f},
-    {false, 5, R_FOOT, R_TOES, R_FOOT, {0.f, 0.f, -0.36f}, -1, {1.f, 0.f, 0.f}, false, -45.f, 45.f}};
-
-struct Target { v3 pos[6], vel[6]; q4 localRot; };   // learning_target
-struct Env {
-    float smoothed[kActionFloats];   // lastSmoothedAction
-    float headTargetHeight;
-    v3 torsoVelocityTarget;
-    v3 localPositions[kParts][6];
-    Target targets[kParts];
-    Rng rng;
-    float totalReward;
-    v3 origin;
-};
 
 struct Batch {
     phys_world* world = nullptr;
@@ -146,10 +66,12 @@ struct Batch {
     std::vector<uint32_t> coneIds, hingeIds;         // constraint ids, same layout
     std::vector<float> initialStates;                // [env][part][13]
     std::vector<float> pos, rot, lin, ang;           // per entity, refreshed after every step (transform_component, rb velocities)
-    v3 localCOG[kParts];
+    EnvTables tables;                                // parents, local centres of gravity, local positions: the same for every environment
     uint64_t seed = 0x9E3779B97F4A7C15ull;
     int device = 0;
     std::string error;
+    unsigned long long pushes = 0;                   // random pushes applied since the world was (re)created
+    bool deviceMode = false;                         // the device path steps the batch (learning_device.hip) and holds the RNG states
 };
 Batch g;
 // host threads of the per-environment loops: a fixed small number (MI_LEARN_THREADS overrides) — containers often expose far
@@ -162,16 +84,15 @@ bool ok(int rc, const char* what) {
     if (const char* detail = physLastError()) g.error += std::string(": ") + detail;
     return false;
 }
-uint32_t entityOf(int env, int part) { return (uint32_t)(env * kEntitiesPerEnv + 1 + part); }
-v3 entityPos(uint32_t e) { return {g.pos[3 * e], g.pos[3 * e + 1], g.pos[3 * e + 2]}; }
-q4 entityRot(uint32_t e) { return {g.rot[4 * e], g.rot[4 * e + 1], g.rot[4 * e + 2], g.rot[4 * e + 3]}; }
-v3 entityLin(uint32_t e) { return {g.lin[3 * e], g.lin[3 * e + 1], g.lin[3 * e + 2]}; }
-v3 entityAng(uint32_t e) { return {g.ang[3 * e], g.ang[3 * e + 1], g.ang[3 * e + 2]}; }
-v3 globalCOG(uint32_t e, int part) { return entityPos(e) + entityRot(e) * g.localCOG[part]; }   // rigid_body_component::getGlobalCOGPosition
+PoseRows rows() { return PoseRows{g.pos.data(), g.rot.data(), g.lin.data(), g.ang.data()}; }   // the host's pose cache
+v3 entityPos(uint32_t e) { return learn::entityPos(rows(), e); }
 
 void destroyWorld() {
+#ifndef MI_LEARNING_BACKEND_HEADER
+    learn_device::release();   // (the device path's buffers belong to this world)
+#endif
     if (g.world) PHYS(world_destroy)(g.world);
-    g.world = nullptr; g.n = 0;
+    g.world = nullptr; g.n = 0; g.deviceMode = false;
 }
 
 bool refreshTransforms() {
@@ -204,82 +125,36 @@ void localPositionsOf(int part, v3 out[6]) {
 
 // learned_locomotion::updateConstraint x13 over the smoothed action (learned_locomotion.cpp:74-115) -> one batched update per type
 bool applyActions(const float* actions /* [n][27] or null = all zero */, const std::vector<int>* only = nullptr) {
-    const float beta = 0.1f;
     std::vector<uint8_t> pick;
     if (only) { pick.assign(g.n, 0); for (int e : *only) pick[e] = 1; }
 #pragma omp parallel for schedule(static) num_threads(g_threads) if (g.n >= 256)
     for (int e = 0; e < g.n; ++e) {
         if (only && !pick[e]) continue;
         Env& env = g.envs[e];
-        for (int i = 0; i < kActionFloats; ++i) env.smoothed[i] = lerpf(env.smoothed[i], actions ? actions[e * kActionFloats + i] : 0.f, beta);
-        for (int s = 0; s < kCone; ++s) {
-            mi_cone_twist_constraint& c = g.cones[e * kCone + s];
-            c.max_swing_motor_torque = 200.f; c.max_twist_motor_torque = 200.f;
-            c.swing_motor_type = 1u; c.twist_motor_type = 1u;   // constraint_position_motor
-            c.twist_motor_velocity_or_target_angle = env.smoothed[3 * s];        // cone_twist_action: twistTargetAngle, swingTargetAngle, swingAxisAngle
-            c.swing_motor_velocity_or_target_angle = env.smoothed[3 * s + 1];
-            c.swing_motor_axis = env.smoothed[3 * s + 2];
-        }
-        for (int s = 0; s < kHinge; ++s) {
-            mi_hinge_constraint& h = g.hinges[e * kHinge + s];
-            h.max_motor_torque = 200.f; h.motor_type = 1u;
-            h.motor_velocity_or_target_angle = env.smoothed[kCone * 3 + s];
-        }
+        smoothAction(env.smoothed, actions ? actions + (size_t)e * kActionFloats : nullptr);
+        armMotors(env.smoothed, &g.cones[(size_t)e * kCone], &g.hinges[(size_t)e * kHinge]);
     }
     return ok(PHYS(constraints_update)(g.world, MI_CONSTRAINT_CONE_TWIST, (uint32_t)g.coneIds.size(), g.coneIds.data(), g.cones.data(), sizeof(mi_cone_twist_constraint)), "constraints_update") &&
            ok(PHYS(constraints_update)(g.world, MI_CONSTRAINT_HINGE, (uint32_t)g.hingeIds.size(), g.hingeIds.data(), g.hinges.data(), sizeof(mi_hinge_constraint)), "constraints_update");
 }
 
-// learned_locomotion::getState (learned_locomotion.cpp:117-156); returns hasFallen (head below 1 m)
-bool stateOf(int e, float* out) {
-    const Env& env = g.envs[e];
-    v3 cog = globalCOG(entityOf(e, TORSO), TORSO);
-    cog.y = 0.f;
-    auto toLocalPos = [&](v3 p) { return p - cog; };        // trs(cog, identity): conjugate(identity) * (p - cog) / 1
-    auto part = [&](int p, float* posOut, float* velOut) {
-        v3 lp = toLocalPos(globalCOG(entityOf(e, p), p)), lv = entityLin(entityOf(e, p));
-        posOut[0] = lp.x; posOut[1] = lp.y; posOut[2] = lp.z; velOut[0] = lv.x; velOut[1] = lv.y; velOut[2] = lv.z;
-    };
-    // learning_state layout (learned_locomotion.h:41-65)
-    v3 cv = entityLin(entityOf(e, TORSO));
-    out[0] = cv.x; out[1] = cv.y; out[2] = cv.z;
-    part(L_TOES, out + 3, out + 6); part(R_TOES, out + 9, out + 12); part(TORSO, out + 15, out + 18); part(HEAD, out + 21, out + 24);
-    part(L_LOWER_ARM, out + 27, out + 30); part(R_LOWER_ARM, out + 33, out + 36);
-    std::memcpy(out + 39, env.smoothed, sizeof(env.smoothed));
-    return out[21 + 1] < 1.f;
-}
+// learned_locomotion::getState; returns hasFallen (head below 1 m)
+bool stateOf(int e, float* out) { return learn::stateOf(rows(), g.tables.localCOG, e, g.envs[e].smoothed, out); }
 
-// training_locomotion::getBodyPartTarget / readPartDifference / getReward (learned_locomotion.cpp:248-345)
-void partPoints(int e, int p, v3 pos[6], v3 vel[6], q4& localRot) {
-    const uint32_t ent = entityOf(e, p);
-    const v3 tp = entityPos(ent); const q4 tr = entityRot(ent);
-    const v3 cog = globalCOG(ent, p), lv = entityLin(ent), av = entityAng(ent);
-    for (int i = 0; i < 6; ++i) {
-        v3 gp = tr * g.envs[e].localPositions[p][i] + tp;     // transformPosition (scale 1)
-        pos[i] = gp;
-        vel[i] = lv + cross(av, gp - cog);                   // getGlobalPointVelocity
-    }
-    q4 parentRot = kParent[p] >= 0 ? entityRot(entityOf(e, kParent[p])) : q4{0.f, 0.f, 0.f, 1.f};
-    localRot = tr * conjugate(parentRot);
-}
+// training_locomotion::getReward (learned_locomotion.cpp:318-345): the parts' errors added in part order
 float rewardOf(int e) {
     const Env& env = g.envs[e];
+    const PoseRows r = rows();
     float positionError = 0.f, velocityError = 0.f, rotationError = 0.f;
     for (int p = 0; p < kParts; ++p) {
         v3 pos[6], vel[6]; q4 localRot;
-        partPoints(e, p, pos, vel, localRot);
-        float pe = 0.f, ve = 0.f;
-        for (int i = 0; i < 6; ++i) { pe += length(pos[i] - env.targets[p].pos[i]); ve += length(vel[i] - env.targets[p].vel[i]); }
-        q4 diff = env.targets[p].localRot * conjugate(localRot);
+        partPoints(r, g.tables, e, p, pos, vel, localRot);
+        float pe, ve, re;
+        partErrors(pos, vel, localRot, env.targets[p], pe, ve, re);
         positionError += pe; velocityError += ve;
-        rotationError += 2.f * std::acos(clampf(diff.w, -1.f, 1.f));
+        rotationError += re;
     }
-    float vcmError = length(entityLin(entityOf(e, TORSO)) - env.torsoVelocityTarget);
-    float rp = std::exp(-10.f / kParts * positionError), rv = std::exp(-1.f / kParts * velocityError);
-    float rlocal = std::exp(-10.f / kParts * rotationError), rvcm = std::exp(-vcmError);
-    float headHeight = entityPos(entityOf(e, HEAD)).y;
-    float fall = clampf(1.3f - 1.4f * (env.headTargetHeight - headHeight), 0.f, 1.f);
-    return fall * (rp + rv + rlocal + rvcm);
+    return rewardOfSums(positionError, velocityError, rotationError, entityLin(r, entityOf(e, TORSO)), env.torsoVelocityTarget, env.headTargetHeight, entityPos(entityOf(e, HEAD)).y);
 }
 
 // training_locomotion::reset + learned_locomotion::reset (learned_locomotion.cpp:294-307, 35-43) for the listed environments,
@@ -287,12 +162,11 @@ float rewardOf(int e) {
 void resetEnvState(int e) {
     Env& env = g.envs[e];
     for (int p = 0; p < kParts; ++p) {
-        localPositionsOf(p, env.localPositions[p]);
-        partPoints(e, p, env.targets[p].pos, env.targets[p].vel, env.targets[p].localRot);
+        partPoints(rows(), g.tables, e, p, env.targets[p].pos, env.targets[p].vel, env.targets[p].localRot);
     }
     std::memset(env.smoothed, 0, sizeof(env.smoothed));
     env.headTargetHeight = entityPos(entityOf(e, HEAD)).y;
-    env.torsoVelocityTarget = {0.f, 0.f, 0.f};
+    env.torsoVelocityTarget = kTorsoVelocityTarget;
     env.totalReward = 0.f;
 }
 
@@ -300,7 +174,7 @@ bool buildWorld(int n) {
     destroyWorld();
     g.error.clear();
     if (!ok(physCreateWorld(g.device, &g.world), "world_create")) return false;
-    g.n = n;
+    g.n = n; g.pushes = 0;
     g.envs.assign(n, Env{});
     const int side = (int)std::ceil(std::sqrt((double)n));
     const float spacing = 50.f;   // ground slabs are 40 m x 40 m
@@ -373,7 +247,11 @@ bool buildWorld(int n) {
         const uint32_t ne = (uint32_t)(n * kEntitiesPerEnv);
         std::vector<float> cog(3 * (size_t)ne);
         if (!ok(PHYS(world_get_mass_properties)(g.world, nullptr, nullptr, cog.data(), ne), "world_get_mass_properties")) return false;
-        for (int p = 0; p < kParts; ++p) g.localCOG[p] = {cog[3 * entityOf(0, p)], cog[3 * entityOf(0, p) + 1], cog[3 * entityOf(0, p) + 2]};
+        for (int p = 0; p < kParts; ++p) {
+            g.tables.parent[p] = kParent[p];
+            g.tables.localCOG[p] = {cog[3 * entityOf(0, p)], cog[3 * entityOf(0, p) + 1], cog[3 * entityOf(0, p) + 2]};
+            localPositionsOf(p, g.tables.localPositions[p]);
+        }
     }
     // initial pose: humanoid_ragdoll::create(scene, vec3(0, 1.25, 0)) (rotation 0), shifted to the environment's origin
     g.initialStates.assign((size_t)n * kParts * MI_BODY_STATE_FLOATS, 0.f);
@@ -418,6 +296,17 @@ bool ensureBatch(int n) {
     return resetEnvs(all);
 }
 
+// Which path steps the batch is fixed by the reset call.  Leaving the device path: the per-environment RNG states come back (they
+// survive resets; setPhysicsSeed sends new ones up at once); everything else a reset writes anew.
+const char* const kWrongModeHost = "the batch was reset with resetPhysicsBatchDevice: step it with updatePhysicsBatchDevice (or reset it with resetPhysicsBatch / resetPhysics first)";
+bool enterHostMode() {
+#ifndef MI_LEARNING_BACKEND_HEADER
+    if (g.deviceMode && !learn_device::pullRng(g.envs.data(), g.n)) return false;
+#endif
+    g.deviceMode = false;
+    return true;
+}
+
 // MI_LEARN_PROFILE=1: wall time per phase of the batched step, printed every 100 steps (development aid)
 struct PhaseTimer {
     double acc[6] = {0, 0, 0, 0, 0, 0}; int steps = 0; bool on = std::getenv("MI_LEARN_PROFILE") != nullptr;
@@ -440,17 +329,13 @@ bool stepAll(const float* actions, float* outStates, float* outRewards, int* out
     // random pushes: with probability 0.02 a ray from 5 m away at a random body part (458-468), strength 1000
     std::vector<float> origins, directions; std::vector<uint32_t> ranges;
     for (int e = 0; e < g.n; ++e) {
-        Rng& rng = g.envs[e].rng;
-        if (rng.float01() < 0.02f) {
-            uint32_t part = rng.between(0, kParts - 1);
-            v3 target = entityPos(entityOf(e, (int)part)) + v3{0.f, 0.2f, 0.f};
-            float dx = rng.floatBetween(-1.f, 1.f), dz = rng.floatBetween(-1.f, 1.f);
-            v3 dir = normalize(v3{dx, 0.f, dz});
-            v3 origin = target - dir * 5.f;
+        v3 origin, dir;
+        if (drawPush(g.envs[e].rng, rows(), e, origin, dir)) {
             origins.insert(origins.end(), {origin.x, origin.y, origin.z}); directions.insert(directions.end(), {dir.x, dir.y, dir.z});
             ranges.push_back((uint32_t)(e * kEntitiesPerEnv)); ranges.push_back((uint32_t)((e + 1) * kEntitiesPerEnv));
         }
     }
+    g.pushes += origins.size() / 3;
     if (!origins.empty() && !ok(PHYS(world_test_interactions)(g.world, (uint32_t)(origins.size() / 3), origins.data(), directions.data(), nullptr, ranges.data()), "world_test_interactions")) return false;
     // physicsStep(scene, arena, timer = 0, settings{frameRate 60}, 1/60): one internal step; the interpolated transforms end
     // up at physics_transform0, i.e. the pose BEFORE this step, while the velocities are the new ones (physics.cpp:1364-1402)
@@ -504,6 +389,7 @@ EXPORT void getPhysicsRanges(float* stateMin, float* stateMax, float* actionMin,
 }
 
 EXPORT void resetPhysics(float* outState) {
+    if (!enterHostMode()) return;
     if (!ensureBatch(1)) return;
     std::vector<int> all{0};
     if (!resetEnvs(all)) return;
@@ -511,6 +397,7 @@ EXPORT void resetPhysics(float* outState) {
 }
 
 EXPORT int updatePhysics(float* action, float* outState, float* outReward) {
+    if (g.deviceMode) { g.error = kWrongModeHost; return 1; }
     if (!g.world && !ensureBatch(1)) return 1;
     int done = 0;
     float reward = 0.f;
@@ -525,13 +412,20 @@ EXPORT int updatePhysics(float* action, float* outState, float* outReward) {
 }
 
 // ---- batched environments -----------------------------------------------------------------------------------------------
-EXPORT void setPhysicsSeed(unsigned long long seed) { g.seed = seed; for (int e = 0; e < g.n; ++e) g.envs[e].rng.state = g.seed + 0x632BE59BD9B4E019ull * (uint64_t)(e + 1); }
+EXPORT void setPhysicsSeed(unsigned long long seed) {
+    g.seed = seed;
+    for (int e = 0; e < g.n; ++e) g.envs[e].rng.state = g.seed + 0x632BE59BD9B4E019ull * (uint64_t)(e + 1);
+#ifndef MI_LEARNING_BACKEND_HEADER
+    if (g.deviceMode) (void)learn_device::pushRng(g.envs.data(), g.n);   // the next step draws from the new stream on either path (a failure is in getPhysicsError())
+#endif
+}
 EXPORT void setPhysicsDevice(int device) { if (device != g.device) { destroyWorld(); g.device = device; } }
 EXPORT const char* getPhysicsError() { return g.error.c_str(); }
 EXPORT int getPhysicsNumEnvs() { return g.n; }
 // (Re)creates `numEnvs` environments and writes their initial states ([numEnvs][stateSize]); 0 on success.
 EXPORT int resetPhysicsBatch(int numEnvs, float* outStates) {
     if (numEnvs <= 0) return MI_ERR_INVALID_ARGUMENT;
+    if (!enterHostMode()) return MI_ERR_DEVICE;
     if (!ensureBatch(numEnvs)) return MI_ERR_DEVICE;
     std::vector<int> all(numEnvs); for (int e = 0; e < numEnvs; ++e) all[e] = e;
     if (!resetEnvs(all)) return MI_ERR_DEVICE;
@@ -542,8 +436,31 @@ EXPORT int resetPhysicsBatch(int numEnvs, float* outStates) {
 // ragdoll fell (done = 1) is reset in place after its terminal state was written; 0 on success.
 EXPORT int updatePhysicsBatch(const float* actions, float* outStates, float* outRewards, int* outDone) {
     if (!g.world) return MI_ERR_INVALID_ARGUMENT;
+    if (g.deviceMode) { g.error = kWrongModeHost; return MI_ERR_INVALID_ARGUMENT; }
     std::vector<int> done(g.n);
     if (!stepAll(actions, outStates, outRewards, outDone ? outDone : done.data())) return MI_ERR_DEVICE;
     return MI_OK;
 }
 EXPORT void shutdownPhysics() { destroyWorld(); }
+// Random pushes applied since the world was (re)created — by whichever path stepped it.
+EXPORT unsigned long long getPhysicsPushCount() { return g.pushes; }
+
+// ---- the host's side of the device path (learning_device.hpp) ------------------------------------------------------------
+#ifndef MI_LEARNING_BACKEND_HEADER
+namespace learn_device {
+HostBatch hostBatch() {
+    return HostBatch{g.world, g.n, g.device, g.deviceMode, g.envs.data(), g.cones.data(), g.hinges.data(), g.coneIds.data(), g.hingeIds.data(), g.initialStates.data(),
+                     g.pos.data(), g.rot.data(), g.lin.data(), g.ang.data(), &g.tables};
+}
+bool hostReset(int numEnvs) {
+    if (!enterHostMode() || !ensureBatch(numEnvs)) return false;
+    std::vector<int> all(numEnvs); for (int e = 0; e < numEnvs; ++e) all[e] = e;
+    return resetEnvs(all);
+}
+void hostStates(float* out) { for (int e = 0; e < g.n; ++e) stateOf(e, out + (size_t)e * kStateFloats); }
+void setError(const std::string& what) { g.error = what; }
+bool failed(int rc, const char* what) { return !ok(rc, what); }
+void enterDeviceMode() { g.deviceMode = true; }
+void addPushes(unsigned long long n) { g.pushes += n; }
+}
+#endif

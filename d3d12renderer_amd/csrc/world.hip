@@ -244,6 +244,9 @@ struct mi_world {
     bool posesWantedAhead();
     void posesArm(bool lerpAfterwards, float lerpTAfterwards);
     int posesProduce(float t, bool fromNextState, bool ahead);
+    int posesEnsureTables();
+    DBuf<float4> poseStagePos, poseStageRot; DBuf<float> poseScratch;   // mi_world_get_transforms_device_async: host-held transforms on their way up; rows the caller did not ask for
+    DBuf<uint32_t> interBody; DBuf<float> interFT;                      // mi_world_test_interactions_device_async: hit body and (force, torque) per ray
     void posesAbort();
     int posesViewLanded(bool physics, const float** p, const float** r, uint32_t* count, uint64_t* ofStep);
     int posesFetch(float* p, float* r, const float** viewP, const float** viewR, float* lin = nullptr, float* ang = nullptr, const float** viewL = nullptr, const float** viewA = nullptr);

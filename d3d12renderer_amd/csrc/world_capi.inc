@@ -399,6 +399,75 @@ MI_API int mi_world_test_interactions(mi_world* w, uint32_t count, const float* 
     return MI_OK;
 }
 
+// mi_world_test_interactions on rays that already live on the device (k_ray_interactions' own layout): only enqueued.
+MI_API int mi_world_test_interactions_device_async(mi_world* w, uint32_t count, const float* rays8Dev, const uint32_t* ranges2Dev) {
+    if (!w || (count && !rays8Dev)) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    if (w->shard.enabled) return fail(MI_ERR_UNSUPPORTED, "mi_world_test_interactions_device_async: not on a sharded world");
+    if (!count) return MI_OK;
+    int rc = ensureUploaded(w); if (rc != MI_OK) return rc;
+    const uint32_t nc = (uint32_t)w->colliders.size();
+    if (!nc || w->bodies.empty()) return MI_OK;
+    HIP_TRY(w->interBody.ensure(count)); HIP_TRY(w->interFT.ensure(6 * (size_t)count));
+    HullFaces hf{w->hullVerts.p, w->hullRanges.p, w->hullTris.p, w->hullTriRanges.p};
+    k_ray_interactions<<<count, 256, 0, w->stream>>>(nc, rays8Dev, ranges2Dev, w->cTypeBody.p, w->cEntity.p, w->cShape.p, w->bPos.p, w->bRot.p, w->bCogInvMass.p, hf, w->interBody.p, w->interFT.p);
+    k_add_forces_sparse<<<1, 1024, 0, w->stream>>>(count, w->interBody.p, w->interFT.p, w->bForce.p, w->bTorque.p);
+    HIP_TRY(hipGetLastError());
+    w->hostStale = true;
+    return MI_OK;
+}
+
+// ---- constraint PODs written on the device
+extern "C++" {
+template <class JT> static int podIndices(JT& l, uint32_t count, const uint32_t* ids, uint32_t* out) {
+    for (uint32_t i = 0; i < count; ++i) { const int d = l.dense(ids[i]); if (d < 0) return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint id"); out[i] = (uint32_t)d; }
+    return MI_OK;
+}
+}
+MI_API int mi_constraints_to_device_indices(mi_world* w, uint32_t type, uint32_t count, const uint32_t* ids, uint32_t* out) {
+    if (!w || (count && (!ids || !out))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    JointSet& j = w->joints;
+    switch (type) {
+        case MI_CONSTRAINT_DISTANCE: return podIndices(j.distance, count, ids, out);
+        case MI_CONSTRAINT_BALL: return podIndices(j.ball, count, ids, out);
+        case MI_CONSTRAINT_FIXED: return podIndices(j.fixed, count, ids, out);
+        case MI_CONSTRAINT_HINGE: return podIndices(j.hinge, count, ids, out);
+        case MI_CONSTRAINT_CONE_TWIST: return podIndices(j.cone, count, ids, out);
+        case MI_CONSTRAINT_SLIDER: return podIndices(j.slider, count, ids, out);
+    }
+    return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
+}
+extern "C++" {
+template <class JT> static int podsScatter(mi_world* w, JT& l, uint32_t count, const uint32_t* idxDev, const void* podsDev, uint32_t podBytes) {
+    typedef typename std::remove_reference<decltype(l.pods[0])>::type P;
+    static_assert(sizeof(P) % 4 == 0, "PODs are arrays of 32-bit words");
+    if (podBytes != sizeof(P)) return fail(MI_ERR_INVALID_ARGUMENT, "constraint pod size mismatch (the packed mi_*_constraint)");
+    if (l.pods.empty() || !l.dPods) return fail(MI_ERR_INVALID_ARGUMENT, "no constraint of this type");
+    if (l.podsDirty) { HIP_TRY(l.uploadPods(w->stream)); HIP_TRY(hipStreamSynchronize(w->stream)); }   // a host update still waiting for the next step: it goes first, or that step's re-upload would undo this call
+    const uint32_t words = (uint32_t)(sizeof(P) / 4u);
+    const size_t total = (size_t)count * words;
+    k_scatter_pods<<<(uint32_t)((total + 255u) / 256u), 256, 0, w->stream>>>(count, words, idxDev, static_cast<const uint32_t*>(podsDev), (uint32_t)l.pods.size(), reinterpret_cast<uint32_t*>(l.dPods));
+    HIP_TRY(hipGetLastError());
+    l.deviceNewer = true;
+    return MI_OK;
+}
+}
+MI_API int mi_constraints_update_device_async(mi_world* w, uint32_t type, uint32_t count, const uint32_t* idxDev, const void* podsDev, uint32_t podBytes) {
+    if (!w || (count && (!idxDev || !podsDev))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    if (w->shard.enabled) return fail(MI_ERR_UNSUPPORTED, "mi_constraints_update_device_async: not on a sharded world");
+    if (!count) return MI_OK;
+    int rc = ensureUploaded(w); if (rc != MI_OK) return rc;
+    JointSet& j = w->joints;
+    switch (type) {
+        case MI_CONSTRAINT_DISTANCE: return podsScatter(w, j.distance, count, idxDev, podsDev, podBytes);
+        case MI_CONSTRAINT_BALL: return podsScatter(w, j.ball, count, idxDev, podsDev, podBytes);
+        case MI_CONSTRAINT_FIXED: return podsScatter(w, j.fixed, count, idxDev, podsDev, podBytes);
+        case MI_CONSTRAINT_HINGE: return podsScatter(w, j.hinge, count, idxDev, podsDev, podBytes);
+        case MI_CONSTRAINT_CONE_TWIST: return podsScatter(w, j.cone, count, idxDev, podsDev, podBytes);
+        case MI_CONSTRAINT_SLIDER: return podsScatter(w, j.slider, count, idxDev, podsDev, podBytes);
+    }
+    return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
+}
+
 MI_API int mi_world_step_fixed(mi_world* w, const mi_step_settings* s, float dt, uint32_t n) {
     if (!w || !s) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
     if (n > 1 && w->shard.enabled && !w->shard.rccl) return fail(MI_ERR_INVALID_ARGUMENT, "a sharded world with the caller's transport takes one internal step per call (exchange in between)");

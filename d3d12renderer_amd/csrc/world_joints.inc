@@ -27,6 +27,7 @@ static int jointAddTo(mi_world& w, JT& l, uint32_t ea, uint32_t eb, const void* 
 }
 // deleteConstraint / deleteAllConstraints / deleteAllConstraintsFromEntity — src/physics/physics.cpp:443-539
 int JointSet::destroy(uint32_t type, uint32_t id) {
+    { int rc = pullDeviceWrites(); if (rc != MI_OK) return rc; }
     bool ok = false;
     switch (type) {
         case MI_CONSTRAINT_DISTANCE: ok = distance.destroy(id); break;
@@ -38,7 +39,7 @@ int JointSet::destroy(uint32_t type, uint32_t id) {
     }
     return ok ? MI_OK : fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type or id");
 }
-void JointSet::destroyAll() { distance.clearAll(); ball.clearAll(); fixed.clearAll(); hinge.clearAll(); cone.clearAll(); slider.clearAll(); }
+void JointSet::destroyAll() { (void)pullDeviceWrites(); distance.clearAll(); ball.clearAll(); fixed.clearAll(); hinge.clearAll(); cone.clearAll(); slider.clearAll(); }
 void JointSet::destroyOfEntity(uint32_t entity) {
     struct Hit { uint64_t seq; uint32_t type, handle; };
     std::vector<Hit> hits;
@@ -49,6 +50,7 @@ void JointSet::destroyOfEntity(uint32_t entity) {
     for (const Hit& h : hits) (void)destroy(h.type, h.handle);
 }
 int JointSet::add(mi_world& w, uint32_t type, uint32_t ea, uint32_t eb, const void* pod, uint32_t bytes, uint32_t* out) {
+    { int rc = pullDeviceWrites(); if (rc != MI_OK) return rc; }
     switch (type) {
         case MI_CONSTRAINT_DISTANCE: return jointAddTo(w, distance, ea, eb, pod, bytes, out);
         case MI_CONSTRAINT_BALL: return jointAddTo(w, ball, ea, eb, pod, bytes, out);
@@ -66,6 +68,7 @@ template <class JT> static int jointCopy(JT& l, uint32_t id, void* dst, const vo
     return MI_OK;
 }
 int JointSet::update(uint32_t type, uint32_t id, const void* pod, uint32_t bytes) {
+    { int rc = pullDeviceWrites(); if (rc != MI_OK) return rc; }   // (the re-upload sends the WHOLE array: what the device wrote into other constraints must be in it)
     switch (type) {
         case MI_CONSTRAINT_DISTANCE: distance.podsDirty = true; return jointCopy(distance, id, nullptr, pod, bytes);
         case MI_CONSTRAINT_BALL: ball.podsDirty = true; return jointCopy(ball, id, nullptr, pod, bytes);
@@ -76,7 +79,22 @@ int JointSet::update(uint32_t type, uint32_t id, const void* pod, uint32_t bytes
     }
     return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
 }
-int JointSet::uploadPods(hipStream_t st) {   // the host copy is authoritative for the PODs (the device never writes them)
+// Brings the host mirror up to date with what mi_constraints_update_device_async wrote (per type; a no-op otherwise).  Positions in dPods are positions
+// in `pods` as long as no constraint of the type was created or destroyed since the upload — and both pull first.
+int JointSet::pullDeviceWrites() {
+    if (!(distance.deviceNewer || ball.deviceNewer || fixed.deviceNewer || hinge.deviceNewer || cone.deviceNewer || slider.deviceNewer)) return MI_OK;
+    HIP_TRY(hipSetDevice(mirrorDevice));
+    auto pull = [&](auto& t) -> hipError_t {
+        if (!t.deviceNewer) return hipSuccess;
+        t.deviceNewer = false;
+        if (t.pods.empty() || !t.dPods || t.pods.size() > t.dCap) return hipSuccess;
+        return hipMemcpyAsync(t.pods.data(), t.dPods, t.pods.size() * sizeof(t.pods[0]), hipMemcpyDeviceToHost, mirrorStream);
+    };
+    HIP_TRY(pull(distance)); HIP_TRY(pull(ball)); HIP_TRY(pull(fixed)); HIP_TRY(pull(hinge)); HIP_TRY(pull(cone)); HIP_TRY(pull(slider));
+    HIP_TRY(hipStreamSynchronize(mirrorStream));
+    return MI_OK;
+}
+int JointSet::uploadPods(hipStream_t st) {   // the host copy is authoritative for the PODs (unless pullDeviceWrites has something to fetch: the callers that dirty it pull first)
     if (distance.podsDirty) HIP_TRY(distance.uploadPods(st));
     if (ball.podsDirty) HIP_TRY(ball.uploadPods(st));
     if (fixed.podsDirty) HIP_TRY(fixed.uploadPods(st));
@@ -86,6 +104,7 @@ int JointSet::uploadPods(hipStream_t st) {   // the host copy is authoritative f
     return MI_OK;
 }
 int JointSet::get(uint32_t type, uint32_t id, void* pod, uint32_t bytes) {
+    { int rc = pullDeviceWrites(); if (rc != MI_OK) return rc; }
     switch (type) {
         case MI_CONSTRAINT_DISTANCE: return jointCopy(distance, id, pod, nullptr, bytes);
         case MI_CONSTRAINT_BALL: return jointCopy(ball, id, pod, nullptr, bytes);
@@ -157,6 +176,8 @@ int JointSet::addFromGlobal(mi_world& w, uint32_t type, uint32_t ea, uint32_t eb
     return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
 }
 int JointSet::upload(mi_world& w, hipStream_t st) {
+    { int rc = pullDeviceWrites(); if (rc != MI_OK) return rc; }   // (a topology upload re-sends the mirror)
+    mirrorStream = st; mirrorDevice = w.device;
     if (!count()) {   // the last constraint may just have been deleted: nothing of the previous topology may survive
         releaseIslands();
         distance.order.clear(); ball.order.clear(); fixed.order.clear(); hinge.order.clear(); cone.order.clear(); slider.order.clear();

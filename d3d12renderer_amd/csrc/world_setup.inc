@@ -303,6 +303,20 @@ bool mi_world::posesPossible(bool physics, float* t) const {
     *t = follow ? -1.f : lerpT;
     return true;
 }
+// entity -> rigid body (or -1) on the device, and the entities without one: rebuilt after an upload
+int mi_world::posesEnsureTables() {
+    PoseStream& ps = pose;
+    const uint32_t n = (uint32_t)entities.size();
+    if (!ps.tablesValid || ps.tableCount != n) {
+        std::vector<int> eb(n); ps.noBody.clear();
+        for (uint32_t i = 0; i < n; ++i) { eb[i] = entities[i].rb; if (eb[i] < 0) ps.noBody.push_back(i); }
+        HIP_TRY(ps.entBody.ensure(std::max<size_t>(n, 1)));
+        HIP_TRY(hipMemcpyAsync(ps.entBody.p, eb.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));   // (eb is pageable and goes away)
+        ps.tablesValid = true; ps.tableCount = n;
+    }
+    return MI_OK;
+}
 int mi_world::posesProduce(float t, bool fromNextState, bool ahead) {
     HIP_TRY(hipSetDevice(device));
     PoseStream& ps = pose;
@@ -314,14 +328,7 @@ int mi_world::posesProduce(float t, bool fromNextState, bool ahead) {
         for (auto& ff : ps.sets) for (auto& si : ff) HIP_TRY(hipEventCreateWithFlags(&si.landed, hipEventDisableTiming));
     }
     if (ps.copyInFlight) { HIP_TRY(hipStreamWaitEvent(stream, ps.chunkEv[kPoseChunks - 1], 0)); ps.copyInFlight = false; }   // the device-side rows are about to be rewritten
-    if (!ps.tablesValid || ps.tableCount != n) {
-        std::vector<int> eb(n); ps.noBody.clear();
-        for (uint32_t i = 0; i < n; ++i) { eb[i] = entities[i].rb; if (eb[i] < 0) ps.noBody.push_back(i); }
-        HIP_TRY(ps.entBody.ensure(std::max<size_t>(n, 1)));
-        HIP_TRY(hipMemcpyAsync(ps.entBody.p, eb.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));   // (eb is pageable and goes away)
-        ps.tablesValid = true; ps.tableCount = n;
-    }
+    { int rc = posesEnsureTables(); if (rc != MI_OK) return rc; }
     if (ahead && ps.valid && ps.hasVel && !ps.velConsumed) ps.wantVel = false;   // nobody read the velocities of the last frame: they stop riding along
     const bool vel = ps.wantVel;
     const size_t floats = (vel ? 13u : 7u) * (size_t)n;   // [n][4] rotations, [n][3] positions (, [n][3] linear, [n][3] angular velocities)

@@ -26,6 +26,7 @@ MI_API int mi_world_save_checkpoint(mi_world* w, void* out, uint64_t capacity, u
     if (!w || !out_size) return fail(MI_ERR_INVALID_ARGUMENT, "null");
     HIP_TRY(hipSetDevice(w->device));
     int rc = w->download(); if (rc != MI_OK) return rc;
+    rc = w->joints.pullDeviceWrites(); if (rc != MI_OK) return rc;   // (the blob holds the PODs as the next step would see them)
     if (w->shard.enabled) { rc = w->shardCheckOverflow(true); if (rc != MI_OK) return rc; rc = w->shardSyncAxis(); if (rc != MI_OK) return rc; }
     std::vector<unsigned long long> keys; std::vector<uint32_t> vals;
     if (w->tabValid) {   // also with a pending topology edit: the keys are creation indices, the live world keeps the history across it
@@ -90,6 +91,7 @@ MI_API int mi_world_load_checkpoint(mi_world* w, const void* data, uint64_t size
         CheckpointHeader h;
         if (!take(p, end, &h, 1) || h.magic != kCheckpointMagic || h.version != 1) return fail(MI_ERR_INVALID_ARGUMENT, "not a checkpoint of this library version");
         JointSet& j = w->joints;
+        { int prc = j.pullDeviceWrites(); if (prc != MI_OK) return prc; }   // (the blob's PODs replace the mirror; nothing newer may be pulled over them later)
         const uint32_t jc[6] = {(uint32_t)j.distance.pods.size(), (uint32_t)j.ball.pods.size(), (uint32_t)j.fixed.pods.size(), (uint32_t)j.hinge.pods.size(), (uint32_t)j.cone.pods.size(), (uint32_t)j.slider.pods.size()};
         if (h.numEntities != w->entities.size() || h.numBodies != w->bodies.size() || h.numColliders != w->colliders.size() || std::memcmp(jc, h.jointCounts, sizeof(jc)) != 0)
             return fail(MI_ERR_INVALID_ARGUMENT, "checkpoint belongs to a different scene (entity / body / collider / constraint counts differ)");
@@ -545,6 +547,58 @@ MI_API int mi_world_set_body_states_device(mi_world* w, uint32_t n, const uint32
 // next step ordered on the device with no host round trip in between.
 MI_API int mi_world_get_body_states_device_async(mi_world* w, uint32_t n, const uint32_t* idsDev, float* outDev) { return statesDevice(w, n, idsDev, outDev, nullptr, false); }
 MI_API int mi_world_set_body_states_device_async(mi_world* w, uint32_t n, const uint32_t* idsDev, const float* inDev) { return statesDevice(w, n, idsDev, nullptr, inDev, false); }
+// mi_world_set_body_states_device_async with the choice of rows left to the device: the same bookkeeping (the call may write any of the rows)
+MI_API int mi_world_set_body_states_masked_device_async(mi_world* w, uint32_t n, const uint32_t* idsDev, const float* inDev, const uint32_t* maskDev, uint32_t group) {
+    if (!w || (n && (!idsDev || !inDev || !maskDev)) || !group) return fail(MI_ERR_INVALID_ARGUMENT, "null argument, or group = 0");
+    if (w->shard.enabled) return fail(MI_ERR_UNSUPPORTED, "mi_world_set_body_states_masked_device_async: not on a sharded world");
+    int rc = ensureUploaded(w); if (rc != MI_OK) return rc;
+    if (!n) return MI_OK;
+    w->ahead.stale = true; ++w->poseEpoch;
+    k_scatter_states_masked<<<divUp(n, 256), 256, 0, w->stream>>>(n, idsDev, inDev, maskDev, group, (uint32_t)w->bodies.size(), w->bPos.p, w->bRot.p, w->bLinVel.p, w->bAngVel.p);
+    HIP_TRY(hipGetLastError());
+    w->hostStale = true; w->shard.prevValid = false; w->shard.rearmFullSize(); w->pose.valid = false;
+    return MI_OK;
+}
+// The rows of mi_world_get_transforms / mi_world_get_physics_transforms / mi_world_get_velocities in the caller's DEVICE buffers: k_entity_poses, which the
+// pinned pose stream uses too, launched straight into them.  The pose stream itself (its rows, `valid`, `wanted`, the host sets) is not touched; only the
+// entity -> body table is shared.
+MI_API int mi_world_get_transforms_device_async(mi_world* w, uint32_t physics, float* posDev, float* rotDev, float* linDev, float* angDev) {
+    if (!w) return fail(MI_ERR_INVALID_ARGUMENT, "null");
+    if ((reinterpret_cast<uintptr_t>(rotDev) & 15u) != 0u) return fail(MI_ERR_INVALID_ARGUMENT, "rotations4_dev must be 16-byte aligned");
+    if (w->shard.enabled) return fail(MI_ERR_UNSUPPORTED, "mi_world_get_transforms_device_async: not on a sharded world");
+    int rc = ensureUploaded(w); if (rc != MI_OK) return rc;
+    const uint32_t n = (uint32_t)w->entities.size(), nb = (uint32_t)w->bodies.size();
+    if (!n || !nb || (!posDev && !rotDev && !linDev && !angDev)) return MI_OK;
+    rc = w->posesEnsureTables(); if (rc != MI_OK) return rc;
+    const bool follow = physics != 0u || w->transformsFollowPhysics, lerpNow = !follow && w->lerpPending;
+    const float4 *pos = w->bPos.p, *rot = w->bRot.p; float t = -1.f;
+    if (w->hostStale && (follow || (lerpNow && w->p0OnDevice))) { if (!follow) t = w->lerpT; }
+    else {   // the host holds the transforms (nothing stepped since the last download, or physics_transform0 lives there): exactly what the host calls would do, then up in body order
+        rc = w->download(); if (rc != MI_OK) return rc;
+        std::vector<float4> hp(nb), hr(nb);
+        for (uint32_t b = 0; b < nb; ++b) {
+            const HBody& hb = w->bodies[b]; const HEntity& e = w->entities[hb.entity];
+            const V3 p = physics ? hb.p1 : e.pos; const Q4 q = physics ? hb.r1 : e.rot;
+            hp[b] = make_float4(p.x, p.y, p.z, 0.f); hr[b] = make_float4(q.x, q.y, q.z, q.w);
+        }
+        HIP_TRY(w->poseStagePos.ensure(nb)); HIP_TRY(w->poseStageRot.ensure(nb));
+        HIP_TRY(hipMemcpyAsync(w->poseStagePos.p, hp.data(), (size_t)nb * 16, hipMemcpyHostToDevice, w->stream));
+        HIP_TRY(hipMemcpyAsync(w->poseStageRot.p, hr.data(), (size_t)nb * 16, hipMemcpyHostToDevice, w->stream));
+        HIP_TRY(hipStreamSynchronize(w->stream));   // (hp / hr are locals)
+        pos = w->poseStagePos.p; rot = w->poseStageRot.p;
+    }
+    // k_entity_poses writes positions AND rotations, and the velocities when both of their rows are given: a missing row goes to a scratch row of the library
+    float *oP = posDev, *oR = rotDev, *oL = linDev, *oA = angDev;
+    const bool vel = linDev || angDev;
+    if (!oP || !oR || (vel && (!oL || !oA))) {
+        HIP_TRY(w->poseScratch.ensure(4u * (size_t)n));
+        if (!oP) oP = w->poseScratch.p; if (!oR) oR = w->poseScratch.p; if (vel && !oL) oL = w->poseScratch.p; if (vel && !oA) oA = w->poseScratch.p;
+    }
+    hipLaunchKernelGGL(k_entity_poses, dim3(divUp(n, 256u)), dim3(256), 0, w->stream, n, w->pose.entBody.p, pos, rot, w->bPos0.p, w->bRot0.p, t, oP, oR,
+                       w->bLinVel.p, w->bAngVel.p, vel ? oL : nullptr, vel ? oA : nullptr);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
 MI_API int mi_world_get_stream(mi_world* w, void** out) {
     if (!w || !out) return fail(MI_ERR_INVALID_ARGUMENT, "null");
     *out = (void*)w->stream;

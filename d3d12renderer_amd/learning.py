@@ -1,7 +1,8 @@
 """ctypes binding of libPhysics-Lib.so — the reference's learning DLL ABI (src/learning/learned_locomotion.cpp:395-489,
 consumer learning/loco_env.py) plus the batched entry points.  `PhysicsDLL` mirrors the class of the same name in the
 reference's loco_env.py (same methods, same return shapes) so that file's LocoEnv works by pointing it at this library;
-`BatchedLocoEnv` steps many ragdolls per call."""
+`BatchedLocoEnv` steps many ragdolls per call — through host arrays, or (device=True) through torch tensors on the world's GPU without a
+host copy of any per-environment data (resetPhysicsBatchDevice / updatePhysicsBatchDevice)."""
 import ctypes as C
 from pathlib import Path
 
@@ -29,6 +30,13 @@ class PhysicsDLL:
         self._physics.setPhysicsSeed.argtypes = (C.c_ulonglong,)
         self._physics.setPhysicsDevice.argtypes = (C.c_int,)
         self._physics.getPhysicsError.restype = C.c_char_p
+        self._physics.getPhysicsPushCount.restype = C.c_ulonglong
+        self.has_device_path = hasattr(self._physics, "resetPhysicsBatchDevice")   # (a build of learning.cpp alone over another physics backend has none)
+        if self.has_device_path:
+            self._physics.resetPhysicsBatchDevice.argtypes = (C.c_int, C.c_void_p)
+            self._physics.updatePhysicsBatchDevice.argtypes = (C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+            self._physics.getPhysicsStream.restype = C.c_void_p
+        self._device = 0
         self.state_size = self._physics.getPhysicsStateSize()
         self.action_size = self._physics.getPhysicsActionSize()
 
@@ -42,7 +50,12 @@ class PhysicsDLL:
         self._physics.setPhysicsSeed(C.c_ulonglong(seed))
 
     def set_device(self, device):
+        self._device = int(device)
         self._physics.setPhysicsDevice(device)
+
+    def push_count(self):
+        """Random pushes applied since the environments were last (re)created, by either path."""
+        return int(self._physics.getPhysicsPushCount())
 
     def error(self):
         return self._physics.getPhysicsError().decode()
@@ -78,6 +91,36 @@ class PhysicsDLL:
             raise RuntimeError(f"updatePhysicsBatch failed ({rc}): {self.error()}")
         return states, rewards, done != 0
 
+    # --- batched, device resident: torch tensors on the world's GPU in and out
+    def stream(self):
+        """The world's hipStream_t as an integer (0 before the first reset): torch.cuda.ExternalStream(dll.stream()) produces actions on it."""
+        return int(self._physics.getPhysicsStream() or 0)
+
+    def reset_batch_device(self, num_envs):
+        import torch
+        states = torch.zeros((num_envs, self.state_size), dtype=torch.float32, device=f"cuda:{self._device}")
+        torch.cuda.current_stream(states.device).synchronize()   # (the zeros are written on torch's stream, the states on the world's)
+        rc = self._physics.resetPhysicsBatchDevice(num_envs, C.c_void_p(states.data_ptr()))
+        if rc != 0:
+            raise RuntimeError(f"resetPhysicsBatchDevice failed ({rc}): {self.error()}")
+        return states
+
+    def step_batch_device(self, actions):
+        """actions: float32 CUDA tensor [n][action_size] on the world's device -> (states, rewards, done) tensors there.  torch's current stream
+        is synchronised first (the actions must be complete); the outputs are complete on return."""
+        import torch
+        assert actions.is_cuda and actions.dtype == torch.float32 and actions.device.index == self._device
+        a = actions.contiguous()
+        n = a.shape[0]
+        assert tuple(a.shape) == (n, self.action_size)
+        states = torch.empty((n, self.state_size), dtype=torch.float32, device=a.device)
+        rewards = torch.empty(n, dtype=torch.float32, device=a.device); done = torch.empty(n, dtype=torch.int32, device=a.device)
+        torch.cuda.current_stream(a.device).synchronize()
+        rc = self._physics.updatePhysicsBatchDevice(C.c_void_p(a.data_ptr()), C.c_void_p(states.data_ptr()), C.c_void_p(rewards.data_ptr()), C.c_void_p(done.data_ptr()))
+        if rc != 0:
+            raise RuntimeError(f"updatePhysicsBatchDevice failed ({rc}): {self.error()}")
+        return states, rewards, done != 0
+
     def shutdown(self):
         self._physics.shutdownPhysics()
 
@@ -85,17 +128,19 @@ class PhysicsDLL:
 class BatchedLocoEnv:
     """Vectorised counterpart of the reference's LocoEnv (learning/loco_env.py:55-82): `num_envs` ragdolls in one world."""
 
-    def __init__(self, num_envs, path=None, seed=1):
+    def __init__(self, num_envs, path=None, seed=1, device=False):
+        """device=True: states, rewards, done flags and actions are torch tensors on the world's GPU (no per-environment data crosses the host)."""
         self.dll = PhysicsDLL(path)
         self.dll.seed(seed)
         self.num_envs = num_envs
+        self.device = bool(device)
         _, _, self.action_min, self.action_max = self.dll.ranges()
-        self.states = self.dll.reset_batch(num_envs)
+        self.states = self.reset()
 
     def reset(self):
-        self.states = self.dll.reset_batch(self.num_envs)
+        self.states = self.dll.reset_batch_device(self.num_envs) if self.device else self.dll.reset_batch(self.num_envs)
         return self.states
 
     def step(self, actions):
-        self.states, rewards, done = self.dll.step_batch(actions)
+        self.states, rewards, done = self.dll.step_batch_device(actions) if self.device else self.dll.step_batch(actions)
         return self.states, rewards, done, {}

@@ -612,6 +612,40 @@ MI_API int mi_world_get_body_states_device_async(mi_world* world, uint32_t count
 MI_API int mi_world_set_body_states_device_async(mi_world* world, uint32_t count, const uint32_t* body_indices_dev, const float* states13_dev);
 MI_API int mi_world_get_stream(mi_world* world, void** out_hip_stream);
 
+/*
+ * Device-side access for a controller that lives on the same GPU (a policy in PyTorch, a sensor model, scripted pokes): motor targets in,
+ * poses out, pushes and resets without a host copy.  Like the other *_device_async calls: the buffers are device memory (e.g. torch
+ * tensors' data_ptr()), 16-byte aligned; the work is only ENQUEUED on the world's stream (mi_world_get_stream), no host synchronisation;
+ * pending topology edits are uploaded first (that upload, like any, waits for the stream); a sharded world returns MI_ERR_UNSUPPORTED.
+ * Two more cases wait for the stream, because the host still holds what the call needs: mi_constraints_update_device_async after a host
+ * mi_constraint(s)_update that no step has sent up yet (it goes first), and mi_world_get_transforms_device_async while the host holds
+ * the transforms (nothing stepped since the last download): they are sent up.  In a loop of device calls and steps neither occurs.  Each call leaves the world in the state its
+ * host twin would: later steps, downloads and queries see no difference.
+ */
+/* The rows mi_world_get_transforms (physics_transforms = 0; the pending interpolation of mi_world_step included) or
+ * mi_world_get_physics_transforms (!= 0) and mi_world_get_velocities would return at this point of the stream, byte for byte, in entity
+ * order: positions [n][3], rotations [n][4], linear and angular velocities [n][3]; any pointer may be NULL.  Rows of entities WITHOUT a
+ * rigid body are NOT WRITTEN: their transforms live on the host and never change in a step — fill them once from mi_world_get_transforms.
+ * The pinned pose stream of mi_world_view_transforms is neither used nor disturbed. */
+MI_API int mi_world_get_transforms_device_async(mi_world* world, uint32_t physics_transforms, float* positions3_dev, float* rotations4_dev,
+                                                float* linear3_dev, float* angular3_dev);
+/* Constraint ids -> positions in the type's device POD array (host side).  The positions stay valid until a constraint of that type is
+ * created or destroyed. */
+MI_API int mi_constraints_to_device_indices(mi_world* world, uint32_t type, uint32_t count, const uint32_t* constraint_ids, uint32_t* out_indices);
+/* mi_constraints_update from device memory: whole PODs (pod_bytes = sizeof(mi_*_constraint) of the type, packed back to back) are written to
+ * the positions indices_dev names (an index outside the array is skipped).  The device array is then newer than the library's host copy; the
+ * library fetches it before mi_constraint_get reads that copy, before mi_constraint(s)_update / create / destroy change it, before a
+ * topology upload re-sends it and before a checkpoint saves it — a later host update of one constraint keeps what the device wrote into the others. */
+MI_API int mi_constraints_update_device_async(mi_world* world, uint32_t type, uint32_t count, const uint32_t* indices_dev, const void* pods_dev, uint32_t pod_bytes);
+/* mi_world_test_interactions on rays in device memory: rays8_dev per ray origin3, direction3, strength, pad; ranges2_dev per ray the entity
+ * range [lo, hi) it may hit, NULL = the whole scene.  Forces, torques and the order they are added in are those of the host call.  A ray with
+ * an empty range (lo >= hi) hits nothing and costs no scan of the scene: a caller can keep one slot per environment and mark the idle ones so. */
+MI_API int mi_world_test_interactions_device_async(mi_world* world, uint32_t count, const float* rays8_dev, const uint32_t* ranges2_dev);
+/* mi_world_set_body_states_device_async where the device decides which rows count: row i is written iff mask_dev[i / group] != 0 (uint32
+ * flags, one per `group` consecutive rows — e.g. one per environment of `group` bodies); every other body is left untouched. */
+MI_API int mi_world_set_body_states_masked_device_async(mi_world* world, uint32_t count, const uint32_t* body_indices_dev, const float* states13_dev,
+                                                        const uint32_t* mask_dev, uint32_t group);
+
 #ifdef __cplusplus
 }
 #endif
