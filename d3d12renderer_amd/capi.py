@@ -49,6 +49,11 @@ VOLUME_CONTACT_COUNT_MASK, VOLUME_CONTACT_VOLUME_IS_B = 7, 1 << 8
 # mi_terrain_contact (mi_world_terrain_contacts): one record per contact of a volume with the heightmap terrain, in the reference's emission order
 terrain_contact_dtype = np.dtype([("point", "<f4", 3), ("depth", "<f4"), ("normal", "<f4", 3), ("volume", "<u4")])
 assert terrain_contact_dtype.itemsize == 32
+# mi_sweep_hit (mi_world_sweep): the first collider a moved volume touches; entity / collider MI_RAY_MISS and t = +inf on a miss
+sweep_hit_dtype = np.dtype([("entity", "<u4"), ("collider", "<u4"), ("t", "<f4"), ("object_type", "<u4"), ("point", "<f4", 3), ("flags", "<u4"),
+                            ("normal", "<f4", 3), ("volume", "<u4")])
+assert sweep_hit_dtype.itemsize == 48
+SWEEP_INITIAL_OVERLAP, SWEEP_UNCONVERGED = 1, 2
 MI_ERR_CAPACITY = -5
 QUERY_ALL = QUERY_RIGID_BODIES | QUERY_STATIC | QUERY_TERRAIN | QUERY_TRIGGERS | QUERY_FORCE_FIELDS
 
@@ -393,6 +398,29 @@ class World:
         self.L.check(self.L.fn("world_overlap_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_uint32(include), C.c_void_p(ranges_ptr or None),
                                                               C.c_void_p(offsets_ptr), C.c_void_p(hits_ptr or None), C.c_uint32(capacity), C.c_void_p(total_ptr)),
                      "world_overlap_device_async")
+
+    # --- shape-cast scene queries (the first collider a volume touches when it is moved along a displacement; read-only)
+    def _sweep(self, name, volumes, displacements, include, entity_ranges):
+        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
+        d = np.ascontiguousarray(displacements, dtype=np.float32).reshape(len(v), 3)
+        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
+        out = np.zeros(len(v), dtype=sweep_hit_dtype)
+        self.L.check(self.L.fn(name)(self.h, C.c_uint32(len(v)), _ptr(v), _ptr(d), C.c_uint32(include), _ptr(r), _ptr(out)), name)
+        return out
+
+    def sweep(self, volumes, displacements, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_world_sweep: volume i moves from its pose by t * displacements[i], t in [0, 1]; the first touch of each as a `sweep_hit_dtype` array."""
+        return self._sweep("world_sweep", volumes, displacements, include, entity_ranges)
+
+    def debug_sweep_exhaustive(self, volumes, displacements, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_debug_sweep_exhaustive: the same records from every collider against every cast (byte for byte what sweep returns)."""
+        return self._sweep("debug_sweep_exhaustive", volumes, displacements, include, entity_ranges)
+
+    def sweep_device_async(self, n, volumes_ptr, displacements_ptr, out_ptr, include=QUERY_DEFAULT, ranges_ptr=0):
+        """mi_world_sweep_device_async: device buffers (volumes: n x 96 bytes; displacements: n x 4 float32, w ignored; out: n x 48 bytes), enqueued on the
+        world's stream without a host synchronisation."""
+        self.L.check(self.L.fn("world_sweep_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_void_p(displacements_ptr), C.c_uint32(include),
+                                                            C.c_void_p(ranges_ptr or None), C.c_void_p(out_ptr)), "world_sweep_device_async")
 
     # --- contact-manifold scene queries (where a shape touches the world, along which normal, how deep; read-only)
     def volume_contacts(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):

@@ -1,0 +1,369 @@
+// kernels_sweep.hpp — batched shape-cast (sweep) scene queries (mi_world_sweep*, include/mi_physics.h): the first collider a sphere, capsule,
+// cylinder, box or hull touches when it is moved along a displacement, with the time, the point and the normal.  Part of the ONE translation
+// unit of the physics library (world.hip includes it after kernels_overlap.hpp, whose volume rows and grid it uses).  Host side: world_query.inc.
+//
+// Read-only with respect to the step: everything here reads query-owned rows and writes the caller's records.
+//   sweepPair             the pair test: a convex cast in the relative frame (van den Bergen's GJK ray cast against the Minkowski difference
+//                         collider - volume), spheres and capsules as a point / segment core plus a radius margin
+//   k_q_sweep             one wave per cast: the lanes stride over the entries of the grid cells the SWEPT AABB overlaps, then over the large
+//                         list; a cast over many cells strides over all colliders instead; a candidate whose conservative entry time lies
+//                         behind the wave's best time so far is skipped
+//   k_q_sweep_exhaustive  the yardstick: every collider for every cast, rows computed for the call, nothing skipped
+// Both kernels decide through swCandidate and write through swFinalise: the same winner key (t bits << 32 | collider) gives the same bytes.
+// No atomics, no dependence between workgroups; every loop is bounded by a constant, the collider count or the grid.
+#pragma once
+#include "kernels_overlap.hpp"
+
+namespace mi {
+
+constexpr uint32_t kSweepMaxIter = 32;        // iterations of the pair test; a pair that reaches it reports its (lower-bound) t with kSweepUnconverged
+constexpr uint32_t kSweepInitialOverlap = 1u, kSweepUnconverged = 2u;   // MI_SWEEP_*
+constexpr float kSweepTolRel = 2e-6f;         // touching = closer than this times the largest coordinate seen (a few float32 ulps of the support points)
+constexpr uint32_t kSweepRecordRows = 3;      // mi_sweep_hit: three rows of 16 bytes
+
+// ---- the pair test
+struct SweepResult { bool hit; float t; V3 normal, point; uint32_t flags; };
+
+// Support point of a shape's CORE along dir (any length, zero included: some point of the core, never NaN).  Spheres and capsules are their
+// centre / segment (the radius is the margin); cylinders, boxes and hulls are the whole shape.
+__device__ inline V3 swSupport(const Shape& s, const HullSet& hs, V3 dir) {
+    switch (s.type) {
+        case T_SPHERE: return s.a;
+        case T_CAPSULE: return dot(dir, s.a - s.b) > 0.f ? s.a : s.b;
+        case T_CYLINDER: {
+            const V3 ax = s.b - s.a, far = dot(dir, ax) < 0.f ? s.a : s.b;
+            const float aa = sqlen(ax);
+            const V3 perp = aa > 0.f ? dir - ax * (dot(dir, ax) / aa) : dir;
+            const float pl = sqlen(perp);
+            return pl > 1e-12f * sqlen(dir) ? far + perp * (s.radius / sqrtf(pl)) : far;   // (dir along the axis, or too short to square: the cap's centre)
+        }
+        case T_AABB: return V3(dir.x < 0.f ? s.a.x : s.b.x, dir.y < 0.f ? s.a.y : s.b.y, dir.z < 0.f ? s.a.z : s.b.z);
+        case T_OBB: {
+            const V3 l = rotate(conj(s.rot), dir);
+            return s.a + rotate(s.rot, V3(l.x < 0.f ? -s.b.x : s.b.x, l.y < 0.f ? -s.b.y : s.b.y, l.z < 0.f ? -s.b.z : s.b.z));
+        }
+        default: {
+            const V3 l = rotate(conj(s.rot), dir);
+            const uint32_t first = hs.ranges[2 * s.hull], count = hs.ranges[2 * s.hull + 1];
+            V3 best; float maxD = -FLT_MAX;
+            for (uint32_t i = 0; i < count; ++i) {
+                const float4 q = hs.verts[first + i]; const V3 v(q.x, q.y, q.z);
+                const float d = dot(l, v);
+                if (d > maxD) { maxD = d; best = v; }
+            }
+            return s.a + rotate(s.rot, best);
+        }
+    }
+}
+__device__ __forceinline__ float swMargin(const Shape& s) { return s.type <= T_CAPSULE ? s.radius : 0.f; }
+__device__ __forceinline__ float swMaxAbs(V3 a) { return fmaxr(fabsf(a.x), fmaxr(fabsf(a.y), fabsf(a.z))); }
+
+// The simplex: up to four points of the Minkowski difference (collider - volume) with their witnesses on the collider, in named slots (no runtime
+// indexing: it stays in registers).
+struct SwSimplex { V3 y0, y1, y2, y3, b0, b1, b2, b3; uint32_t n; };
+struct SwWeights { float w0, w1, w2, w3; };
+
+// closest point of the triangle (a, b, c) to the origin as barycentric weights (Ericson, Real-Time Collision Detection 5.1.5; every quotient guarded) and
+// the point itself; in the interior the point is the origin's projection along the triangle's normal, not the weighted sum: its DIRECTION is then exact
+// however far apart the vertices lie (the weighted sum of large vertices cancels down to a short vector with the vertices' rounding error)
+__device__ inline void swTriangleWeights(V3 a, V3 b, V3 c, float& u, float& v, float& w, bool& interior) {
+    interior = false;
+    const V3 ab = b - a, ac = c - a;
+    const float d1 = -dot(ab, a), d2 = -dot(ac, a);
+    if (d1 <= 0.f && d2 <= 0.f) { u = 1.f; v = 0.f; w = 0.f; return; }
+    const float d3 = -dot(ab, b), d4 = -dot(ac, b);
+    if (d3 >= 0.f && d4 <= d3) { u = 0.f; v = 1.f; w = 0.f; return; }
+    const float vc = d1 * d4 - d3 * d2;
+    if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { const float den = d1 - d3; v = den > 0.f ? d1 / den : 0.f; u = 1.f - v; w = 0.f; return; }
+    const float d5 = -dot(ab, c), d6 = -dot(ac, c);
+    if (d6 >= 0.f && d5 <= d6) { u = 0.f; v = 0.f; w = 1.f; return; }
+    const float vb = d5 * d2 - d1 * d6;
+    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { const float den = d2 - d6; w = den > 0.f ? d2 / den : 0.f; u = 1.f - w; v = 0.f; return; }
+    const float va = d3 * d6 - d5 * d4;
+    if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) { const float den = (d4 - d3) + (d5 - d6); w = den > 0.f ? (d4 - d3) / den : 0.f; u = 0.f; v = 1.f - w; return; }
+    const float sum = va + vb + vc;
+    if (!(sum > 0.f)) { u = 1.f; v = 0.f; w = 0.f; return; }   // (a triangle without area whose edges all declined: keep a vertex, the caller's next support point replaces it)
+    v = vb / sum; w = vc / sum; u = 1.f - v - w; interior = true;
+}
+__device__ inline V3 swTriangle(V3 a, V3 b, V3 c, float& u, float& v, float& w) {
+    bool interior;
+    swTriangleWeights(a, b, c, u, v, w, interior);
+    if (interior) {
+        const V3 n = cross(b - a, c - a); const float nn = sqlen(n);
+        if (nn > 0.f) return n * (dot(n, a) / nn);
+    }
+    return a * u + b * v + c * w;
+}
+// Closest point of the simplex (points p_i = x - y_i) to the origin: the weights of its vertices (0 = dropped) and the point.  false: the
+// origin lies inside a proper tetrahedron (x is inside the Minkowski difference).
+__device__ inline bool swClosest(uint32_t n, V3 p0, V3 p1, V3 p2, V3 p3, SwWeights& w, V3& v) {
+    w.w0 = 1.f; w.w1 = w.w2 = w.w3 = 0.f;
+    if (n == 1u) { v = p0; return true; }
+    if (n == 2u) {
+        const V3 e = p1 - p0; const float ee = sqlen(e), t = ee > 0.f ? clamp01(-dot(p0, e) / ee) : 0.f;
+        w.w0 = 1.f - t; w.w1 = t; v = p0 * w.w0 + p1 * w.w1; return true;
+    }
+    if (n == 3u) { v = swTriangle(p0, p1, p2, w.w0, w.w1, w.w2); return true; }
+    // The closest point of the tetrahedron's surface: the nearest of its four triangles (right wherever the origin is outside).  The origin counts as
+    // INSIDE only when the tetrahedron is proper, no face is a needle, and the origin lies on the inner side of every face by a clear margin; each face
+    // sees its opposite vertex at the height of the one determinant `det`, so one sign serves all four.  Anything doubtful is "outside": the nearest
+    // triangle then gives a distance within the noise of zero, which ends the search just as well.
+    const V3 nrm = cross(p1 - p0, p2 - p0);
+    const float det = dot(p3 - p0, nrm);
+    bool inside = det * det > 1e-6f * sqlen(nrm) * sqlen(p3 - p0);
+    float bestD = FLT_MAX;
+    v = V3();
+#define MI_SW_FACE(A, B, C, WA, WB, WC, WO)                                                                   \
+    {                                                                                                         \
+        const V3 e1 = B - A, e2 = C - A, fn = cross(e1, e2);                                                  \
+        const float ff = sqlen(fn), sp = -dot(A, fn);   /* the origin's height over the face, times |fn| */  \
+        if (!(ff > 1e-6f * sqlen(e1) * sqlen(e2)) || !(sp * det > 0.f) || !(sp * sp > 1e-8f * ff * sqlen(A))) inside = false; \
+        float fu, fv, fw;                                                                                     \
+        const V3 c = swTriangle(A, B, C, fu, fv, fw); const float dd = sqlen(c);                              \
+        if (dd < bestD) { bestD = dd; v = c; w.WA = fu; w.WB = fv; w.WC = fw; w.WO = 0.f; }                   \
+    }
+    MI_SW_FACE(p0, p1, p2, w0, w1, w2, w3)
+    MI_SW_FACE(p0, p2, p3, w0, w2, w3, w1)
+    MI_SW_FACE(p0, p3, p1, w0, w3, w1, w2)
+    MI_SW_FACE(p1, p3, p2, w1, w3, w2, w0)
+#undef MI_SW_FACE
+    return !inside;
+}
+__device__ __forceinline__ void swPush(SwSimplex& s, V3 y, V3 b) {
+    if (s.n == 0u) { s.y0 = y; s.b0 = b; } else if (s.n == 1u) { s.y1 = y; s.b1 = b; } else if (s.n == 2u) { s.y2 = y; s.b2 = b; } else { s.y3 = y; s.b3 = b; }
+    ++s.n;
+}
+
+// A box collider cut down to the neighbourhood of the cast: its part inside the cast's swept AABB (sweptMin, sweptMax: the union of the volume's AABB at
+// t = 0 and t = 1), grown by a margin; an OBB is cut in its own frame by the swept AABB's bounds there.  The volume touches the collider only inside its
+// swept AABB, so time, point and normal are those of the whole box (a plane that supports a convex shape near the touching point supports all of it), but
+// the simplex of a ground box a hundred units wide no longer has vertices a hundred units apart: float32 keeps its closest point.
+__device__ inline Shape swClipBox(const Shape& b, V3 sweptMin, V3 sweptMax) {
+    if (b.type != T_AABB && b.type != T_OBB) return b;
+    const V3 ext = sweptMax - sweptMin;
+    const float grow = 0.05f * fmaxr(ext.x, fmaxr(ext.y, ext.z)) + 1e-3f;
+    Shape r = b;
+    if (b.type == T_AABB) {
+        const V3 lo = vmax(b.a, sweptMin - V3(grow)), hi = vmin(b.b, sweptMax + V3(grow));
+        if (lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z) { r.a = lo; r.b = hi; }   // (apart: the pair test says so on the whole box)
+        return r;
+    }
+    // the swept AABB's centre and half-extents in the box's frame: |R^T| applied to the half-extents
+    const V3 c = rotate(conj(b.rot), (sweptMin + sweptMax) * 0.5f - b.a), h = ext * 0.5f + V3(grow);
+    const V3 ex = vabs(rotate(conj(b.rot), V3(h.x, 0.f, 0.f))), ey = vabs(rotate(conj(b.rot), V3(0.f, h.y, 0.f))), ez = vabs(rotate(conj(b.rot), V3(0.f, 0.f, h.z)));
+    const V3 e = ex + ey + ez;
+    const V3 lo = vmax(-b.b, c - e), hi = vmin(b.b, c + e);
+    if (lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z) { r.a = b.a + rotate(b.rot, (lo + hi) * 0.5f); r.b = (hi - lo) * 0.5f; }
+    return r;
+}
+
+// THE pair test.  Volume A keeps its orientation and moves by t * d, t in [0, 1]; collider B stands still.  A(t) touches B when t * d reaches
+// C = B - A, so the cast is the ray x = t * d from the origin against C (the cores' difference, grown by both margins R): x advances only by
+// clipping against support planes of C (every clip is safe: t never passes the true time of impact), and the simplex of C's points closest to x
+// ends the search once x is within R + tolerance of it.  normal: unit, from B towards A; point: on B's surface.
+// Never clipped = the shapes touch at t = 0: kSweepInitialOverlap (normal and point are the caller's).  Out of iterations: the current t with
+// kSweepUnconverged.  The result depends on (A, B, d) alone; one body (not inlined) serves the candidate test and the record writer of both kernels.
+__device__ __noinline__ SweepResult sweepPair(const Shape& A, V3 sweptMin, V3 sweptMax, const Shape& collider, const HullSet& hs, V3 d) {
+    SweepResult r; r.hit = false; r.t = 0.f; r.flags = 0u;
+    const Shape B = swClipBox(collider, sweptMin, sweptMax);
+    const float R = swMargin(A) + swMargin(B);
+    float lambda = 0.f, scale = 1.f;
+    V3 x, n, witness, v = swSupport(A, hs, V3()) - swSupport(B, hs, V3());   // (from some point of B to some point of A)
+    if (sqlen(v) == 0.f) v = V3(1.f, 0.f, 0.f);
+    bool clipped = false, done = false;
+    SwSimplex s; s.n = 0u;
+    float dist2 = FLT_MAX, tol = 0.f;
+    for (uint32_t it = 0; it < kSweepMaxIter && !done; ++it) {
+        const V3 pb = swSupport(B, hs, v), pa = swSupport(A, hs, -v), p = pb - pa;
+        scale = fmaxr(scale, fmaxr(swMaxAbs(pa), swMaxAbs(pb)));
+        tol = kSweepTolRel * fmaxr(scale, R);
+        const float lv = len(v), vw = dot(v, x - p) - R * lv;
+        const bool clip = vw > 0.f;
+        if (clip) {   // the plane through C's support point along v separates x from C: clip the ray against it
+            const float vd = dot(v, d);
+            if (vd >= 0.f) return r;   // moving along or away from it: a miss
+            lambda = lambda - vw / vd;
+            if (!(lambda <= 1.f)) return r;   // (t is a lower bound: the touch lies behind the end of the displacement; coordinates that overflowed into a NaN are a miss too)
+            x = d * lambda; n = v; clipped = true;
+        }
+        // a support point the simplex already holds brings nothing new: the search has stalled unless this iteration clipped
+        const bool dup = (s.n > 0u && p.x == s.y0.x && p.y == s.y0.y && p.z == s.y0.z) || (s.n > 1u && p.x == s.y1.x && p.y == s.y1.y && p.z == s.y1.z) ||
+                         (s.n > 2u && p.x == s.y2.x && p.y == s.y2.y && p.z == s.y2.z) || (s.n > 3u && p.x == s.y3.x && p.y == s.y3.y && p.z == s.y3.z);
+        if (dup && !clip) break;
+        if (!dup) swPush(s, p, pb);   // (at most three points were kept: a proper tetrahedron ended the search, a flat one kept a face)
+        SwWeights w;
+        const bool outside = swClosest(s.n, x - s.y0, x - s.y1, x - s.y2, x - s.y3, w, v);
+        if (!outside) { v = V3(); dist2 = 0.f; done = true; break; }
+        witness = s.b0 * w.w0;
+        if (s.n > 1u) witness = witness + s.b1 * w.w1;
+        if (s.n > 2u) witness = witness + s.b2 * w.w2;
+        if (s.n > 3u) witness = witness + s.b3 * w.w3;
+        // keep the vertices that carry the closest point
+        SwSimplex k; k.n = 0u;
+        if (w.w0 > 0.f) swPush(k, s.y0, s.b0);
+        if (s.n > 1u && w.w1 > 0.f) swPush(k, s.y1, s.b1);
+        if (s.n > 2u && w.w2 > 0.f) swPush(k, s.y2, s.b2);
+        if (s.n > 3u && w.w3 > 0.f) swPush(k, s.y3, s.b3);
+        if (k.n == 0u) swPush(k, s.y0, s.b0);
+        s = k;
+        dist2 = sqlen(v);
+        done = dist2 <= (R + tol) * (R + tol);
+    }
+    r.hit = true; r.t = lambda;
+    if (!done) r.flags |= kSweepUnconverged;
+    if (!clipped) { r.flags |= kSweepInitialOverlap; r.t = 0.f; return r; }
+    // round pairs end at distance R from the cores: x - closest is the exact contact normal; flat pairs end at distance 0: the last clip plane's
+    const V3 dir = (R > 0.f && dist2 > 0.25f * R * R) ? v : n;
+    r.normal = dir * (1.f / len(dir));
+    r.point = witness + r.normal * swMargin(B);
+    return r;
+}
+
+// ---- kernels
+// what a cast is: the volume (rows of k_ov_prepare), its displacement, the swept bounds
+struct SweepCast { OverlapVolume q; V3 d, centre, half, sweptMin, sweptMax; bool valid; };
+
+__device__ __forceinline__ SweepCast swLoadCast(const float4* __restrict__ vShape, const float4* __restrict__ vMin, const float4* __restrict__ vMax, const uint32_t* __restrict__ vRange,
+                                               const float4* __restrict__ disp, uint32_t v, uint32_t include) {
+    SweepCast c;
+    c.q = ovLoadVolume(vShape, vMin, vMax, vRange, v, include);
+    const float4 d4 = disp[v];
+    c.d = V3(d4.x, d4.y, d4.z);
+    c.centre = c.q.mn * 0.5f + c.q.mx * 0.5f; c.half = c.q.mx * 0.5f - c.q.mn * 0.5f;   // (halved first: bounds near FLT_MAX must not overflow into an infinite centre)
+    const V3 end = c.q.mx + c.d, begin = c.q.mn + c.d;
+    c.sweptMin = vmin(c.q.mn, begin); c.sweptMax = vmax(c.q.mx, end);
+    c.valid = c.q.valid && qFinite(c.d.x) && qFinite(c.d.y) && qFinite(c.d.z) && qFinite(end.x) && qFinite(end.y) && qFinite(end.z) && qFinite(begin.x) && qFinite(begin.y) && qFinite(begin.z);
+    return c;
+}
+// the swept AABB (the union of the volume's AABB at t = 0 and at t = 1) as the volume the grid helpers take
+__device__ __forceinline__ OverlapVolume swSweptBounds(const SweepCast& c) {
+    OverlapVolume q = c.q;
+    q.mn = c.sweptMin; q.mx = c.sweptMax;
+    return q;
+}
+// THE candidate test: collider k against the cast -> key = t bits << 32 | k, or ~0.  Object type, entity range, a finite AABB, the slab test of the
+// displacement against the collider's AABB grown by the volume's half-extents (a conservative entry time; padded by a few ulps), then sweepPair.
+// The reported t is never below the entry time (both are lower bounds of the true time), so with kSkip a candidate whose entry lies strictly
+// behind bestT cannot win and is not evaluated.
+template <bool kSkip> __device__ inline unsigned long long swCandidate(const OverlapScene& s, const SweepCast& c, uint32_t k, float bestT) {
+    const float4 a = s.mn[k], b = s.mx[k];
+    const uint32_t tag = __float_as_uint(a.w), type = tag & 0xFFu, obj = (tag >> 8) & 0xFFu;
+    if (!(c.q.include & qFlagOf(obj))) return ~0ull;
+    const uint32_t ent = s.cEntity[k];
+    if (ent < c.q.lo || ent >= c.q.hi) return ~0ull;
+    if (!(qExtent(a, b) >= 0.f)) return ~0ull;
+    const float lo[3] = {a.x - c.half.x - c.centre.x, a.y - c.half.y - c.centre.y, a.z - c.half.z - c.centre.z};
+    const float hi[3] = {b.x + c.half.x - c.centre.x, b.y + c.half.y - c.centre.y, b.z + c.half.z - c.centre.z};
+    const float d[3] = {c.d.x, c.d.y, c.d.z};
+    const float o[3] = {c.centre.x, c.centre.y, c.centre.z}, ca[3] = {a.x, a.y, a.z}, cb[3] = {b.x, b.y, b.z};
+    float t0 = 0.f, t1 = 1.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float pad = 1e-5f * (fabsf(o[i]) + fabsf(ca[i]) + fabsf(cb[i]) + 1.f);
+        const float l = lo[i] - pad, h = hi[i] + pad;
+        if (d[i] == 0.f) { if (l > 0.f || h < 0.f) return ~0ull; }
+        else { const float ta = l / d[i], tb = h / d[i]; t0 = fmaxr(t0, fminr(ta, tb)); t1 = fminr(t1, fmaxr(ta, tb)); }
+    }
+    if (!(t0 <= t1) || !qFinite(t1)) return ~0ull;
+    if (kSkip && t0 > bestT) return ~0ull;
+    const SweepResult r = sweepPair(c.q.s, c.sweptMin, c.sweptMax, loadShape(s.shape, k, type), s.hs, c.d);
+    if (!r.hit) return ~0ull;
+    const float t = (r.flags & kSweepInitialOverlap) ? 0.f : fmaxr(r.t, t0);
+    return ((unsigned long long)__float_as_uint(t + 0.f) << 32) | k;
+}
+__device__ __forceinline__ unsigned long long swWaveMin(unsigned long long key) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)key, off, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(key >> 32), off, 64);
+        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+        if (other < key) key = other;
+    }
+    return key;
+}
+// THE record writer (one lane): the winner's pair test once more (it depends on the pair alone: the same bits), three rows of 16 bytes
+__device__ inline void swFinalise(const OverlapScene& s, const SweepCast& c, unsigned long long key, float4 pose, uint32_t v, uint4* __restrict__ out) {
+    uint32_t ent = kRayMiss, col = kRayMiss, obj = 0u, flags = 0u;
+    float t = __uint_as_float(0x7F800000u);   // +inf
+    V3 p, n;
+    if (key != ~0ull) {
+        col = (uint32_t)key; t = __uint_as_float((uint32_t)(key >> 32));
+        const uint32_t tag = __float_as_uint(s.mn[col].w);
+        ent = s.cEntity[col]; obj = (tag >> 8) & 0xFFu;
+        const SweepResult r = sweepPair(c.q.s, c.sweptMin, c.sweptMax, loadShape(s.shape, col, tag & 0xFFu), s.hs, c.d);
+        flags = r.flags;
+        const float dl = len(c.d);
+        if (flags & kSweepInitialOverlap) { p = V3(pose.x, pose.y, pose.z); if (dl > 0.f) n = c.d * (-1.f / dl); }
+        else { p = r.point; n = r.normal; }
+    }
+    out[kSweepRecordRows * (size_t)v] = make_uint4(ent, col, __float_as_uint(t), obj);
+    out[kSweepRecordRows * (size_t)v + 1] = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), flags);
+    out[kSweepRecordRows * (size_t)v + 2] = make_uint4(__float_as_uint(n.x), __float_as_uint(n.y), __float_as_uint(n.z), v);
+}
+__device__ __forceinline__ float swBestT(unsigned long long key) { return __uint_as_float((uint32_t)(swWaveMin(key) >> 32)); }   // (~0: a NaN pattern, nothing is "behind" it)
+
+// ---- accelerated: one wave per cast over the grid cells of the swept AABB (the dedup rule of ovGridWalk: a collider is taken from the entry in the
+// lowest cell of the intersection of its range with the cast's), then the large list; or the stride over all colliders
+__global__ __launch_bounds__(64 * kOvWaves) void k_q_sweep(uint32_t count, uint32_t include, OverlapScene s, const float4* __restrict__ vShape, const float4* __restrict__ vMin,
+                                                          const float4* __restrict__ vMax, const uint32_t* __restrict__ vRange, const float4* __restrict__ vPos,
+                                                          const float4* __restrict__ disp, const QueryGrid* __restrict__ grid, const uint32_t* __restrict__ start,
+                                                          const uint32_t* __restrict__ entries, const uint32_t* __restrict__ large, uint4* __restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u, v = blockIdx.x * kOvWaves + (threadIdx.x >> 6);
+    if (v >= count) return;
+    const SweepCast c = swLoadCast(vShape, vMin, vMax, vRange, disp, v, include);
+    unsigned long long best = ~0ull;
+    if (c.valid) {
+        const QueryGrid g = *grid;
+        const OverlapVolume swept = swSweptBounds(c);
+        uint32_t lo[3], hi[3];
+        float bestT = __uint_as_float(0x7F800000u);
+        if (ovCellRange(g, swept, lo, hi)) {
+            for (uint32_t z = lo[2]; z <= hi[2]; ++z)
+                for (uint32_t y = lo[1]; y <= hi[1]; ++y) {
+                    const uint32_t row = (z * g.dimY + y) * g.dimX;
+                    const uint32_t e0 = start[row + lo[0]], e1 = start[row + hi[0] + 1u];
+                    for (uint32_t eb = e0; eb < e1; eb += 64u) {
+                        const uint32_t e = eb + lane;
+                        if (e < e1) {
+                            const uint32_t k = entries[e];
+                            uint32_t klo[3], khi[3];
+                            if (qCellRange(g, s.mn[k], s.mx[k], klo, khi) && max(klo[1], lo[1]) == y && max(klo[2], lo[2]) == z) {
+                                const uint32_t cell = row + max(klo[0], lo[0]);
+                                if (start[cell] <= e && e < start[cell + 1u]) best = min(best, swCandidate<true>(s, c, k, bestT));
+                            }
+                        }
+                        bestT = swBestT(best);
+                    }
+                }
+            const uint32_t nl = g.numLarge;
+            for (uint32_t i0 = 0; i0 < nl; i0 += 64u) {
+                const uint32_t i = i0 + lane;
+                if (i < nl) best = min(best, swCandidate<true>(s, c, large[i], bestT));
+                bestT = swBestT(best);
+            }
+        } else {
+            for (uint32_t k0 = 0; k0 < s.nc; k0 += 64u) {
+                const uint32_t k = k0 + lane;
+                if (k < s.nc) best = min(best, swCandidate<true>(s, c, k, bestT));
+                bestT = swBestT(best);
+            }
+        }
+    }
+    best = swWaveMin(best);
+    if (lane == 0u) swFinalise(s, c, best, vPos[v], v, out);
+}
+
+// ---- exhaustive: one wave per cast over every collider, no grid, no skipping; the rows in `s` are computed for the call, not taken from the cache
+__global__ __launch_bounds__(64 * kOvWaves) void k_q_sweep_exhaustive(uint32_t count, uint32_t include, OverlapScene s, const float4* __restrict__ vShape, const float4* __restrict__ vMin,
+                                                                     const float4* __restrict__ vMax, const uint32_t* __restrict__ vRange, const float4* __restrict__ vPos,
+                                                                     const float4* __restrict__ disp, uint4* __restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u, v = blockIdx.x * kOvWaves + (threadIdx.x >> 6);
+    if (v >= count) return;
+    const SweepCast c = swLoadCast(vShape, vMin, vMax, vRange, disp, v, include);
+    unsigned long long best = ~0ull;
+    if (c.valid)
+        for (uint32_t k = lane; k < s.nc; k += 64u) best = min(best, swCandidate<false>(s, c, k, 0.f));
+    best = swWaveMin(best);
+    if (lane == 0u) swFinalise(s, c, best, vPos[v], v, out);
+}
+
+}  // namespace mi

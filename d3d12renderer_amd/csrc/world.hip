@@ -33,6 +33,7 @@
 #include "knobs.hpp"
 #include "kernels_query.hpp"
 #include "kernels_overlap.hpp"
+#include "kernels_sweep.hpp"
 #include "kernels_contacts_query.hpp"
 #include "kernels_terrain_query.hpp"
 
@@ -447,7 +448,7 @@ struct mi_world {
             DeviceScan<uint32_t> scan;
             DBuf<uint32_t> candOffsets;
         } vol;
-        // The exhaustive yardstick's own collider rows, computed per call (it does not trust `built`).  Sized by the collider count; overlapEnqueue() grows them
+        // The exhaustive yardstick's own collider rows, computed per call (it does not trust `built`).  Sized by the collider count; overlapEnqueue() and sweepEnqueue() grow them
         // when called with exhaustive = true.
         struct Exhaustive { DBuf<float4> shape, mn, mx; DBuf<QPartial> partials; } exh;
         // Contact queries: candidates (boxes-only overlap records), one 96-byte slot and one flag per candidate, the GJK queue, the scan over the flags.
@@ -468,9 +469,9 @@ struct mi_world {
         // Staging of the blocking variants: inputs copied in, results copied out.  Sized by the call's ray / volume count and record capacity; the blocking
         // entry points grow it.  One set serves every family: a blocking call synchronises before it returns, so two never use it at once.
         struct Blocking {
-            DBuf<float> rays; DBuf<uint32_t> hits;   // ray casts
+            DBuf<float> rays; DBuf<uint32_t> hits;   // ray casts; the displacement rows of a shape cast (rays)
             DBuf<uint32_t> ranges;                   // the optional entity ranges of any family
-            DBuf<uint32_t> volumes, offsets, totals; DBuf<uint4> records;   // volume queries: mi_overlap_hit is one row of 16 bytes, mi_terrain_contact two, mi_volume_contact six
+            DBuf<uint32_t> volumes, offsets, totals; DBuf<uint4> records;   // volume queries: mi_overlap_hit is one row of 16 bytes, mi_terrain_contact two, mi_sweep_hit three, mi_volume_contact six
         } host;
     } query;
     int queryBuild();
@@ -481,6 +482,7 @@ struct mi_world {
                        uint32_t* totalDev, bool exhaustive, uint32_t passes, bool boxesOnly);
     int contactsReserve(uint32_t maxCandidates);
     int contactsEnqueue(uint32_t count, uint32_t bound, uint32_t capacity, uint4* contactsDev, uint32_t* offsetsDev, uint32_t* totals2Dev, bool exhaustive);
+    int sweepEnqueue(uint32_t count, const uint32_t* volumesDev, const float4* displacementsDev, uint32_t include, const uint32_t* rangesDev, uint4* outDev, bool exhaustive);
 };
 
 int mi_world::init(int dev) {

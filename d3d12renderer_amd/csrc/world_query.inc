@@ -1,5 +1,6 @@
 // Part of world.hip (one translation unit; #included there, after world_state.inc): batched scene queries (include/mi_physics.h): ray casts
-// (mi_world_raycast*; kernels in kernels_query.hpp), volume overlaps (mi_world_overlap*; kernels in kernels_overlap.hpp) and the contact manifolds of
+// (mi_world_raycast*; kernels in kernels_query.hpp), volume overlaps (mi_world_overlap*; kernels in kernels_overlap.hpp), shape casts (mi_world_sweep*;
+// kernels in kernels_sweep.hpp) and the contact manifolds of
 // query volumes (mi_world_volume_contacts*; kernels in kernels_contacts_query.hpp) and their terrain contacts (mi_world_terrain_contacts*; the step's terrain
 // kernels of heightmap.hpp under the policy of kernels_terrain_query.hpp).
 //
@@ -169,6 +170,51 @@ int mi_world::overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_
     return MI_OK;
 }
 
+// ---- shape casts.  Volume rows (two launches), then one launch: a wave per cast writes its record.  The exhaustive yardstick computes its own world rows first,
+// as the overlap yardstick does.  displacementsDev: one row of 16 bytes per cast (w ignored).
+int mi_world::sweepEnqueue(uint32_t count, const uint32_t* volumesDev, const float4* displacementsDev, uint32_t include, const uint32_t* rangesDev, uint4* outDev, bool exhaustive) {
+    QueryCache::VolumeRows& v = query.vol; QueryCache::Exhaustive& x = query.exh; const QueryCache::Built& g = query.built;
+    const uint32_t nc = (uint32_t)colliders.size();
+    if (!exhaustive) { int rc = queryBuild(); if (rc != MI_OK) return rc; }
+    Launcher& L = query.L;
+    L.begin(false, false);
+    if (exhaustive) {
+        HIP_TRY(x.shape.ensure(3 * (size_t)std::max(nc, 1u))); HIP_TRY(x.mn.ensure(std::max(nc, 1u))); HIP_TRY(x.mx.ensure(std::max(nc, 1u)));
+        HIP_TRY(x.partials.ensure(divUp(std::max(nc, 1u), 256)));
+        if (nc) L.launch(k_q_colliders, dim3(divUp(nc, 256)), dim3(256), 0, stream, nc, colliderRows(bPos.p, bRot.p, x.shape.p, x.mn.p, x.mx.p), x.partials.p);
+    }
+    const OverlapScene s = overlapScene(exhaustive);
+    int rc = volumeRowsEnqueue(count, volumesDev, rangesDev); if (rc != MI_OK) return rc;
+    const dim3 grid(divUp(count, kOvWaves)), block(64 * kOvWaves);
+    if (exhaustive)
+        L.launch(k_q_sweep_exhaustive, grid, block, 0, stream, count, include, s, (const float4*)v.shape.p, (const float4*)v.mn.p, (const float4*)v.mx.p, (const uint32_t*)v.range.p,
+                 (const float4*)v.cPos.p, displacementsDev, outDev);
+    else
+        L.launch(k_q_sweep, grid, block, 0, stream, count, include, s, (const float4*)v.shape.p, (const float4*)v.mn.p, (const float4*)v.mx.p, (const uint32_t*)v.range.p,
+                 (const float4*)v.cPos.p, displacementsDev, (const QueryGrid*)g.grid.p, (const uint32_t*)g.start.p, (const uint32_t*)g.entries.p, (const uint32_t*)g.large.p, outDev);
+    if (L.firstError != hipSuccess) return fail(MI_ERR_DEVICE, std::string("sweep query: ") + hipGetErrorString(L.firstError));
+    return MI_OK;
+}
+static_assert(sizeof(mi_sweep_hit) == kSweepRecordRows * sizeof(uint4), "a sweep record is three rows of 16 bytes");
+// the blocking variants: volumes, ranges and displacement rows through the blocking staging, the records read back once
+static int sweepHost(mi_world* w, uint32_t count, const mi_query_volume* volumes, const float* displacements3, uint32_t include, const uint32_t* ranges, mi_sweep_hit* out, bool exhaustive) {
+    if (!w || (count && (!volumes || !displacements3 || !out))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = queryPrepare(w); if (rc != MI_OK) return rc;
+    if (!count) return MI_OK;
+    std::vector<float> rows(4 * (size_t)count, 0.f);
+    for (uint32_t i = 0; i < count; ++i) for (int k = 0; k < 3; ++k) rows[4 * (size_t)i + k] = displacements3[3 * (size_t)i + k];
+    mi_world::QueryCache::Blocking& h = w->query.host;
+    HIP_TRY(h.rays.ensure(rows.size())); HIP_TRY(h.records.ensure((size_t)count * kSweepRecordRows));
+    HIP_TRY(hipMemcpyAsync(h.rays.p, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, w->stream));
+    const uint32_t *volumesDev, *rangesDev;
+    rc = stageVolumes(w, count, volumes, &volumesDev); if (rc != MI_OK) return rc;
+    rc = stageRanges(w, count, ranges, &rangesDev); if (rc != MI_OK) return rc;
+    rc = w->sweepEnqueue(count, volumesDev, reinterpret_cast<const float4*>(h.rays.p), include, rangesDev, h.records.p, exhaustive); if (rc != MI_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, h.records.p, (size_t)count * sizeof(mi_sweep_hit), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));   // (the inputs were pageable host memory as well)
+    return MI_OK;
+}
+
 // ---- contact manifolds of query volumes.  Candidates by the overlap passes in boxes-only mode, then narrow phase, GJK queue, scan and write: no read-back
 // between them.  `bound` = the candidates evaluated, at most what contactsReserve() sized the staging for.
 int mi_world::contactsReserve(uint32_t maxCandidates) {
@@ -330,6 +376,20 @@ MI_API int mi_world_overlap_device_async(mi_world* w, uint32_t count, const mi_q
     int rc = queryPrepare(w); if (rc != MI_OK) return rc;
     if (!count) return MI_OK;
     return w->overlapEnqueue(count, reinterpret_cast<const uint32_t*>(volumesDev), include, ranges2Dev, offsetsDev, reinterpret_cast<uint4*>(hitsDev), capacity, totalDev, false, kOvPassCount | kOvPassWrite, false);
+}
+
+MI_API int mi_world_sweep(mi_world* w, uint32_t count, const mi_query_volume* volumes, const float* displacements3, uint32_t include, const uint32_t* ranges2, mi_sweep_hit* out) {
+    return sweepHost(w, count, volumes, displacements3, include, ranges2, out, false);
+}
+MI_API int mi_debug_sweep_exhaustive(mi_world* w, uint32_t count, const mi_query_volume* volumes, const float* displacements3, uint32_t include, const uint32_t* ranges2, mi_sweep_hit* out) {
+    return sweepHost(w, count, volumes, displacements3, include, ranges2, out, true);
+}
+MI_API int mi_world_sweep_device_async(mi_world* w, uint32_t count, const mi_query_volume* volumesDev, const float* displacements4Dev, uint32_t include, const uint32_t* ranges2Dev,
+                                       mi_sweep_hit* outDev) {
+    if (!w || (count && (!volumesDev || !displacements4Dev || !outDev))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = queryPrepare(w); if (rc != MI_OK) return rc;
+    if (!count) return MI_OK;
+    return w->sweepEnqueue(count, reinterpret_cast<const uint32_t*>(volumesDev), reinterpret_cast<const float4*>(displacements4Dev), include, ranges2Dev, reinterpret_cast<uint4*>(outDev), false);
 }
 
 MI_API int mi_world_volume_contacts(mi_world* w, uint32_t count, const mi_query_volume* volumes, uint32_t include, const uint32_t* ranges2, uint32_t* outOffsets,

@@ -342,6 +342,51 @@ MI_API int mi_debug_overlap_exhaustive(mi_world* world, uint32_t count, const mi
                                        uint32_t capacity, uint32_t* out_total);
 
 /*
+ * Batched shape casts (sweeps): move a volume along a displacement and report the first collider it touches, where, and with what normal
+ * (a character controller's move, a foot or ground probe, a projectile with thickness, a spawn check).  The volumes, their validation (an
+ * invalid one is a miss, never an error), their pose handling (an AABB under a rotation that is not exactly (0,0,0,1) is an OBB), the
+ * include flags, entity_ranges2 and the pose read (physics_transform1, pending edits included) are those of mi_world_overlap; the casts share
+ * the grid of the other queries and change nothing a step computes.  A sharded world returns MI_ERR_UNSUPPORTED.
+ *   - The motion: volume i keeps its orientation and moves from its pose by t * displacement_i, t in [0, 1].  The hit is the smallest t at
+ *     which volume and collider touch; ties go to the lowest world collider index.  Closest hit only; translation only.  A zero
+ *     displacement is valid (it reports an initial overlap or a miss); a non-finite displacement is a miss.
+ *   - A hit: normal is a unit separating direction at the moment of touch, pointing from the collider to the volume (moving the volume
+ *     along it leaves the collider), dot(normal, displacement) <= 0; point lies on the collider's surface; t is a fraction of the
+ *     displacement.  Spheres and capsules are swept as a point / segment with a radius, so their normals are exact and a sphere of radius
+ *     0 is a ray.
+ *   - Initial overlap (the volume touches a collider at its pose): t = 0, MI_SWEEP_INITIAL_OVERLAP is set, normal =
+ *     -normalize(displacement) (0 for a zero displacement), point = the volume's pose position.  For penetration data call
+ *     mi_world_volume_contacts.
+ *   - Termination: the pair test (a GJK-based convex cast) runs at most 32 iterations.  Its t only advances by clips that cannot pass the
+ *     true time of impact, so a pair that reaches the limit reports its current t, a lower bound, with MI_SWEEP_UNCONVERGED: conservative,
+ *     never a silent miss.
+ *   - Not hit: the terrain (MI_QUERY_TERRAIN is accepted and ignored, as by mi_world_overlap; sweeps against the heightmap are out of
+ *     scope) and cloth.  Also out of scope: rotation during the sweep, all-hits and any-hit variants.
+ *   - Result: one record per cast, out[count].
+ */
+typedef struct mi_sweep_hit {   /* 48 bytes, 16-byte aligned rows: usable from the host and as a device buffer */
+    uint32_t entity, collider;  /* MI_RAY_MISS when nothing is hit; collider = world collider index */
+    float t;                    /* fraction of the displacement in [0,1]; +inf on a miss */
+    uint32_t object_type;       /* mi_object_type of the collider; 0 on a miss */
+    float point[3];             /* world space, on the collider's surface (0 on a miss) */
+    uint32_t flags;             /* MI_SWEEP_* */
+    float normal[3];            /* world space, unit, from the collider towards the volume (0 on a miss) */
+    uint32_t volume;            /* index of the cast */
+} mi_sweep_hit;
+enum { MI_SWEEP_INITIAL_OVERLAP = 1, MI_SWEEP_UNCONVERGED = 2 };
+/* displacements3: three floats per cast. */
+MI_API int mi_world_sweep(mi_world* world, uint32_t count, const mi_query_volume* volumes, const float* displacements3,
+                          uint32_t include, const uint32_t* entity_ranges2, mi_sweep_hit* out);
+/* Device buffers (16-byte aligned), only enqueued on the world's stream: no reservation and no host synchronisation.
+ * displacements4_dev: one row of 16 bytes per cast (x, y, z; w is ignored); ranges2_dev may be NULL. */
+MI_API int mi_world_sweep_device_async(mi_world* world, uint32_t count, const mi_query_volume* volumes_dev, const float* displacements4_dev,
+                                       uint32_t include, const uint32_t* ranges2_dev, mi_sweep_hit* out_dev);
+/* The same result from every collider tested against every cast, without the grid, without skipping by the best time so far and from
+ * collider rows computed for the call (the yardstick of the accelerated path): byte for byte equal. */
+MI_API int mi_debug_sweep_exhaustive(mi_world* world, uint32_t count, const mi_query_volume* volumes, const float* displacements3,
+                                     uint32_t include, const uint32_t* entity_ranges2, mi_sweep_hit* out);
+
+/*
  * Batched contact-manifold queries: where a shape touches the world, along which normal and how deep (what PhysX calls
  * computePenetration and Bullet contactTest).  The volumes, their validation (an invalid one yields an empty segment), the include
  * flags, entity_ranges2, the pose read (physics_transform1, pending edits included), the CSR result in ascending world collider index

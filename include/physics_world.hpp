@@ -151,6 +151,28 @@ public:
         countThenFetch(mi_world_overlap, "mi_world_overlap", "overlap", volumes, include, entityRanges, r.offsets, r.hits);
         return r;
     }
+    // The first collider each volume touches when it moves from its pose by t * displacement, t in [0, 1] (mi_world_sweep): one record per volume with t, the
+    // point on the collider and the normal from the collider towards the volume; entity MI_RAY_MISS on a miss; read-only.
+    // entityRanges: empty = the whole scene, otherwise one [lo, hi) pair of entity ids per volume (2 x volumes.size() words)
+    std::vector<mi_sweep_hit> sweep(const std::vector<mi_query_volume>& volumes, const std::vector<vec3>& displacements, uint32_t include = MI_QUERY_DEFAULT,
+                                    const std::vector<uint32_t>& entityRanges = {}) {
+        if (displacements.size() != volumes.size()) throw std::invalid_argument("sweep: one displacement per volume");
+        if (!entityRanges.empty() && entityRanges.size() != 2 * volumes.size()) throw std::invalid_argument("sweep: entityRanges holds one [lo, hi) pair per volume");
+        std::vector<mi_sweep_hit> out(volumes.size());
+        if (!volumes.empty())
+            check(mi_world_sweep(w_, (uint32_t)volumes.size(), volumes.data(), &displacements[0].x, include, entityRanges.empty() ? nullptr : entityRanges.data(), out.data()), "mi_world_sweep");
+        return out;
+    }
+    mi_sweep_hit sweepSphere(vec3 center, float radius, vec3 displacement, uint32_t include = MI_QUERY_DEFAULT) {
+        mi_query_volume v{}; v.type = MI_COLLIDER_SPHERE; v.rotation[3] = 1.f;
+        v.shape[0] = center.x; v.shape[1] = center.y; v.shape[2] = center.z; v.shape[3] = radius;
+        return sweep(std::vector<mi_query_volume>{v}, std::vector<vec3>{displacement}, include)[0];
+    }
+    mi_sweep_hit sweepCapsule(vec3 a, vec3 b, float radius, vec3 displacement, uint32_t include = MI_QUERY_DEFAULT) {
+        mi_query_volume v{}; v.type = MI_COLLIDER_CAPSULE; v.rotation[3] = 1.f;
+        v.shape[0] = a.x; v.shape[1] = a.y; v.shape[2] = a.z; v.shape[3] = b.x; v.shape[4] = b.y; v.shape[5] = b.z; v.shape[6] = radius;
+        return sweep(std::vector<mi_query_volume>{v}, std::vector<vec3>{displacement}, include)[0];
+    }
     // Where each volume touches the world (mi_world_volume_contacts): CSR offsets [volumes + 1] and one manifold per (volume, collider) in ascending
     // collider index; normal from A to B, bit 8 of count_flags set when the volume was B (include/mi_physics.h); read-only.
     struct volume_contacts_result { std::vector<uint32_t> offsets; std::vector<mi_volume_contact> contacts; };
