@@ -19,6 +19,7 @@ namespace mi {
 constexpr uint32_t kSweepMaxIter = 32;        // iterations of the pair test; a pair that reaches it reports its (lower-bound) t with kSweepUnconverged
 constexpr uint32_t kSweepInitialOverlap = 1u, kSweepUnconverged = 2u;   // MI_SWEEP_*
 constexpr float kSweepTolRel = 2e-6f;         // touching = closer than this times the largest coordinate seen (a few float32 ulps of the support points)
+constexpr float kSweepStallTol = 16.f;        // a search that has STALLED (see sweepPair) counts as touching within this many tolerances (stalls of rounding alone measured up to 4)
 constexpr uint32_t kSweepRecordRows = 3;      // mi_sweep_hit: three rows of 16 bytes
 
 // ---- the pair test
@@ -33,7 +34,11 @@ __device__ inline V3 swSupport(const Shape& s, const HullSet& hs, V3 dir) {
         case T_CYLINDER: {
             const V3 ax = s.b - s.a, far = dot(dir, ax) < 0.f ? s.a : s.b;
             const float aa = sqlen(ax);
-            const V3 perp = aa > 0.f ? dir - ax * (dot(dir, ax) / aa) : dir;
+            V3 perp = aa > 0.f ? dir - ax * (dot(dir, ax) / aa) : dir;
+            // once more: under a dir nearly along the axis (a cap flat on something) the short remainder keeps rounding error ALONG the axis of the order
+            // of 1e-7 |dir|, which the scaling to the radius blows up: the "rim" point then lies off the cap's plane by radius x 1e-7 |dir| / |perp|
+            // (measured: a cylinder of radius 6 reported its touch 5.6e-3 past the true one).  The second pass leaves 1e-7 |perp|.
+            if (aa > 0.f) perp = perp - ax * (dot(perp, ax) / aa);
             const float pl = sqlen(perp);
             return pl > 1e-12f * sqlen(dir) ? far + perp * (s.radius / sqrtf(pl)) : far;   // (dir along the axis, or too short to square: the cap's centre)
         }
@@ -162,7 +167,13 @@ __device__ inline Shape swClipBox(const Shape& b, V3 sweptMin, V3 sweptMax) {
 // clipping against support planes of C (every clip is safe: t never passes the true time of impact), and the simplex of C's points closest to x
 // ends the search once x is within R + tolerance of it.  normal: unit, from B towards A; point: on B's surface.
 // Never clipped = the shapes touch at t = 0: kSweepInitialOverlap (normal and point are the caller's).  Out of iterations: the current t with
-// kSweepUnconverged.  The result depends on (A, B, d) alone; one body (not inlined) serves the candidate test and the record writer of both kernels.
+// kSweepUnconverged.  STALLED = an iteration that neither clips nor moves the closest point: its support point is one the simplex holds, or one the
+// simplex takes and drops again (the closest vector comes out bit for bit the same; every further iteration would repeat it).  In exact arithmetic
+// that happens only at distance <= R, so what is left of the distance is rounding: a cast that never clipped stays an initial overlap (no plane
+// separates the shapes; the distance plays no part), any other ends converged within kSweepStallTol tolerances (degenerate touches end here:
+// parallel faces and edges, a cap flat on a face) and with kSweepUnconverged beyond them (measured: a box of 1e-2 on the side of a cylinder of
+// radius 15 stalls 42 tolerances = 2.5e-3 short of the touch, on a thin triangle of far-apart points of the curved side).
+// The result depends on (A, B, d) alone; one body (not inlined) serves the candidate test and the record writer of both kernels.
 __device__ __noinline__ SweepResult sweepPair(const Shape& A, V3 sweptMin, V3 sweptMax, const Shape& collider, const HullSet& hs, V3 d) {
     SweepResult r; r.hit = false; r.t = 0.f; r.flags = 0u;
     const Shape B = swClipBox(collider, sweptMin, sweptMax);
@@ -189,9 +200,11 @@ __device__ __noinline__ SweepResult sweepPair(const Shape& A, V3 sweptMin, V3 sw
         // a support point the simplex already holds brings nothing new: the search has stalled unless this iteration clipped
         const bool dup = (s.n > 0u && p.x == s.y0.x && p.y == s.y0.y && p.z == s.y0.z) || (s.n > 1u && p.x == s.y1.x && p.y == s.y1.y && p.z == s.y1.z) ||
                          (s.n > 2u && p.x == s.y2.x && p.y == s.y2.y && p.z == s.y2.z) || (s.n > 3u && p.x == s.y3.x && p.y == s.y3.y && p.z == s.y3.z);
-        if (dup && !clip) break;
+        const float stallR = R + kSweepStallTol * tol;
+        if (dup && !clip) { done = !clipped || dist2 <= stallR * stallR; break; }
         if (!dup) swPush(s, p, pb);   // (at most three points were kept: a proper tetrahedron ended the search, a flat one kept a face)
         SwWeights w;
+        const V3 before = v;
         const bool outside = swClosest(s.n, x - s.y0, x - s.y1, x - s.y2, x - s.y3, w, v);
         if (!outside) { v = V3(); dist2 = 0.f; done = true; break; }
         witness = s.b0 * w.w0;
@@ -208,6 +221,7 @@ __device__ __noinline__ SweepResult sweepPair(const Shape& A, V3 sweptMin, V3 sw
         s = k;
         dist2 = sqlen(v);
         done = dist2 <= (R + tol) * (R + tol);
+        if (!done && !clip && v.x == before.x && v.y == before.y && v.z == before.z) { done = !clipped || dist2 <= stallR * stallR; break; }   // (took the point and dropped it again)
     }
     r.hit = true; r.t = lambda;
     if (!done) r.flags |= kSweepUnconverged;

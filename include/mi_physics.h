@@ -358,8 +358,14 @@ MI_API int mi_debug_overlap_exhaustive(mi_world* world, uint32_t count, const mi
  *     -normalize(displacement) (0 for a zero displacement), point = the volume's pose position.  For penetration data call
  *     mi_world_volume_contacts.
  *   - Termination: the pair test (a GJK-based convex cast) runs at most 32 iterations.  Its t only advances by clips that cannot pass the
- *     true time of impact, so a pair that reaches the limit reports its current t, a lower bound, with MI_SWEEP_UNCONVERGED: conservative,
- *     never a silent miss.
+ *     true time of impact, so a pair that reaches the limit, or whose search stalls more than 16 distance tolerances (2e-6 x the largest
+ *     coordinate each) from the touch, reports its current t, a lower bound, with MI_SWEEP_UNCONVERGED: conservative, never a silent miss.
+ *     In practice (all 36 volume type x collider type pairs at parallel faces, edges and axes, grazing passes, coordinates up to 1e3,
+ *     sizes from 1e-2 to 200, displacements from 1e-3 to 1e4, starts and ends a hair from the touch): the flag appeared only for a box of
+ *     1e-2 on the curved side of a cylinder of radius 15, with t 1e-4 x the coordinates early and the hit itself right.
+ *   - Accuracy (float32, measured against a float64 reference; "coordinates" = the largest |coordinate| of the cast, at least 1): t times
+ *     the displacement's length is within 5e-6 x coordinates of the true travelled distance (1.1e-4 x in the unconverged case above) and
+ *     passes it by no more than 2e-7 x coordinates; point lies within 1e-7 x coordinates of the collider's surface.
  *   - Not hit: the terrain (MI_QUERY_TERRAIN is accepted and ignored, as by mi_world_overlap; sweeps against the heightmap are out of
  *     scope) and cloth.  Also out of scope: rotation during the sweep, all-hits and any-hit variants.
  *   - Result: one record per cast, out[count].

@@ -5,7 +5,9 @@
   * the DISTANCE between two cores by GJK, whose closest point of a simplex of at most 4 vertices is found by solving every sub-simplex
     (the affine minimiser of each, kept when its weights are non-negative; the nearest of those wins);
   * the TIME OF IMPACT of a volume moved along a displacement by conservative advancement: t += gap / -(d.n) with n the unit direction
-    from the collider to the volume at the current t; a miss when d.n >= 0 or t > 1; a hit once the gap is <= 1e-10;
+    from the collider to the volume at the current t; a miss when d.n >= 0 or t > 1; a hit once the gap is <= 1e-10; with a slack, the
+    cast of the shapes grown or shrunk by it;
+  * the CLOSEST APPROACH of a volume's path to a collider: the gap of the collider and the convex shape the moving volume covers;
   * a cast against a scene: the candidates are culled by the swept bounds (the slab entry time of the displacement into the collider's
     AABB grown by the volume's half-extents, a lower bound of the time of impact) before the pair loop runs;
   * the cast set the tests use.
@@ -20,7 +22,7 @@ import overlap_ref as R
 GAP_EPS = 1e-10
 
 
-# ---- shapes: ("pts", vertices[n, 3], margin) or ("cyl", a, b, radius)
+# ---- shapes: ("pts", vertices[n, 3], margin), ("cyl", a, b, radius) or ("swept", shape, d): everything the shape covers while it moves by d
 def convex(world_shape, hull_vertices=None):
     """The core-plus-margin form of an overlap_ref world shape (type, parameters); hull_vertices = the geometry's local vertices."""
     t, p = world_shape
@@ -45,17 +47,22 @@ def moved(shape, offset):
     offset = np.asarray(offset, np.float64)
     if shape[0] == "pts":
         return ("pts", shape[1] + offset, shape[2])
+    if shape[0] == "swept":
+        return ("swept", moved(shape[1], offset), shape[2])
     return ("cyl", shape[1] + offset, shape[2] + offset, shape[3])
 
 
 def margin(shape):
-    return shape[2] if shape[0] == "pts" else 0.0
+    return shape[2] if shape[0] == "pts" else margin(shape[1]) if shape[0] == "swept" else 0.0
 
 
 def bounds(shape):
     """World AABB of the whole shape (margin included)."""
     if shape[0] == "pts":
         return shape[1].min(axis=0) - shape[2], shape[1].max(axis=0) + shape[2]
+    if shape[0] == "swept":
+        mn, mx = bounds(shape[1])
+        return np.minimum(mn, mn + shape[2]), np.maximum(mx, mx + shape[2])
     a, b, r = shape[1:]
     u = b - a
     n = np.linalg.norm(u)
@@ -67,11 +74,16 @@ def support(shape, direction):
     """The core's support point along `direction`."""
     if shape[0] == "pts":
         return shape[1][int(np.argmax(shape[1] @ direction))]
+    if shape[0] == "swept":
+        p = support(shape[1], direction)
+        return p + shape[2] if direction @ shape[2] > 0 else p
     a, b, r = shape[1:]
     far = a if direction @ a > direction @ b else b
     u = b - a
     n = np.linalg.norm(u)
     perp = direction - (direction @ u) / (n * n) * u if n > 0 else direction
+    if n > 0:
+        perp = perp - (perp @ u) / (n * n) * u   # (once more: under a direction nearly along the axis the short remainder keeps rounding error along the axis, which the scaling to the radius blows up: the rim point would leave the cap's plane)
     ln = np.linalg.norm(perp)
     return far + (r / ln) * perp if ln > 1e-14 * max(np.linalg.norm(direction), 1e-300) else far
 
@@ -139,11 +151,27 @@ def point_gap(point, shape):
     return gap(("pts", np.asarray(point, np.float64).reshape(1, 3), 0.0), shape)
 
 
-def time_of_impact(vol, col, d, max_steps=256):
+def closest_approach(vol, col, d):
+    """The smallest gap between `col` and `vol` anywhere on its way along d, t in [0, 1]: the gap of the collider and everything the moving
+    volume covers (a convex shape again), so one distance query and no search over t.  0 or below (as far as the margins reach): a hit."""
+    return gap(("swept", vol, np.asarray(d, np.float64)), col)
+
+
+def time_of_impact(vol, col, d, max_steps=256, slack=0.0, plain=None):
     """Conservative advancement of `vol` along d against `col`: None on a miss, else (t, unit normal from col to vol, point on col,
-    initial overlap).  t in [0, 1]."""
+    initial overlap).  t in [0, 1].  slack is added to the sum of the margins: the cast of shapes grown (slack > 0) or shrunk (slack < 0) by
+    that much between them.  Where the margins cannot be shrunk that far (boxes, hulls and cylinders have none; the core distance does
+    not measure a depth), the shrunk cast is the plain one required to travel on past its touch until it is -slack deep along the
+    touch's normal: exact while the touching features stay the same (flat contacts), an upper bound of the depth elsewhere.  plain = the
+    result of the plain cast (slack 0) where the caller has it, not to compute it again."""
     d = np.asarray(d, np.float64)
-    rr = margin(vol) + margin(col)
+    rr = margin(vol) + margin(col) + slack
+    if rr < 0:
+        hit = plain if plain is not None else time_of_impact(vol, col, d, max_steps)
+        if hit is None or hit[3]:
+            return hit
+        t = hit[0] + rr / (d @ hit[1])   # (d.n < 0 at a hit)
+        return (t, *hit[1:]) if t <= 1 else None
     t = 0.0
     last = np.zeros(3)
     for step in range(max_steps):

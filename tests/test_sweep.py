@@ -1,5 +1,6 @@
 """Shape-cast scene queries without a GPU: the ABI (header, exports, the record's layout), the float64 yardstick of tests/sweep_ref.py
-against closed forms, and the conditions the GPU tests' cast set has to meet — all computed by the reference alone."""
+against closed forms, and the conditions the GPU tests' cast set and pair-level matrix (tests/sweep_matrix.py) have to meet — all computed
+by the reference alone."""
 import re
 from pathlib import Path
 
@@ -7,6 +8,7 @@ import numpy as np
 import pytest
 
 import overlap_ref as R
+import sweep_matrix as M
 import sweep_ref as S
 from overlap_ref import AABB, CAPSULE, CYLINDER, HULL, OBB, SPHERE
 
@@ -130,3 +132,122 @@ def test_cast_set_is_a_valid_yardstick(seed):
     assert len(hits) >= 0.9 * n
     assert not any(h[4] for h in hits)
     assert min(ref["leads"]) >= 1e-2
+
+
+# ---- the pair-level matrix (tests/sweep_matrix.py)
+@pytest.mark.parametrize("name", M.BASE_FAMILIES)
+def test_matrix_family_is_a_valid_yardstick(name):
+    """What the GPU comparison of a family relies on, from the reference alone: all 36 pairs survive the robustness filter (the decision is the
+    same with the shapes shrunk and grown by delta = 4 x the family's bound x scale; no hit starts within delta) with at least 2 cases each,
+    at most 10 % of the generated cases are filtered out, and the family holds the hits and misses it is meant to."""
+    cases = M.family(name)
+    table = M.counts(cases)
+    n, kept = len(cases), [c for c in cases if c["kept"]]
+    hits = sum(c["ref"] is not None for c in kept)
+    print(f"{name}: {n} cases, {n - len(kept)} filtered out ({100.0 * (n - len(kept)) / n:.1f} %), {hits} hits and {len(kept) - hits} misses kept, "
+          f"scale up to {max(c['scale'] for c in cases):.3g}, delta {min(M.delta(c) for c in cases):.2e} .. {max(M.delta(c) for c in cases):.2e}")
+    for vt in range(6):
+        print(f"  {M.TYPES[vt]:>8} ->  " + "  ".join(f"{M.TYPES[ct]} {table[(vt, ct)][1]}/{table[(vt, ct)][0]} ({table[(vt, ct)][2]} hit)" for ct in range(6)))
+    assert set(table) == set(M.PAIRS) and all(m[0] >= 3 for m in table.values()), "a pair has fewer than 3 samples"
+    assert all(m[1] >= 2 for m in table.values()), [p for p, m in table.items() if m[1] < 2]
+    assert n - len(kept) <= 0.1 * n
+    assert not any(c["ref"][3] for c in kept if c["ref"] is not None)
+    if name == "grazing":
+        assert 0.4 * len(kept) <= hits <= 0.6 * len(kept)
+        for c in kept:   # the closest approach is where the family puts it: k delta clear, or a hit that the cast shrunk by delta still makes
+            k = int(c["tag"][1:].rstrip("hitms"))
+            assert (c["ref"] is None) == c["tag"].endswith("miss"), c["tag"]
+            if c["ref"] is None:
+                assert abs(S.closest_approach(c["vconv"], c["cconv"], c["d"]) - k * M.delta(c)) <= 0.05 * M.delta(c), c["tag"]
+    else:
+        assert hits >= 0.8 * len(kept)
+    if name == "far":
+        assert min(c["scale"] for c in cases) >= 90 and max(c["scale"] for c in cases) >= 900
+    if name == "displacement":
+        lengths = sorted(set(float(np.linalg.norm(c["d"])) for c in kept))
+        ts = [c["ref"][0] for c in kept if c["ref"] is not None]
+        assert lengths[0] <= 1.1e-3 and lengths[-1] >= 0.9e4 and min(ts) <= 0.02 and max(ts) >= 0.98 and any(0.3 <= t <= 0.7 for t in ts)
+
+
+def _point_cylinder_distance(p, a, b, r):
+    """Distance of a point outside a solid cylinder (axis a..b, radius r) from it."""
+    u = (b - a) / np.linalg.norm(b - a)
+    h = (p - (a + b) / 2) @ u
+    rho = np.linalg.norm(p - (a + b) / 2 - h * u)
+    return float(np.hypot(max(rho - r, 0.0), max(abs(h) - np.linalg.norm(b - a) / 2, 0.0)))
+
+
+def test_matrix_reference_equals_the_closed_forms():
+    """Where a closed form exists the reference agrees with it to 1e-9 in travelled distance, on the rounded float32 inputs both see:
+      * aligned k 0 (centred, exactly along -y, flat or round onto flat: box / cylinder cap / capsule side / sphere onto a box face or a
+        cylinder cap) travels the gap of the two bounds along y;
+      * two axis-aligned boxes (AABB on AABB in generic and in aligned k 0, 1, 2: face on face, edge onto the parallel edge along the face
+        diagonal, half-overlapping faces; with the OBBs of aligned k 0, whose half turn is exact in float32) touch when the displacement
+        enters the collider grown by the volume's half-extents: the slab test;
+      * a sphere against a sphere, capsule or AABB (generic and aligned), against the exactly turned OBB of aligned k 0 and against a
+        cylinder ends at gap 0 (overlap_ref.signed_gap; the point-cylinder distance above).
+    Not compared: a sphere against the other OBBs (overlap_ref.qmat of a rounded quaternion is orthonormal to 1e-7 only and signed_gap
+    measures in that skewed frame: 1e-6, test_gap_equals_the_closed_forms), against a hull (no closed form short of another polytope
+    distance algorithm), and the quarter-turned OBBs of aligned k 1 and 2 (their faces are tilted by 6e-8)."""
+    worst = [0.0, 0.0, 0.0]; seen = [0, 0, 0]
+    for c in M.family("aligned"):
+        flat_below = c["ct"] in (AABB, OBB) or (c["ct"] == CYLINDER and c["vt"] in (CYLINDER, AABB, OBB))
+        if c["tag"] == "s0" and c["vt"] != HULL and flat_below:
+            want = S.bounds(c["vconv"])[0][1] - S.bounds(c["cconv"])[1][1]
+            worst[0] = max(worst[0], abs(c["ref"][0] * np.linalg.norm(c["d"]) - want)); seen[0] += 1
+    for c in M.family("generic") + M.family("aligned"):
+        boxes = (AABB,) if c["family"] == "generic" or c["tag"] != "s0" else (AABB, OBB)
+        if c["vt"] in boxes and c["ct"] in boxes:
+            (vmn, vmx), (cmn, cmx) = S.bounds(c["vconv"]), S.bounds(c["cconv"])
+            want = S.slab_entry(cmn, cmx, (vmx - vmn) / 2, (vmn + vmx) / 2, c["d"])
+            assert want is not None and c["ref"] is not None, (c["family"], c["tag"])
+            worst[2] = max(worst[2], abs(c["ref"][0] - want) * np.linalg.norm(c["d"])); seen[2] += 1
+        exact_obb = c["ct"] == OBB and c["family"] == "aligned" and c["tag"] == "s0"
+        if c["vt"] == SPHERE and (c["ct"] in (SPHERE, CAPSULE, CYLINDER, AABB) or exact_obb) and c["ref"] is not None:
+            t, n = c["ref"][0], c["ref"][1]
+            v = c["volume"][0].copy(); v["position"] = 0
+            ws = R.volume_world_shape(v)
+            ws = (ws[0], (ws[1][0] + c["volume"]["position"][0].astype(np.float64) + t * c["d"], ws[1][1]))
+            cw = R.world_shape(c["col_type"], c["col_words"], c["col_pos"], c["col_rot"])
+            gap = _point_cylinder_distance(ws[1][0], *cw[1]) - ws[1][1] if c["ct"] == CYLINDER else R.signed_gap(ws, cw)
+            d_hat = c["d"] / np.linalg.norm(c["d"])
+            worst[1] = max(worst[1], abs(gap) / -(d_hat @ n)); seen[1] += 1
+    print(f"aligned flat contacts: {seen[0]} cases, largest |travel - bounds gap| {worst[0]:.2e}; box on box: {seen[2]} cases, largest |travel - slab entry| {worst[2]:.2e}; "
+          f"sphere casts: {seen[1]} cases, largest |gap at the hit| / |d.n| {worst[1]:.2e}")
+    assert seen[0] >= 12 and seen[1] >= 25 and seen[2] >= 9
+    assert max(worst) <= 1e-9
+
+
+def test_matrix_derived_families():
+    """The derived families rescale kept hits in closed form; what they expect follows from the base case's reference time alone."""
+    base = sum(c["ref"] is not None for c in M.kept("generic") + M.kept("aligned"))
+    for name in ("starts_just_clear", "starts_just_inside", "ends_just_short", "just_reaches"):
+        cases = M.derived(name)
+        assert len(cases) == base and set((c["vt"], c["ct"]) for c in cases) == set(M.PAIRS)
+    far = sum(c["ref"] is not None for c in M.kept("far"))
+    for name in [f for f in M.DERIVED_FAMILIES if f.startswith("far_")]:
+        cases = M.derived(name)
+        assert len(cases) == far and set((c["vt"], c["ct"]) for c in cases) == set(M.PAIRS) and min(c["scale"] for c in cases) >= 90
+    rays = M.derived("zero_radius")
+    print(f"derived: {base} cases per family, {len(rays)} zero-radius spheres ({sum(c['kept'] for c in rays)} kept)")
+    assert set(c["ct"] for c in rays if c["kept"]) == set(range(6)) and all(c["volume"]["shape"][0, 3] == 0 for c in rays)
+    # a sample: the rescaling against the reference itself, to the rounding of the moved start to float32 (3e-7 x its coordinates)
+    for c in M.derived("just_reaches")[:12] + M.derived("starts_just_clear")[:12] + M.derived("far_starts_just_clear")[:12]:
+        hit = S.time_of_impact(c["vconv"], c["cconv"], c["d"])
+        assert hit is not None and not hit[3] and abs(hit[0] - c["expect"]) * np.linalg.norm(c["d"]) <= 1e-5 * max(1.0, c["scale"] / 30), (c["family"], c["tag"], hit[0], c["expect"])
+    for c in M.derived("ends_just_short")[:12]:
+        assert S.time_of_impact(c["vconv"], c["cconv"], c["d"]) is None
+    for c in M.derived("starts_just_inside")[:12] + M.derived("far_starts_just_inside")[:12]:
+        assert S.time_of_impact(c["vconv"], c["cconv"], c["d"])[3]
+
+
+def test_slack_and_closest_approach_equal_the_closed_forms():
+    a, b = _shape(SPHERE, [-5, 0.3, 0, 0.25]), _shape(SPHERE, [0, 0, 0, 0.5])
+    assert abs(S.closest_approach(a, b, (8, 0, 0)) - (0.3 - 0.75)) <= 1e-12 and abs(S.closest_approach(a, b, (2, 0, 0)) - (np.hypot(3, 0.3) - 0.75)) <= 1e-12
+    for slack in (-0.1, 0.1):
+        t = S.time_of_impact(a, b, (8, 0, 0), slack=slack)[0]
+        assert abs(t * 8 - (5 - np.sqrt((0.75 + slack) ** 2 - 0.3 ** 2))) <= 1e-9
+    box, small = _shape(AABB, [-1, -1, -1, 1, 1, 1], (10, 0, 0)), _shape(AABB, [-0.5, -0.5, -0.5, 0.5, 0.5, 0.5], (5, 0.2, 0.1))
+    assert abs(S.closest_approach(small, box, (2, 0, 0)) - 1.5) <= 1e-12
+    assert abs(S.time_of_impact(small, box, (6, 0, 0), slack=-0.25)[0] * 6 - 3.75) <= 1e-9    # without a margin: 0.25 deep along the touch's normal
+    assert S.time_of_impact(small, box, (3.6, 0, 0), slack=-0.25) is None and S.time_of_impact(small, box, (3.4, 0, 0), slack=0.25) is not None
