@@ -189,23 +189,89 @@ __device__ __forceinline__ void qPose(const QueryScene& s, uint32_t k, uint32_t 
     if (body != kNoBody) { pos = xyz(s.bPos[body]); rot = toQ(s.bRot[body]); }
     else { pos = xyz(s.cStaticPos[k]); rot = toQ(s.cStaticRot[k]); }
 }
-// rayVsCollider with t in the units of any direction: the reference's sphere test (raySphere; a sphere, a capsule's end spheres) assumes
-// |d| = 1, so it runs on d / |d| and its t is divided by |d|; every other test is already written for any length.  A direction whose length
-// rounds to exactly 1 takes rayVsCollider's arithmetic unchanged (so unit rays see the t mi_world_test_interactions sees).
-__device__ inline bool qRayVsCollider(uint32_t type, float4 s0, float4 s1, float4 s2, const HullFaces& hf, V3 o, V3 d, float& t) {
-    if (type != T_SPHERE && type != T_CAPSULE) return rayVsCollider(type, s0, s1, s2, hf, o, d, t);
-    const float l = len(d);
-    if (l == 1.f) return rayVsCollider(type, s0, s1, s2, hf, o, d, t);
-    const V3 u = d * (1.f / l);
-    float tt;
-    if (type == T_SPHERE) { if (!raySphere(o, u, xyz(s0), s0.w, tt)) return false; t = tt / l; return true; }
-    const V3 pa = xyz(s0), pb(s0.w, s1.x, s1.y); const float r = s1.z;   // capsule: the same three tests and minimum as rayVsCollider
-    t = FLT_MAX;
-    bool result = false;
-    if (rayCylinder(o, d, pa, pb, r, tt)) { t = tt; result = true; }
-    if (raySphere(o, u, pa, r, tt)) { t = fminr(t, tt / l); result = true; }
-    if (raySphere(o, u, pb, r, tt)) { t = fminr(t, tt / l); result = true; }
+// rayVsCollider with t in the units of any direction.  Only the slab test of the boxes is homogeneous in d; the reference's other tests are
+// written for |d| = 1: raySphere outright, rayCylinder through its absolute epsilons (delta = b^2 - a c scales with |d|^2 r^2, `t <= epsilon`
+// is a distance only for a unit ray), rayPlane and rayTriangle through `|dot(d, n)| < 1e-6`.  So spheres, capsules, cylinders and hulls run
+// on d / |d| and their t is divided by |d|.  A direction whose length rounds to exactly 1 takes rayVsCollider's arithmetic unchanged (so unit
+// rays see the t mi_world_test_interactions sees).
+__device__ __forceinline__ V3 qUnitDirection(V3 d, float& l) { l = len(d); return l == 1.f ? d : d * (1.f / l); }
+// rayTriangle with the plane's normal normalised whatever its length: the reference's noz() returns the zero vector for a cross product
+// shorter than 1e-4, so a triangle with edges under about 1e-2 was invisible to every ray.  The same arithmetic, hence the same t, for
+// every triangle rayTriangle sees.
+__device__ inline bool qRayTriangle(V3 o, V3 d, V3 a, V3 b, V3 c, float& t) {
+    const V3 cr = cross(b - a, c - a);
+    const float sl = sqlen(cr);
+    if (!(sl > 0.f)) return false;
+    const V3 normal = cr * (1.f / sqrtf(sl));
+    const float pd = -dot(normal, a), nDotR = dot(d, normal);
+    if (fabsf(nDotR) <= 1e-6f) return false;
+    t = -(dot(o, normal) + pd) / nDotR;
+    return t >= 0.f && pointInTriangle(o + t * d, a, b, c);
+}
+// the hull loop of rayVsCollider over qRayTriangle: the first triangle with the smallest t, and its (unnormalised) outward normal in the hull's frame
+__device__ inline bool qRayHull(float4 s0, float4 s1, const HullFaces& hf, V3 o, V3 d, float& t, V3& n) {
+    const Q4 inv = conj(Q4(s0.x, s0.y, s0.z, s0.w)); const V3 pos(s1.x, s1.y, s1.z);
+    const uint32_t geom = __float_as_uint(s1.w);
+    const V3 lo = rotate(inv, o - pos), ld = rotate(inv, d);
+    const uint32_t v0 = hf.ranges[2 * geom], f0 = hf.triRanges[2 * geom], nf = hf.triRanges[2 * geom + 1];
+    float minT = FLT_MAX; bool result = false;
+    for (uint32_t f = 0; f < nf; ++f) {
+        float tt;
+        const V3 a = xyz(hf.verts[v0 + hf.tris[3 * (f0 + f)]]), b = xyz(hf.verts[v0 + hf.tris[3 * (f0 + f) + 1]]), c = xyz(hf.verts[v0 + hf.tris[3 * (f0 + f) + 2]]);
+        if (qRayTriangle(lo, ld, a, b, c, tt) && tt < minT) { minT = tt; n = cross(b - a, c - a); result = true; }
+    }
+    t = minT;
     return result;
+}
+// rayCylinder once more for a ray it missed, its comparisons of lengths (the side hit's height against [0, height], the cap hit's distance from
+// the axis against the radius) widened from the absolute 1e-6 to `tol`, a few float32 roundings of the coordinates involved: at coordinates
+// of about 1 a ray aimed exactly at the rim otherwise passes between side and cap, and the cap of a cylinder tens of units long is missed
+// whenever o.y + t d.y rounds above height + 1e-6.  The thresholds on delta and on t stay.
+__device__ inline bool qRayCylinderWidened(V3 o, V3 d, V3 pa, V3 pb, float radius, float tol, float& t) {
+    const V3 axis = pb - pa;
+    const float height = len(axis);
+    const Q4 q = rotateFromTo(axis, V3(0.f, 1.f, 0.f));
+    o = rotate(q, o - pa); d = rotate(q, d);
+    const float epsilon = 1e-6f;
+    float y = -1.f - tol;
+    t = 0.f;
+    if (o.x * o.x + o.z * o.z > radius * radius) {
+        const float a = d.x * d.x + d.z * d.z, b = d.x * o.x + d.z * o.z, c = o.x * o.x + o.z * o.z - radius * radius;
+        const float delta = b * b - a * c;
+        if (delta < epsilon) return false;
+        t = (-b - sqrtf(delta)) / a;
+        if (t <= epsilon) return false;
+        y = o.y + t * d.y;
+    }
+    if (y > height + tol || y < -tol) {
+        float dist;
+        if (d.y < 0.f && rayPlane(o, d, V3(0.f, 1.f, 0.f), -height, dist) && len(o + dist * d - V3(0.f, height, 0.f)) <= radius + tol) t = dist;
+        if (d.y > 0.f && rayPlane(o, d, V3(0.f, -1.f, 0.f), 0.f, dist) && len(o + dist * d) <= radius + tol) t = dist;
+        y = o.y + t * d.y;
+    }
+    return y > -tol && y < height + tol;
+}
+// Round shapes, in two steps the reference does not take.  (1) An origin more than 32 bounding radii in front of the shape is first moved
+// along the ray to the shape's bounding sphere: the quadratics subtract r^2 from |o - c|^2, and from 20 units a collider of 1e-2 was hit 5e-3
+// early or late, or missed.  (2) A cylinder the reference's test misses is tried once more with widened comparisons (above).  A unit ray that
+// starts within 32 radii and that the reference's test hits sees rayVsCollider's arithmetic unchanged, to the byte.
+__device__ inline bool qRayVsCollider(uint32_t type, float4 s0, float4 s1, float4 s2, const HullFaces& hf, V3 o, V3 d, float& t) {
+    if (type == T_AABB || type == T_OBB) return rayVsCollider(type, s0, s1, s2, hf, o, d, t);
+    float l;
+    const V3 u = qUnitDirection(d, l);
+    if (type == T_HULL) { V3 n; float tt; if (!qRayHull(s0, s1, hf, o, u, tt, n)) return false; t = l == 1.f ? tt : tt / l; return true; }
+    V3 centre = xyz(s0); float bound = s0.w;
+    if (type != T_SPHERE) { const V3 pb(s0.w, s1.x, s1.y); centre = 0.5f * (centre + pb); bound = 0.5f * len(pb - xyz(s0)) + s1.z; }
+    const float ahead = dot(centre - o, u) - bound;
+    const bool far = bound > 0.f && ahead > 32.f * bound;
+    const V3 start = far ? o + ahead * u : o;
+    float tt;
+    bool hit = rayVsCollider(type, s0, s1, s2, hf, start, u, tt);
+    if (!hit && type == T_CYLINDER) hit = qRayCylinderWidened(start, u, xyz(s0), V3(s0.w, s1.x, s1.y), s1.z, 2e-6f * (1.f + bound + len(start - centre)), tt);
+    if (!hit) return false;
+    if (far) tt += ahead;
+    t = l == 1.f ? tt : tt / l;
+    return true;
 }
 // collider k against the ray in its entity's frame (qRayVsCollider; rayVsCollider, as mi_world_test_interactions, for unit rays): key = t bits << 32 | k, or ~0
 __device__ __forceinline__ unsigned long long qTestCollider(const QueryScene& s, const QueryRay& q, uint32_t k) {
@@ -335,18 +401,12 @@ __device__ inline V3 qLocalNormal(uint32_t type, float4 s0, float4 s1, float4 s2
             const Q4 q(s0.x, s0.y, s0.z, s0.w), inv = conj(q); const V3 c(s1.x, s1.y, s1.z), r(s1.w, s2.x, s2.y);
             return rotate(q, qBoxNormal(rotate(inv, o - c), rotate(inv, d), V3() - r, V3() + r));
         }
-        default: {   // the hit triangle, found as rayVsCollider finds it
-            const Q4 q(s0.x, s0.y, s0.z, s0.w), inv = conj(q); const V3 pos(s1.x, s1.y, s1.z);
-            const uint32_t geom = __float_as_uint(s1.w);
-            const V3 lo = rotate(inv, o - pos), ld = rotate(inv, d);
-            const uint32_t v0 = hf.ranges[2 * geom], f0 = hf.triRanges[2 * geom], nf = hf.triRanges[2 * geom + 1];
-            float minT = FLT_MAX; V3 n;
-            for (uint32_t f = 0; f < nf; ++f) {
-                float tt;
-                const V3 a = xyz(hf.verts[v0 + hf.tris[3 * (f0 + f)]]), b = xyz(hf.verts[v0 + hf.tris[3 * (f0 + f) + 1]]), c = xyz(hf.verts[v0 + hf.tris[3 * (f0 + f) + 2]]);
-                if (rayTriangle(lo, ld, a, b, c, tt) && tt < minT) { minT = tt; n = cross(b - a, c - a); }
-            }
-            return rotate(q, n);
+        default: {   // the hit triangle, found as qRayVsCollider found it: the same unit direction, so the same triangle wins
+            float l, tt; V3 n;
+            qRayHull(s0, s1, hf, o, qUnitDirection(d, l), tt, n);
+            const float sl = sqlen(n);
+            if (sl > 0.f && sl < 1e-8f) n = n * (1.f / sqrtf(sl));   // (qFinalise's noz() would take the normal of a small triangle for zero)
+            return rotate(Q4(s0.x, s0.y, s0.z, s0.w), n);
         }
     }
 }

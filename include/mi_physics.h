@@ -256,8 +256,25 @@ MI_API int mi_world_test_interactions(mi_world* world, uint32_t count, const flo
  *     runs), quirks included: a sphere that contains the origin reports t = 0 (a capsule too, unless its cylinder part answers first);
  *     a box (AABB / OBB) seen from inside reports no hit; the cylinder test (also the capsule's middle) can answer with a cap
  *     BEHIND the origin, and such a negative t is no hit (as any negative or non-finite t; mi_world_test_interactions still
- *     pushes a body whose only candidate is such a cap).  The reference's sphere test assumes a unit direction: here it runs on
- *     direction / |direction| and its t is rescaled, so t is in the direction's units for every shape.
+ *     pushes a body whose only candidate is such a cap).  Seen from inside, a cylinder (and the middle of a capsule) finds that cap
+ *     behind the origin, so no hit, for every direction with a part along the axis, and reports t = 0 for one exactly perpendicular
+ *     to it; a hull seen from inside reports the triangle the ray LEAVES through: t > 0 and that triangle's outward normal, the one
+ *     answer with dot(normal, direction) > 0 (the reference's triangle test does not cull back faces).
+ *   - Direction length: only the boxes' slab test is independent of |direction|.  The reference's sphere test assumes a unit
+ *     direction outright, its cylinder, cap-plane and triangle tests through absolute epsilons (1e-6 against b^2 - a c, against t and
+ *     against dot(direction, normal)), so for spheres, capsules, cylinders and hulls the test runs on direction / |direction| and its t
+ *     is rescaled: t is in the direction's units for every shape, and a ray hits the same point whatever its direction's length (tested
+ *     from 1e-3 to 1e4).  A direction of length exactly 1 takes the reference's arithmetic unchanged.
+ *   - Three deviations from the reference, each only where its test answers wrongly: a hull triangle whose edge cross product is shorter
+ *     than 1e-4 (edges under about 1e-2), which the reference's noz() gives a zero normal and so never hits, is hit; an origin more than 32
+ *     bounding radii in front of a sphere, capsule or cylinder is first moved along the ray to the shape's bounding sphere (the quadratics
+ *     subtract r^2 from |origin - centre|^2 in float32: from 20 units a collider of 1e-2 was hit 5e-3 off, or missed); a cylinder the
+ *     reference's test misses is tried once more with its comparisons of lengths widened from an absolute 1e-6 to a few float32 roundings of
+ *     the coordinates (a ray aimed exactly at the rim passed between side and cap; the cap of a cylinder tens of units long was missed).
+ *     A unit ray that starts within 32 radii and that the reference's test hits gets the reference's t, to the bit.
+ *   - Limits that remain: t is good to about 5e-6 x the largest coordinate for round shapes (2e-5 from 6 units), 2e-7 x for boxes and
+ *     hulls; a capsule or cylinder whose axis lies within 1e-3 rad of -y is placed about 1e-4 rad off (rotateFromTo next to its half turn);
+ *     a cylinder's side of radius r stays invisible where r^2 - (distance from the axis)^2 < 1e-6.
  *   - The terrain: the heightmap's collision triangles (two per cell, as heightmap contacts use them; not the bilinear
  *     mi_heightmap_get_height surface, which they meet at the grid vertices and edges); chunks without heights are holes.
  *   - Closest hit = smallest t; ties go to the lowest world collider index; a collider wins a tie against the terrain.  A hit

@@ -66,14 +66,16 @@ def _frame_to_y(axis):
     return np.eye(3) + vx + vx @ vx * (1.0 / (1.0 + c))
 
 
-def ray_cylinder(o, d, pa, pb, r):
+def ray_cylinder(o, d, pa, pb, r, tol=None):
+    """tol None: the reference's test; tol (N,): the query's second try of a missed cylinder, the comparisons of lengths widened to tol."""
     axis = pb - pa
     h = np.linalg.norm(axis)
     R = _frame_to_y(axis)
     o = (o - pa) @ R.T
     d = d @ R.T
     eps = 1e-6
-    y = np.full(len(o), -1.0)
+    wide = np.full(len(o), eps) if tol is None else tol
+    y = -1.0 - (0.0 if tol is None else tol)
     t = np.zeros(len(o))
     alive = np.ones(len(o), bool)
     outside = o[:, 0] ** 2 + o[:, 2] ** 2 > r * r
@@ -86,17 +88,17 @@ def ray_cylinder(o, d, pa, pb, r):
     alive &= ~(outside & ((delta < eps) | ~(ts > eps)))
     t = np.where(outside, ts, t)
     y = np.where(outside, o[:, 1] + t * d[:, 1], y)
-    caps = (y > h + eps) | (y < -eps)
+    caps = (y > h + wide) | (y < -wide)
     with np.errstate(divide="ignore", invalid="ignore"):
         for plane_y, sign, cond in ((h, 1.0, d[:, 1] < 0), (0.0, -1.0, d[:, 1] > 0)):
             nd = d[:, 1] * sign
             ok = np.abs(nd) >= 1e-6
             dist = -((o[:, 1] * sign) - plane_y * sign) / nd
             q = o + dist[:, None] * d
-            ok &= np.hypot(q[:, 0], q[:, 2]) ** 2 + (q[:, 1] - plane_y) ** 2 <= r * r
+            ok &= (np.hypot(q[:, 0], q[:, 2]) ** 2 + (q[:, 1] - plane_y) ** 2 <= r * r) if tol is None else (np.sqrt(q[:, 0] ** 2 + q[:, 2] ** 2 + (q[:, 1] - plane_y) ** 2) <= r + tol)
             t = np.where(caps & cond & ok, dist, t)
     y = np.where(caps, o[:, 1] + t * d[:, 1], y)
-    hit = alive & (y > -eps) & (y < h + eps)
+    hit = alive & (y > -wide) & (y < h + wide)
     return np.where(hit, t, INF)
 
 
@@ -153,14 +155,23 @@ def collider_t_and_normal(ctype, shape, hull, o, d):
     """Collider in its entity's frame: t (N,) and the local outward normal (N, 3) at the hit (undefined on a miss)."""
     s = np.asarray(shape, np.float64)
     L = np.linalg.norm(d, axis=1)
-    u = d / np.where(L > 0, L, 1.0)[:, None]   # the sphere test assumes a unit direction: it runs on d / |d|, t rescaled
+    u = d / np.where(L > 0, L, 1.0)[:, None]   # every test but the boxes' slabs assumes a unit direction: it runs on d / |d|, t rescaled
+    if ctype in (SPHERE, CAPSULE, CYLINDER):   # an origin more than 32 bounding radii in front of the shape starts at its bounding sphere
+        centre, bound = (s[:3], s[3]) if ctype == SPHERE else ((s[:3] + s[3:6]) / 2, np.linalg.norm(s[3:6] - s[:3]) / 2 + s[6])
+        ahead = _dot(centre - o, u) - bound
+        ahead = np.where((bound > 0) & (ahead > 32 * bound), ahead, 0.0)
+        start = o + ahead[:, None] * u
     if ctype == SPHERE:
-        t = ray_sphere(o, u, s[:3], s[3]) / L
+        t = (ray_sphere(start, u, s[:3], s[3]) + ahead) / L
         n = o + np.where(np.isfinite(t), t, 0)[:, None] * d - s[:3]
     elif ctype in (CAPSULE, CYLINDER):
         pa, pb, r = s[:3], s[3:6], s[6]
-        t = np.minimum(ray_cylinder(o, d, pa, pb, r), np.minimum(ray_sphere(o, u, pa, r), ray_sphere(o, u, pb, r)) / L) if ctype == CAPSULE \
-            else ray_cylinder(o, d, pa, pb, r)
+        if ctype == CAPSULE:
+            t = np.minimum(ray_cylinder(start, u, pa, pb, r), np.minimum(ray_sphere(start, u, pa, r), ray_sphere(start, u, pb, r)))
+        else:   # a missed cylinder is tried once more with widened comparisons
+            t = ray_cylinder(start, u, pa, pb, r)
+            t = np.where(np.isfinite(t), t, ray_cylinder(start, u, pa, pb, r, 2e-6 * (1 + bound + np.linalg.norm(start - centre, axis=1))))
+        t = (t + ahead) / L
         h = o + np.where(np.isfinite(t), t, 0)[:, None] * d
         ab = pb - pa
         if ctype == CAPSULE:
@@ -183,11 +194,11 @@ def collider_t_and_normal(ctype, shape, hull, o, d):
     else:
         q, p = s[:4], s[4:7]
         verts, tris = hull
-        lo, ld = qrot(qconj(q), o - p), qrot(qconj(q), d)
+        lo, lu = qrot(qconj(q), o - p), qrot(qconj(q), u)
         a, b, c = (np.asarray(verts, np.float64)[np.asarray(tris)[:, i]] for i in range(3))
-        tt = ray_triangles(lo, ld, a, b, c)
+        tt = ray_triangles(lo, lu, a, b, c)
         j = np.argmin(tt, axis=1)
-        t = tt[np.arange(len(o)), j]
+        t = tt[np.arange(len(o)), j] / L
         n = qrot(q, np.cross(b - a, c - a)[j])
     t = np.where((t >= 0) & np.isfinite(t), t, INF)
     return t, n

@@ -325,3 +325,109 @@ def test_errors(mi_lib):
     w.shard_enable(sharding._desc_for(sharding.tile_grid(sc, 1), 0))
     assert f(w.h, C.c_uint32(1), p(v), p(v), None, C.c_uint32(7), None, p(out)) == -6
     w.close()
+
+
+# ---- the matrix: every collider type at its hard rays, one collider at a time, against the exact float64 reference (tests/raycast_matrix.py)
+import raycast_exact as X   # noqa: E402
+import raycast_matrix as M   # noqa: E402
+
+MISS = 0xFFFFFFFF
+
+
+def _who(name, i, c):
+    return f"{name}[{i}] {M.KINDS[c['kind']]} {c['tag']} (scale {c['scale']:.3g}, |d| {np.linalg.norm(c['d']):.3g})"
+
+
+def _is_miss_record(rec):
+    return (rec["entity"] == MISS and rec["collider"] == MISS and np.isposinf(rec["t"]) and not rec["point"].any() and not rec["normal"].any()
+            and rec["object_type"] == 0)
+
+
+# The one place of the matrix with a figure of its own: a capsule / cylinder whose axis lies 1e-3 rad off -y, hit on its side.  The cylinder
+# test turns the ray into the cylinder's frame by rotateFromTo(axis, +y), and next to that function's half-turn branch s = sqrt(2 (1 + d)) is
+# taken of 1 + d = 5e-7, a float32 difference good to one part in ten: the frame is off by about 1e-4 rad, the side by that times the ray's
+# lever.  Measured per unit of scale: capsule 8.2e-5, cylinder 6.8e-5 (their end rays and the axes 1e-2 rad off -y stay within the family's
+# bound).  It is the reference's arithmetic (rayVsCollider), kept for unit rays.  Held to 4 x their own figure; they do not set the family's bound.
+KNOWN_ILL_CONDITIONED = {("axes", 1, "-y+1e-3_side"): 4e-4, ("axes", 2, "-y+1e-3_side"): 3e-4}
+
+
+def _check_matrix(name, cases, ranges, got):
+    """Every record against the exact reference's answer of its case, all measures per unit of the case's scale; returns the failures and
+    prints the worst values per collider type: |dt| |d|, the point off o + t d, the point off the collider's surface, the separation short of
+    0.05 scale after backing off along the normal (one admissible normal only), and |n - the nearest admissible normal| (x the radius of a
+    round shape)."""
+    bad, worst = [], {}
+    nc = int(ranges[-1, 1])
+    for i, c in enumerate(cases):
+        rec, ref, who = got[i], c["ref"], _who(name, i, c)
+        own = KNOWN_ILL_CONDITIONED.get((name, c["kind"], c["tag"]))
+        bound, length = (M.BOUNDS[name] if own is None else own) * c["scale"], float(np.linalg.norm(c["d"]))
+        expect = c.get("expect") if name == "inside" else None
+        want_hit = expect != "miss" if name == "inside" else c["win"] is not None
+        if (rec["entity"] == MISS) == want_hit:
+            bad.append(f"{who}: decision: GPU {'misses' if rec['entity'] == MISS else 'hits at t = %.6g' % rec['t']}, expected "
+                       f"{'a miss' if not want_hit else 'a hit at t = %.6g' % (ref['t_exit'] if expect == 'exit' else ref['t'])}")
+            continue
+        if not want_hit:
+            if not _is_miss_record(rec):
+                bad.append(f"{who}: a miss record that is not all-miss: {rec}")
+            continue
+        ent = int(ranges[i, 0]) + c["win"]
+        if rec["entity"] != ent or rec["collider"] != nc - 1 - ent or rec["object_type"] != 1:
+            bad.append(f"{who}: entity {rec['entity']} (expected {ent}), collider {rec['collider']} (expected {nc - 1 - ent}), object type {rec['object_type']}")
+            continue
+        shape = c["cols"][c["win"]]["shape"]
+        t, p, n = float(rec["t"]), rec["point"].astype(np.float64), rec["normal"].astype(np.float64)
+        if abs(np.linalg.norm(n) - 1) > 1e-5:
+            bad.append(f"{who}: |n| - 1 = {np.linalg.norm(n) - 1:.2e}")
+        if expect == "t0":
+            if t != 0 or not np.allclose(n, -c["d"] / length, atol=1e-6) or not (rec["point"] == c["o32"]).all():
+                bad.append(f"{who}: the origin is inside: expected t = 0, the origin and -normalize(d); got t = {t:.6g}, point {p}, normal {n}")
+            continue
+        t_ref, normals = (ref["t_exit"], c["exit_normals"]) if expect == "exit" else (ref["t"], c["normals"])
+        m = worst.setdefault(c["kind"], [0.0] * 5)
+        dt = abs(t - t_ref) * length
+        dp = float(np.linalg.norm(p - (c["o"] + t * c["d"])))
+        ds = abs(X.sdf(shape, p))
+        rho = float(shape[1][-1]) if shape[0] in (X.SPHERE, X.CAPSULE, X.CYLINDER) else 1.0
+        dn = min(float(np.linalg.norm(n - a)) for a in normals) * rho
+        short = 0.0
+        if len(normals) == 1 and expect is None:
+            short = 0.05 * c["scale"] - X.sdf(shape, p + 0.05 * c["scale"] * n)
+        if own is not None:
+            print(f"{who}: known ill-conditioned case, the largest measure per unit of scale {max(dt, dp, ds, short, dn) / c['scale']:.2e} (allowed {own:.0e})")
+        for k, v in enumerate((dt, dp, ds, short, dn) if own is None else ()):
+            m[k] = max(m[k], v / c["scale"])
+        if dt > bound:
+            bad.append(f"{who}: |t - t_ref| |d| = {dt:.3e} > {bound:.3e} (t = {t:.8g}, the reference {t_ref:.8g})")
+        if dp > bound or ds > bound:
+            bad.append(f"{who}: the point lies {dp:.3e} off o + t d and {ds:.3e} off the collider's surface (bound {bound:.3e})")
+        if short > bound or dn > bound:
+            bad.append(f"{who}: normal {n}: {dn:.3e} off the nearest of {len(normals)} admissible normals, separation short by {short:.3e} (bound {bound:.3e})")
+        if (n @ c["d"] > 0) != (expect == "exit"):
+            bad.append(f"{who}: normal {n} . d = {n @ c['d']:.3e}")
+    for kind, m in sorted(worst.items()):
+        print(f"{name}, {M.KINDS[kind]}, per unit of scale: largest |dt| |d| {m[0]:.2e}, point off o + t d {m[1]:.2e}, point off the surface {m[2]:.2e}, "
+              f"separation short by {m[3]:.2e}, normal off the admissible ones {m[4]:.2e}")
+    if worst:
+        print(f"{name}: the largest measure per unit of scale {max(max(m) for m in worst.values()):.2e} (bound {M.BOUNDS[name]:.0e})")
+    return bad
+
+
+@pytest.mark.parametrize("name", M.FAMILIES)
+def test_matrix_family(mi_lib, name):
+    """One family of tests/raycast_matrix.py in one world, ray i aimed at the entities of case i alone, through the grid and through the
+    exhaustive scan (the same bytes).  Every kept case, without a budget: the exact reference's decision, entity, collider and object type; t,
+    point and normal within the family's bound x scale (_check_matrix); dot(normal, d) <= 0 but for the documented answers of the `inside`
+    family (t = 0 with -normalize(d); a hull's far side); a miss record all-miss.  Every failure of the family is reported, after the worst
+    values."""
+    cases = M.kept(name)
+    sc, ranges = M.scene_of(cases, f"raycast matrix {name}")
+    w = Q.world(mi_lib, sc)
+    pick = list(range(len(cases))) + ([0] if len(cases) % 2 == 0 else [])   # (an odd batch)
+    o, d = np.stack([cases[i]["o32"] for i in pick]), np.stack([cases[i]["d32"] for i in pick])
+    max_t = np.array([cases[i]["max_t32"] for i in pick], np.float32)
+    got = _check_accel_equals_exhaustive(w, o, d, max_t, ranges=ranges[pick], include=ALL)
+    w.close()
+    bad = _check_matrix(name, cases, ranges, got)
+    assert not bad, f"{len(bad)} of {len(cases)} cases fail:\n" + "\n".join(bad)
