@@ -95,9 +95,26 @@ __device__ __forceinline__ OverlapVolume ovLoadVolume(const float4* __restrict__
     q.lo = vRange[2 * v]; q.hi = vRange[2 * v + 1]; q.include = include;
     return q;
 }
-// THE predicate: is collider k reported for this volume?  Object type, entity range, closed world AABBs (a non-finite one never), then the
-// reference's overlapCheck(A, B) with A = the smaller world type, the volume for equal types.  kBoxesOnly: everything but overlapCheck —
-// the candidates of the contact query (kernels_contacts_query.hpp), whose narrow phase decides instead.
+// The shape cast's pair test at a zero displacement (kernels_sweep.hpp, which includes this file: defined there): do the volume and the
+// collider touch?  Its float32 distance search with a tolerance relative to the coordinates (kSweepTolRel), no absolute threshold.
+__device__ bool swOverlaps(const Shape& volume, V3 volumeMin, V3 volumeMax, const Shape& collider, const HullSet& hs);
+
+// THE QUERY'S pair test (the step's triggers keep overlapCheck, gjk.hpp: the reference's bits).  The reference's closed forms where they
+// decide geometrically right, with their bits: spheres and capsules among themselves, a sphere against a box, boxes against boxes (SAT).
+// Everything else goes to swOverlaps: the reference's sphere / capsule vs cylinder compares a squared distance with a radius beyond the caps,
+// and its GJK (every pair with a cylinder or a hull, a capsule against a box) gives up at absolute thresholds (|dir|^2 < 1e-4, +-1e-5 in the
+// simplex update), so shapes of a few centimetres never overlap anything.  A capsule of zero length (a sphere; valid) goes there too: the
+// reference's closest point on its segment divides by the segment's length.
+__device__ __forceinline__ bool ovPointCapsule(const Shape& s) { return s.type == T_CAPSULE && s.a.x == s.b.x && s.a.y == s.b.y && s.a.z == s.b.z; }
+__device__ inline bool ovQueryCheck(const OverlapVolume& q, const Shape& c, const HullSet& hs) {
+    const int lo = min((int)c.type, q.s.type), hi = max((int)c.type, q.s.type);
+    const bool closedForm = ((hi <= T_CAPSULE) || (lo == T_SPHERE && (hi == T_AABB || hi == T_OBB)) || (lo >= T_AABB && hi <= T_OBB)) && !ovPointCapsule(q.s) && !ovPointCapsule(c);
+    if (!closedForm) return swOverlaps(q.s, q.mn, q.mx, c, hs);
+    return (int)c.type < q.s.type ? overlapCheck(c, q.s, hs) : overlapCheck(q.s, c, hs);
+}
+// THE predicate: is collider k reported for this volume?  Object type, entity range, closed world AABBs (a non-finite one never), then
+// ovQueryCheck.  kBoxesOnly: everything but the pair test — the candidates of the contact query (kernels_contacts_query.hpp), whose narrow
+// phase decides instead.
 template <bool kBoxesOnly> __device__ inline bool ovTest(const OverlapScene& s, const OverlapVolume& q, uint32_t k) {
     const float4 a = s.mn[k], b = s.mx[k];
     const uint32_t tag = __float_as_uint(a.w), type = tag & 0xFFu, obj = (tag >> 8) & 0xFFu;
@@ -107,8 +124,7 @@ template <bool kBoxesOnly> __device__ inline bool ovTest(const OverlapScene& s, 
     if (!(qExtent(a, b) >= 0.f)) return false;
     if (q.mx.x < a.x || q.mn.x > b.x || q.mx.y < a.y || q.mn.y > b.y || q.mx.z < a.z || q.mn.z > b.z) return false;
     if (kBoxesOnly) return true;
-    const Shape c = loadShape(s.shape, k, type);
-    return (int)type < q.s.type ? overlapCheck(c, q.s, s.hs) : overlapCheck(q.s, c, s.hs);
+    return ovQueryCheck(q, loadShape(s.shape, k, type), s.hs);
 }
 // THE record writer: slot = position in the whole result; nothing is written at or past capacity
 __device__ __forceinline__ void ovWrite(const OverlapScene& s, uint4* __restrict__ hits, uint32_t capacity, uint32_t slot, uint32_t k, uint32_t v) {

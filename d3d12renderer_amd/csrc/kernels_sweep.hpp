@@ -233,6 +233,15 @@ __device__ __noinline__ SweepResult sweepPair(const Shape& A, V3 sweptMin, V3 sw
     return r;
 }
 
+// The overlap query's pair test (declared in kernels_overlap.hpp): the cast by a zero displacement.  No plane can be clipped against, so the search
+// ends at the first support plane that separates the shapes by more than the margins (apart) or once the distance is within tolerance of the
+// margins, has stalled or has run out of iterations (touching: nothing separated them; measured on the pair matrix of tests/overlap_matrix.py:
+// shapes up to 4.7e-5 of their largest coordinate apart end this way, overlapping shapes never end as apart).  The same body as the casts': on
+// the pairs that come here a cast's initial-overlap flag and the overlap query agree by construction.
+__device__ bool swOverlaps(const Shape& volume, V3 volumeMin, V3 volumeMax, const Shape& collider, const HullSet& hs) {
+    return sweepPair(volume, volumeMin, volumeMax, collider, hs, V3()).hit;
+}
+
 // ---- kernels
 // what a cast is: the volume (rows of k_ov_prepare), its displacement, the swept bounds
 struct SweepCast { OverlapVolume q; V3 d, centre, half, sweptMin, sweptMax; bool valid; };

@@ -1,12 +1,15 @@
 """Volume-overlap scene queries on the GPU (mi_world_overlap, mi_world_overlap_device_async, mi_debug_overlap_exhaustive): against the
 reference's own trigger path (shrunk and grown volumes in oracle worlds), against the numpy gaps of tests/overlap_ref.py, the
 accelerated grid walk against the exhaustive scan byte for byte, the capacity protocol, the device variant, the cache's invalidation,
-and that queries change nothing a step computes."""
+that queries change nothing a step computes, and the pair-level matrix of tests/overlap_matrix.py: every decision against a verified
+float64 certificate, the zero-displacement shape cast, and the same cases as triggers in a step (which keep the reference's bits)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import overlap_exact as E
+import overlap_matrix as OM
 import overlap_ref as R
 import query_helpers as Q
 
@@ -25,7 +28,9 @@ def _accel_equals_exhaustive(w, vols, include, ranges=None, what=""):
 @pytest.mark.parametrize("settled", [False, True])
 def test_sandwiched_by_the_reference_trigger_path(mi_lib, oracle_mod, name, settled):
     """shrunk-oracle <= query <= grown-oracle per volume, as entity sets, with no budget: wherever the reference's answer does not depend
-    on a relative 1e-3 of the volume's size, the query gives exactly it."""
+    on a relative 1e-3 of the volume's size, the query gives exactly it - except where a VERIFIED float64 certificate (tests/overlap_exact.py)
+    contradicts the reference: there the query must give the certificate's answer, and the pair must be of a class the header names (a
+    cylinder or a hull in the pair, or a capsule against a box)."""
     sc = R.query_scene(name)
     w = Q.world(mi_lib, sc, 300 if settled else 0)
     vols = R.volume_set(name, settled)
@@ -39,8 +44,33 @@ def test_sandwiched_by_the_reference_trigger_path(mi_lib, oracle_mod, name, sett
     print(f"{name} settled={settled}: {sum(map(len, shrunk))} shrunk / {sum(map(len, got))} query / {sum(map(len, grown))} grown; both non-empty {both:.0%}, ambiguous {ambiguous:.2%}")
     assert subset and sum(map(len, shrunk)) > 100
     assert both > 0.5 and ambiguous <= 0.02   # the yardstick's own validity for THIS set (a condition on the inputs: seeds and boxes in overlap_ref)
-    missing = [(v, sorted(shrunk[v] - got[v])) for v in range(len(vols)) if not shrunk[v] <= got[v]]
-    extra = [(v, sorted(got[v] - grown[v])) for v in range(len(vols)) if not got[v] <= grown[v]]
+    # where the query leaves the sandwich: the certificates of the volume against every collider of the entity, at the poses the query read
+    shapes = R.scene_world_shapes(sc, *w.physics_transforms())
+    nc = len(sc.colliders)
+    of_entity = {}
+    for k, (ent, obj, ws) in enumerate(shapes):
+        c = sc.colliders[nc - 1 - k]
+        of_entity.setdefault(ent, []).append(E.with_hull(ws, sc.hulls[int(c["hull_geometry"])] if ws[0] == R.HULL else None))
+    contradicted, undecided = [], []
+
+    def certificate_overrules(v, ent, query_reports):
+        vs = E.with_hull(R.volume_world_shape(vols[v]), sc.hulls[int(vols[v]["hull_geometry"])] if int(vols[v]["type"]) == R.HULL else None)
+        verdicts = [(cs[0], *E.certify(vs, cs)) for cs in of_entity[ent]]
+        overlapping = any(d is True for _, d, _ in verdicts)
+        decided = overlapping or all(d is False for _, d, _ in verdicts)
+        if not decided or overlapping != query_reports:
+            undecided.append((v, ent, "no certificate verified" if not decided else "the certificate sides with the reference"))
+            return False    # no certificate against the reference here (or one against the query): the sandwich stands
+        quirk = [t for t, d, _ in verdicts if (d is True) == overlapping and ({R.CYLINDER, R.HULL} & {t, vs[0]} or {t, vs[0]} in ({R.CAPSULE, R.AABB}, {R.CAPSULE, R.OBB}))]
+        assert quirk, f"volume {v} (type {vs[0]}) and entity {ent}: the certificate contradicts the reference on a pair of no class the header names: {verdicts}"
+        contradicted.append((v, ent, "overlapping" if overlapping else "apart", min(c for _, d, c in verdicts if (d is True) == overlapping)))
+        return True
+
+    missing = [(v, sorted(e for e in shrunk[v] - got[v] if not certificate_overrules(v, e, False))) for v in range(len(vols)) if not shrunk[v] <= got[v]]
+    extra = [(v, sorted(e for e in got[v] - grown[v] if not certificate_overrules(v, e, True))) for v in range(len(vols)) if not got[v] <= grown[v]]
+    missing, extra = [m for m in missing if m[1]], [x for x in extra if x[1]]
+    print(f"{name} settled={settled}: {len(contradicted)} (volume, entity) pairs where a verified certificate contradicts the reference and the query follows the certificate: {contradicted[:8]}; "
+          f"{len(undecided)} pairs outside the sandwich that no certificate excuses (they fail below): {undecided[:8]}")
     assert not missing, f"the reference reports these even for the shrunk volume (volume, entities; types {[int(vols['type'][v]) for v, _ in missing[:6]]}): {missing[:6]}"
     assert not extra, f"the reference reports none of these even for the grown volume (volume, entities; types {[int(vols['type'][v]) for v, _ in extra[:6]]}): {extra[:6]}"
     w.close()
@@ -265,7 +295,118 @@ def test_queries_change_nothing(mi_lib):
     a.close(); b.close()
 
 
-# ---- 8. errors
+# ---- 8. the pair-level matrix: every volume type against every collider type, one collider at a time (tests/overlap_matrix.py)
+def _matrix_query(mi_lib, name):
+    """One world per family, one static entity with one collider per case (kept and sub-bound alike); volume i is restricted to entity i.
+    The batch is made odd (never a multiple of the volumes per workgroup) by a repeat of the first volume.  Returns (world, cases, volumes,
+    ranges, per case whether the query reports its collider)."""
+    cases = OM.family(name)
+    w = Q.world(mi_lib, OM.scene_of(cases, f"overlap matrix {name}"))
+    pick = list(range(len(cases))) + ([0] if len(cases) % 2 == 0 else [])
+    vols = np.concatenate([cases[i]["volume"] for i in pick])
+    ranges = np.array([(i, i + 1) for i in pick], np.uint32)
+    offsets, hits = _accel_equals_exhaustive(w, vols, ALL, ranges, what=f"matrix {name}")
+    sizes = np.diff(offsets.astype(np.int64))
+    assert (sizes <= 1).all() and (hits["entity"] == ranges[hits["volume"], 0]).all() and (hits["object_type"] == 1).all()
+    assert len(pick) == len(cases) or sizes[-1] == sizes[0]
+    return w, cases, vols, ranges, sizes[:len(cases)] == 1
+
+
+def _who(name, i, c):
+    return (f"{name}[{i}] {OM.TYPES[c['vt']]} -> {OM.TYPES[c['ct']]} {c['tag']}: {'overlapping' if c['expected'] else 'apart'} by {c['cert']:.3e} "
+            f"= {c['cert'] / c['scale']:.3e} scale (scale {c['scale']:.3g})")
+
+
+def _report_wrong(name, cases, got, what):
+    """Prints what the family measures (the largest certificate per unit of scale of a wrong decision, over all its cases and per pair) and
+    returns the wrong decisions among the KEPT cases."""
+    wrong = [i for i, c in enumerate(cases) if bool(got[i]) != c["expected"]]
+    rel = {i: cases[i]["cert"] / cases[i]["scale"] for i in wrong}
+    per_pair = {}
+    for i in wrong:
+        key = (OM.TYPES[cases[i]["vt"]], OM.TYPES[cases[i]["ct"]], "overlapping" if cases[i]["expected"] else "apart")
+        per_pair[key] = max(per_pair.get(key, 0.0), rel[i])
+    kept = sum(OM.is_kept(c) for c in cases)
+    print(f"{what} {name}: {len(cases)} certified cases ({kept} kept at the bound {OM.BOUNDS[name]:.0e}), {len(wrong)} decided wrongly; the largest certificate of a wrong "
+          f"decision per unit of scale: {max(rel.values(), default=0.0):.3e}; smallest certificate of the family {min(c['cert'] / c['scale'] for c in cases):.3e}")
+    for key, v in sorted(per_pair.items(), key=lambda kv: -kv[1])[:12]:
+        print(f"    {key[0]} -> {key[1]}, {key[2]}: wrong up to {v:.3e} scale")
+    closed = [rel[i] for i in wrong if R.signed_gap(cases[i]["vs"], cases[i]["cs"]) is not None or {cases[i]["vt"], cases[i]["ct"]} <= {R.AABB, R.OBB}]
+    print(f"    the reference's closed forms (spheres, capsules, sphere-box, box-box) among them: {len(closed)}, wrong up to {max(closed, default=0.0):.3e} scale; "
+          f"overlapping cases reported apart: {sum(cases[i]['expected'] for i in wrong)}")
+    return [i for i in wrong if OM.is_kept(cases[i])]
+
+
+@pytest.mark.parametrize("name", OM.FAMILIES)
+def test_matrix_decisions(mi_lib, name):
+    """The query's decision equals the verified float64 certificate's in every kept case (certificate >= 4 x the family's bound x scale); the
+    sub-bound cases are decided too and only printed: they measure the resolution (overlap_matrix.MEASURED)."""
+    w, cases, vols, ranges, got = _matrix_query(mi_lib, name)
+    w.close()
+    bad = _report_wrong(name, cases, got, "overlap")
+    one_sided = OM.one_sided(name)   # (size_ratio: overlapping cases below the family's bound, held never to be reported apart)
+    index = {id(c): i for i, c in enumerate(cases)}
+    bad += [index[id(c)] for c in one_sided if not got[index[id(c)]]]
+    print(f"{name}: {len(one_sided)} overlapping cases under the one-sided bound {OM.ONE_SIDED_BOUND:.0e}")
+    assert not bad, f"{len(bad)} kept cases decided wrongly:\n" + "\n".join(_who(name, i, cases[i]) + f": the query says {'overlapping' if got[i] else 'apart'}" for i in bad[:40])
+
+
+@pytest.mark.parametrize("name", OM.FAMILIES)
+def test_matrix_accelerated_equals_exhaustive(mi_lib, name):
+    """Every case of the family, sub-bound ones included: the grid walk and the exhaustive scan give the same bytes, with and without the
+    entity ranges (without them every volume meets every collider of the family)."""
+    w, cases, vols, ranges, got = _matrix_query(mi_lib, name)
+    sub = vols[:: max(1, len(vols) // 64)]
+    offsets, hits = _accel_equals_exhaustive(w, sub, ALL, what=f"matrix {name}, no ranges")
+    assert len(hits) > 0
+    w.close()
+
+
+@pytest.mark.parametrize("name", OM.FAMILIES)
+def test_matrix_zero_displacement_sweep_agrees(mi_lib, name):
+    """mi_world_sweep with a zero displacement: its initial-overlap verdict is the overlap query's, on every kept case of the family (the
+    sub-bound ones are counted and printed)."""
+    w, cases, vols, ranges, got = _matrix_query(mi_lib, name)
+    recs = w.sweep(vols, np.zeros((len(vols), 3), np.float32), ALL, ranges)[:len(cases)]
+    w.close()
+    hit = recs["entity"] != 0xFFFFFFFF
+    assert (recs["flags"][hit] & 1).all() and (recs["t"][hit] == 0).all(), "a zero displacement hit something it did not start in"
+    # the pair test never ran out of iterations on a kept case: "overlapping" there is a search that ended, not one that gave up
+    gave_up = [i for i in range(len(cases)) if hit[i] and recs["flags"][i] & 2]
+    print(f"{name}: {len(gave_up)} cases end with the sweep's unconverged flag,{sum(OM.is_kept(cases[i]) for i in gave_up)} of them kept: {[_who(name, i, cases[i]) for i in gave_up[:6]]}")
+    assert not [i for i in gave_up if OM.is_kept(cases[i])]
+    bad = _report_wrong(name, cases, hit, "zero-displacement sweep")
+    differ = [i for i in range(len(cases)) if bool(hit[i]) != bool(got[i])]
+    print(f"{name}: sweep and overlap differ on {len(differ)} cases, {sum(OM.is_kept(cases[i]) for i in differ)} of them kept")
+    assert not bad, f"{len(bad)} kept cases:\n" + "\n".join(_who(name, i, cases[i]) for i in bad[:40])
+    assert not [i for i in differ if OM.is_kept(cases[i])]
+
+
+def test_matrix_triggers_in_the_step_keep_the_reference_bits(mi_lib, oracle_mod):
+    """The cylinder_caps cases and the small cases of `size` as trigger entities over rigid bodies, one step: the step's TRIGGER_ENTER events are
+    the oracle's, pair for pair: the query's corrected predicate did not reach k_overlap.  The world holds cases that the reference decides
+    against their certificate, so the two predicates do differ on it."""
+    cases = OM.trigger_cases()
+    n = len(cases)
+    sc = OM.trigger_scene(cases)
+    o = sc.populate(oracle_mod.create_world(oracle_mod.ORDER_REFERENCE))
+    want = OM.trigger_enters(o, sc, n)
+    o.close()
+    w = Q.world(mi_lib, sc)
+    vols = np.concatenate([c["volume"] for c in cases])
+    _, hits = w.overlap(vols, include=RIGID, entity_ranges=np.array([(i, i + 1) for i in range(n)], np.uint32))
+    query = set(int(v) for v in hits["volume"])
+    got = OM.trigger_enters(w, sc, n)
+    w.close()
+    own = {a for a, b in want if a == b}
+    quirks = [i for i, c in enumerate(cases) if OM.is_kept(c) and (i in own) != c["expected"]]
+    print(f"{n} cases: {len(want)} trigger events in the oracle, {len(got)} on the GPU; the reference decides {len(quirks)} kept cases against their certificate; "
+          f"the query differs from the step on {len(query ^ own)} cases")
+    assert got == want, f"only the GPU: {sorted(got - want)[:8]}; only the oracle: {sorted(want - got)[:8]}"
+    assert len(quirks) >= 10 and all((i in query) == cases[i]["expected"] for i in quirks)
+
+
+# ---- 9. errors
 def test_errors(mi_lib):
     from d3d12renderer_amd import capi, scenes, sharding
     sc = scenes.shape_zoo(2, 1, 2)

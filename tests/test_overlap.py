@@ -1,17 +1,50 @@
 """Volume-overlap scene queries without a GPU: the ABI (header, exports, record sizes), the numpy reference the GPU tests compare
-against, and the validity of the trigger yardstick (the reference's own trigger path on shrunk and grown volumes) for the very volume
-sets the GPU tests use."""
+against, the validity of the trigger yardstick (the reference's own trigger path on shrunk and grown volumes) for the very volume
+sets the GPU tests use, the float64 certificate checkers of tests/overlap_exact.py on hand cases, the cap of the pair-level matrix of
+tests/overlap_matrix.py, and the reference's trigger path over that matrix (how many cases it decides wrongly, pinned)."""
 import re
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import overlap_exact as E
+import overlap_matrix as OM
 import overlap_ref as R
 from overlap_ref import AABB, CAPSULE, CYLINDER, HULL, OBB, SPHERE
 
 ROOT = Path(__file__).resolve().parent.parent
 OVERLAP_SYMBOLS = ("mi_world_overlap", "mi_world_overlap_device_async", "mi_debug_overlap_exhaustive")
+# test_reference_trigger_path_over_the_matrix: (family, volume type, collider type) -> kept cases the reference's overlapCheck decides against
+# their certificate
+REFERENCE_DECIDES_WRONGLY = {
+    ('generic', 'AABB', 'capsule'): 1, ('generic', 'OBB', 'cylinder'): 1, ('generic', 'capsule', 'AABB'): 2, ('generic', 'capsule', 'cylinder'): 5,
+    ('generic', 'cylinder', 'OBB'): 1, ('generic', 'cylinder', 'capsule'): 8, ('generic', 'cylinder', 'hull'): 1,
+    ('generic', 'cylinder', 'sphere'): 9, ('generic', 'hull', 'capsule'): 1, ('generic', 'hull', 'cylinder'): 1, ('generic', 'hull', 'sphere'): 1,
+    ('generic', 'sphere', 'cylinder'): 10, ('generic', 'sphere', 'hull'): 1,
+    ('features', 'OBB', 'capsule'): 2, ('features', 'capsule', 'cylinder'): 4, ('features', 'cylinder', 'capsule'): 2,
+    ('features', 'cylinder', 'sphere'): 4, ('features', 'hull', 'capsule'): 1, ('features', 'sphere', 'cylinder'): 4,
+    ('cylinder_caps', 'capsule', 'cylinder'): 30, ('cylinder_caps', 'cylinder', 'capsule'): 29, ('cylinder_caps', 'cylinder', 'sphere'): 35,
+    ('cylinder_caps', 'sphere', 'cylinder'): 38,
+    ('size', 'AABB', 'capsule'): 24, ('size', 'AABB', 'cylinder'): 25, ('size', 'AABB', 'hull'): 16, ('size', 'OBB', 'capsule'): 27,
+    ('size', 'OBB', 'cylinder'): 26, ('size', 'OBB', 'hull'): 18, ('size', 'capsule', 'AABB'): 22, ('size', 'capsule', 'OBB'): 26,
+    ('size', 'capsule', 'cylinder'): 5, ('size', 'capsule', 'hull'): 16, ('size', 'cylinder', 'AABB'): 25, ('size', 'cylinder', 'OBB'): 24,
+    ('size', 'cylinder', 'capsule'): 1, ('size', 'cylinder', 'cylinder'): 24, ('size', 'cylinder', 'hull'): 15, ('size', 'cylinder', 'sphere'): 9,
+    ('size', 'hull', 'AABB'): 14, ('size', 'hull', 'OBB'): 15, ('size', 'hull', 'capsule'): 16, ('size', 'hull', 'cylinder'): 15,
+    ('size', 'hull', 'hull'): 18, ('size', 'hull', 'sphere'): 18, ('size', 'sphere', 'cylinder'): 9, ('size', 'sphere', 'hull'): 16,
+    ('size_ratio', 'capsule', 'cylinder'): 2, ('size_ratio', 'sphere', 'cylinder'): 2,
+    ('far', 'capsule', 'cylinder'): 1,
+    ('thin', 'OBB', 'cylinder'): 1, ('thin', 'capsule', 'cylinder'): 7, ('thin', 'cylinder', 'cylinder'): 2, ('thin', 'cylinder', 'hull'): 2,
+    ('thin', 'hull', 'cylinder'): 1, ('thin', 'sphere', 'cylinder'): 2,
+    ('containment', 'cylinder', 'cylinder'): 1, ('containment', 'hull', 'hull'): 1,
+    ('degenerate', 'AABB', 'capsule'): 3, ('degenerate', 'OBB', 'capsule'): 7, ('degenerate', 'capsule', 'OBB'): 1,
+    ('degenerate', 'capsule', 'cylinder'): 2, ('degenerate', 'capsule', 'hull'): 1, ('degenerate', 'capsule', 'sphere'): 6,
+    ('degenerate', 'cylinder', 'capsule'): 9, ('degenerate', 'cylinder', 'cylinder'): 1, ('degenerate', 'cylinder', 'sphere'): 9,
+    ('ladder', 'AABB', 'capsule'): 2, ('ladder', 'AABB', 'cylinder'): 1, ('ladder', 'OBB', 'capsule'): 2, ('ladder', 'OBB', 'cylinder'): 2,
+    ('ladder', 'capsule', 'AABB'): 2, ('ladder', 'capsule', 'OBB'): 1, ('ladder', 'capsule', 'cylinder'): 8, ('ladder', 'capsule', 'hull'): 2,
+    ('ladder', 'cylinder', 'capsule'): 3, ('ladder', 'cylinder', 'cylinder'): 1, ('ladder', 'cylinder', 'sphere'): 8,
+    ('ladder', 'hull', 'capsule'): 3, ('ladder', 'hull', 'cylinder'): 2, ('ladder', 'sphere', 'cylinder'): 8, ('ladder', 'sphere', 'hull'): 2,
+}
 
 
 def test_header_declares_and_library_exports_the_overlap_api(mi_lib):
@@ -102,6 +135,121 @@ def test_scaling_about_the_centre():
         else:
             assert b["hull_geometry"] == 9
     assert sorted(set(int(t) for t in vols["type"])) == [0, 1, 2, 3, 4, 5]
+
+
+# ---- the certificates of tests/overlap_exact.py and the matrix of tests/overlap_matrix.py
+def _shape(ctype, words, pos=(0, 0, 0), rot=I, hull=None):
+    return E.shape_of(ctype, np.asarray(words, float), pos, rot, hull)
+
+
+def test_certificate_checkers_on_hand_cases():
+    """Support values, inside depths and both checkers on numbers worked out by hand; a wrong direction or point is rejected."""
+    cyl = _shape(CYLINDER, [0, -1, 0, 0, 1, 0, 0.5])
+    ball = _shape(SPHERE, [0.7, 1.2, 0, 0.25])
+    box = _shape(AABB, [-1, -2, -3, 1, 2, 3])
+    turned = _shape(AABB, [-1, -2, -3, 1, 2, 3], rot=Z90)                        # an OBB: x and y half-extents swapped
+    cap = _shape(CAPSULE, [0, -1, 0, 0, 1, 0, 0.25])
+    verts = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], float); tris = np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]])
+    tet = _shape(HULL, [0, 0, 0, 1, 0, 0, 0], pos=(5, 0, 0), hull=(verts, tris))
+    diag = np.array([1.0, 1.0, 0.0]) / np.sqrt(2.0)
+    assert np.isclose(E.support_value(cyl, (0, 1, 0)), 1.0) and np.isclose(E.support_value(cyl, (1, 0, 0)), 0.5)
+    assert np.isclose(E.support_value(cyl, diag), (1.0 + 0.5) / np.sqrt(2.0))      # the rim point (0.5, 1, 0)
+    assert np.isclose(E.support_value(ball, diag), 1.9 / np.sqrt(2.0) + 0.25) and np.isclose(E.support_value(cap, (0, -1, 0)), 1.25)
+    assert np.isclose(E.support_value(box, (1, -1, 0.5)), 1 + 2 + 1.5) and np.isclose(E.support_value(turned, (1, 0, 0)), 2.0)
+    assert np.isclose(E.support_value(tet, (1, 1, 1)), 6.0) and np.isclose(E.support_value(tet, (-1, 0, 0)), -5.0)
+    assert np.isclose(E.inside_depth(cyl, (0.1, 0.8, 0)), 0.2) and np.isclose(E.inside_depth(cyl, (0.4, 0, 0)), 0.1) and E.inside_depth(cyl, (0, 1.1, 0)) < 0
+    assert np.isclose(E.inside_depth(ball, (0.7, 1.1, 0)), 0.15) and np.isclose(E.inside_depth(cap, (0.1, 1.0, 0)), 0.15) and np.isclose(E.inside_depth(cap, (0, 1.2, 0)), 0.05)
+    assert np.isclose(E.inside_depth(box, (0.5, 0, 0)), 0.5) and np.isclose(E.inside_depth(turned, (1.5, 0, 0)), 0.5) and E.inside_depth(turned, (0, 1.5, 0)) < 0
+    assert np.isclose(E.inside_depth(tet, (5.1, 0.1, 0.1)), 0.1) and np.isclose(E.inside_depth(tet, (5.25, 0.25, 0.25)), 0.25 / np.sqrt(3.0)) and E.inside_depth(tet, (5.5, 0.5, 0.5)) < 0
+    # the first confirmed case of the issue: a sphere of 0.25 at (0.7, 1.2, 0) is 0.033 clear of the rim
+    gap = np.hypot(0.2, 0.2) - 0.25
+    assert np.isclose(E.verify_apart(ball, cyl, diag), gap) and np.isclose(E.verify_apart(ball, cyl, E.propose_apart(ball, cyl)), gap)
+    assert E.verify_apart(ball, cyl, (0, 1, 0)) < 0 and E.verify_apart(ball, cyl, (1, 0, 0)) < 0 and E.verify_apart(ball, cyl, -diag) < 0   # wrong directions
+    assert E.verify_apart(ball, cyl, 2 * diag) == -np.inf and E.verify_apart(ball, cyl, (np.nan, 0, 0)) == -np.inf                      # not unit, not finite
+    # the third: a sphere of 2 at (0, 2.8, 0) is 0.2 deep in the cap
+    big = _shape(SPHERE, [0, 2.8, 0, 2.0])
+    assert np.isclose(E.verify_overlap(big, cyl, (0, 0.9, 0)), 0.1)
+    assert E.verify_overlap(big, cyl, (0, 1.1, 0)) < 0 and E.verify_overlap(big, cyl, (0, 0.7, 0)) < 0 and E.verify_overlap(big, cyl, (0.6, 0.9, 0)) < 0   # wrong points
+    assert E.verify_apart(big, cyl, (0, 1, 0)) < 0 and E.verify_overlap(ball, cyl, (0.55, 1.05, 0)) < 0                                                    # and no certificate of the opposite
+    p = E.propose_overlap(big, cyl, (0, 0.95, 0), 0.05, n=np.array([0.0, 1.0, 0.0]))
+    assert E.verify_overlap(big, cyl, p) > 0.09
+    # a degenerate volume: the certificate is a point OF the volume, deep in the collider
+    point = _shape(SPHERE, [0.2, 0.5, 0, 0.0]); flat = _shape(AABB, [-0.2, 0.5, -0.2, 0.2, 0.5, 0.2])
+    assert E.verify_overlap(point, cyl, (0.2, 0.5, 0)) <= 0 and np.isclose(E.verify_overlap(point, cyl, (0.2, 0.5, 0), True), 0.3)
+    assert E.verify_overlap(point, cyl, (0.2, 0.6, 0), True) == -np.inf and np.isclose(E.verify_overlap(flat, cyl, (0, 0.5, 0), True), 0.5)
+    assert np.allclose(E.nearest_core_point(flat, (1, 1, 0)), (0.2, 0.5, 0)) and np.allclose(E.nearest_core_point(_shape(CAPSULE, [0, -1, 0, 0, 1, 0, 0]), (3, 5, 0)), (0, 1, 0))
+    with pytest.raises(ValueError):
+        E.support_value(_shape(CYLINDER, [0, 1, 0, 0, 1, 0, 0.5]), (1, 0, 0))
+
+
+@pytest.mark.parametrize("name", OM.FAMILIES)
+def test_matrix_holds_every_pair_after_the_filter(name):
+    """THE CAP: with the cases whose verified certificate is below 4 x bound x scale left out, the family still holds every pair that applies
+    to it with at least 3 overlapping and 3 apart cases (containment: overlapping only) - from the float64 certificates alone."""
+    cases = OM.family(name)
+    for c in cases:   # every certificate verifies again from the case's own float32 numbers, and says what the case expects
+        vs = E.shape_of(int(c["volume"]["type"][0]), c["volume"]["shape"][0], c["volume"]["position"][0], c["volume"]["rotation"][0], OM._hull_of(c["vol"]))
+        cs = E.shape_of(c["col_type"], c["col_words"], c["col_pos"], c["col_rot"], OM._hull_of(c["col"]))
+        again = E.verify_overlap(vs, cs, c["witness"], c["degenerate"]) if c["expected"] else E.verify_apart(vs, cs, c["witness"])
+        assert again == c["cert"] > 0 and c["scale"] >= 1, c["tag"]
+    for c in [c for c in cases if c["expected"]][::9]:   # (a sample: no separating direction verifies for a case certified as overlapping)
+        n = E.propose_apart(c["vs"], c["cs"])
+        assert n is None or not E.verify_apart(c["vs"], c["cs"], n) > 1e-9 * c["scale"], c["tag"]
+    table = OM.counts(OM.kept(name))
+    print(f"{name}: {len(cases)} certified, {sum(a + b for a, b in table.values())} kept at {OM.BOUNDS[name]:.0e}; fewest per pair: "
+          f"{min(t[0] for t in table.values())} overlapping, {min(t[1] for t in table.values())} apart")
+    assert OM.BOUNDS[name] <= OM.UNIT_BOUND
+    assert set(table) == set(OM.APPLIES[name])
+    if name == "size_ratio":   # (a shape of 1e-2 holds no ball above 5e-3: the overlapping side of the cap is met under the one-sided bound)
+        assert max(c["cert"] for c in cases if c["expected"]) <= 5e-3 * (1 + 1e-6) and OM.ONE_SIDED_BOUND < OM.BOUNDS[name]
+        extra = OM.counts(OM.one_sided(name))
+        table = {p: [t[0] + extra.get(p, [0, 0])[0], t[1]] for p, t in table.items()}
+    else:
+        assert not OM.one_sided(name)
+    short = {(OM.TYPES[v], OM.TYPES[c]): t for (v, c), t in table.items() if t[0] < 3 or (t[1] < 3 and name != "containment")}
+    assert not short, short
+    if name == "size":   # the cap per pair AND per size: the small sizes are what the reference's absolute thresholds lose
+        for s in OM.SIZES:
+            per = OM.counts([c for c in OM.kept(name) if c["setup"] == f"{s:g}"])
+            short = {(s, OM.TYPES[v], OM.TYPES[c]): per.get((v, c)) for v, c in OM.PAIRS if min(per.get((v, c), [0, 0])) < 3}
+            assert not short, short
+    if name == "far":      # overlapping cases are kept at coordinates of 1e3 too
+        per = OM.counts([c for c in OM.kept(name) if c["scale"] > 1000])
+        short = {(OM.TYPES[v], OM.TYPES[c]): per.get((v, c)) for v, c in OM.PAIRS if per.get((v, c), [0, 0])[0] < 3}
+        assert not short, short
+    if name == "cylinder_caps":   # the three cases the reference was confirmed wrong on, verbatim, with their gaps
+        first = cases[:3]
+        assert [c["tag"] for c in first] == ["confirmed-sphere-off-rim", "confirmed-capsule-off-rim", "confirmed-sphere-in-cap"] and all(OM.is_kept(c) for c in first)
+        assert np.isclose(first[0]["cert"], np.hypot(0.2, 0.2) - 0.25, atol=1e-6) and np.isclose(first[1]["cert"], first[0]["cert"], atol=1e-6) and first[2]["cert"] > 0.09
+    if name == "size":
+        assert {c["setup"] for c in cases} == {f"{s:g}" for s in OM.SIZES}
+
+
+def test_reference_trigger_path_over_the_matrix(oracle_mod):
+    """What triggers in the step still do: the reference's overlapCheck (the oracle's trigger path, one step) on every kept case of the
+    matrix, and the number it decides against the verified certificate per (family, volume type, collider type), pinned.  A change of the
+    table is a change of the restatement of overlapCheck in the oracle, or of the matrix."""
+    got = {}
+    for name in OM.FAMILIES:
+        cases = OM.kept(name)
+        for k in range(0, len(cases), 400):
+            part = cases[k:k + 400]
+            sc = OM.trigger_scene(part)
+            w = sc.populate(oracle_mod.create_world(oracle_mod.ORDER_REFERENCE))
+            own = {a for a, b in OM.trigger_enters(w, sc, len(part)) if a == b}
+            w.close()
+            for i, c in enumerate(part):
+                if (i in own) != c["expected"]:
+                    key = (name, OM.TYPES[c["vt"]], OM.TYPES[c["ct"]])
+                    got[key] = got.get(key, 0) + 1
+    for key in sorted(set(got) | set(REFERENCE_DECIDES_WRONGLY)):
+        if got.get(key, 0) != REFERENCE_DECIDES_WRONGLY.get(key, 0):
+            print(f"{key}: {got.get(key, 0)} now, {REFERENCE_DECIDES_WRONGLY.get(key, 0)} pinned")
+    print(f"the reference decides {sum(got.values())} kept cases of the matrix against their certificate, in {len(got)} (family, pair) cells")
+    assert got == REFERENCE_DECIDES_WRONGLY
+    # every cell is one of the classes the header names: a cylinder or a hull in the pair, or a capsule against a box or a point capsule
+    for (name, vt, ct) in got:
+        assert {"cylinder", "hull"} & {vt, ct} or {vt, ct} in ({"capsule", "AABB"}, {"capsule", "OBB"}) or (name == "degenerate" and vt == "capsule"), (name, vt, ct)
 
 
 @pytest.mark.parametrize("name", ["shape_zoo", "zones"])
