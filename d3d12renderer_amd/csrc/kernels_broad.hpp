@@ -4,10 +4,11 @@
 //                                    lane-level pieces of the classification: the five first-step kernels and k_bp_prepare (every later step) are made of them
 //   largeLimit, gridFit, gridWrite   grid set-up; the threshold rule differs: k_bp_threshold (first step) / nextStepThreshold (pairFinishStats, later steps)
 //   pairStage / pairFlush            LDS staging and block flush of both pair passes
-//   bpPairsGridBody = bpColumnRange (column header) + bpWalkCandidates (candidate walk) + pairKey, pairStage + pairFlush;  bpPairsLargeBody;  k_bp_pairs runs both
+//   bpPairsGridBody = bpColumnRange (column header) + bpWalkCandidates (candidate walk on the compact rows of bp_quant.hpp, then the exact test of what passed) + pairKey, pairStage + pairFlush;  bpPairsLargeBody;  k_bp_pairs runs both
 //   pairFinishCounts / pairFinishStats, k_pair_partition     what a step's pair list ends with; next sweep axis and next grid
 // Part of the ONE translation unit of the physics library (world.hip includes kernels.hpp, which includes the stage files in pipeline order).
 #pragma once   // (included by kernels.hpp only, after the stage files before it)
+#include "bp_quant.hpp"
 
 namespace mi {
 
@@ -457,15 +458,18 @@ __global__ __launch_bounds__(256) void k_bp_prepare(uint32_t nc, ColliderRows ro
   });
 }
 
-// Cell-sorted copies of the AABB rows (a column scan reads contiguous memory), the cell key and the collider index.
+// Cell-sorted copies of the AABB rows (a column scan reads contiguous memory), the cell key and the collider index — and the COMPACT row the grid pass walks: the box
+// quantised on the frame of this step's grid + the collider index, 16 bytes (bp_quant.hpp).
 // Positions [numSmall, nc) keep the key 0xFFFFFFFF written by the host-side fill.
 template <bool STRIDED>
 __global__ __launch_bounds__(256) void k_bp_scatter_sorted(uint32_t nc, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ ranks,
                                                            const uint32_t* __restrict__ cellLower,
                                                            const float4* __restrict__ aabbMin, const float4* __restrict__ aabbMax,
                                                            uint32_t* __restrict__ keysS, uint32_t* __restrict__ valsS,
-                                                           float4* __restrict__ sMin, float4* __restrict__ sMax, const uint8_t* __restrict__ cbLive /* sharded world: collider blocks with a live collider, or null */) {
+                                                           float4* __restrict__ sMin, float4* __restrict__ sMax, const GridParams* __restrict__ gp, uint4* __restrict__ sRow,
+                                                           const uint8_t* __restrict__ cbLive /* sharded world: collider blocks with a live collider, or null */) {
     const uint32_t numCb = (nc + blockDim.x - 1u) / blockDim.x;
+    const BpQuantFrame frame = bpQuantFrame(gp->origin, gp->dims, gp->cell);
     forLiveBlocks<STRIDED>(blockIdx.x, gridDim.x, numCb, [&](uint32_t cb) { return !cbLive || cbLive[cb] != 0u; }, [&](uint32_t cb) {
         const uint32_t i = cb * blockDim.x + threadIdx.x;
         if (i >= nc) return;
@@ -473,7 +477,12 @@ __global__ __launch_bounds__(256) void k_bp_scatter_sorted(uint32_t nc, const ui
         if (key == 0xFFFFFFFFu) return;
         const uint32_t pos = cellLower[key] + ranks[i];
         keysS[pos] = key; valsS[pos] = i;
-        sMin[pos] = aabbMin[i]; sMax[pos] = aabbMax[i];
+        const float4 mn = aabbMin[i], mx = aabbMax[i];
+        sMin[pos] = mn; sMax[pos] = mx;
+        const float lo[3] = {mn.x, mn.y, mn.z}, hi[3] = {mx.x, mx.y, mx.z};
+        uint32_t row[4];
+        bpQuantRow(frame, lo, hi, i, row);
+        sRow[pos] = make_uint4(row[0], row[1], row[2], row[3]);
     });
 }
 
@@ -551,7 +560,10 @@ constexpr uint32_t kPairOverflow = 512;   // block-shared overflow slots of k_bp
 #endif
 constexpr uint32_t kPairFetch = MI_PAIR_FETCH;   // candidates of a column fetched per loop trip (2 loads each)
 constexpr uint32_t kPairBuf = 6;      // LDS-staged pair keys per collider-column before the block-level flush
-constexpr uint32_t kGridChunks = 2;   // a workgroup handles 2 x 256 consecutive sorted colliders for one column (24 KiB of staging: 6 workgroups per CU; measured 1: 168, 2: 148, 3: 154, 4: 171 us for the broad phase)
+#ifndef MI_GRID_CHUNKS
+#define MI_GRID_CHUNKS 2
+#endif
+constexpr uint32_t kGridChunks = MI_GRID_CHUNKS;   // a workgroup handles 2 x 256 consecutive sorted colliders for one column (24 KiB of staging: 6 workgroups per CU; measured 1: 168, 2: 148, 3: 154, 4: 171 us for the broad phase)
 
 // Pair compaction: a same-address global atomic sustains only ~90 ops/us on this chip, so per-pair, per-wave or even
 // per-256-lane-block atomics on one word bound the whole broad phase.  Each lane stages its hits in LDS (24 KiB per
@@ -642,20 +654,57 @@ __device__ __forceinline__ bool bpColumnRange(uint32_t col, uint32_t i, uint32_t
     e = cellLower[cbase + (uint32_t)z1 + 1u];
     return true;
 }
-// Candidate walk of the grid pass: the rows [s, e) of the sorted arrays against the box (amn, amx), fetched kPairFetch at a time; hit(j, bmn, bmx) for every row that
-// overlaps.  (The part a faster broad phase replaces: see DESIGN.md §9.)
+// Candidate walk of the grid pass: the rows [s, e) of the sorted arrays against the collider whose compact row is `a` and whose box is (amn, amx), in windows of 64
+// candidates and two passes per window (the shape of bpPairsLargeBody's loops, for the same reason: a hit costs ~10 x a test).
+//   pass 1: ONE 16-byte compact row per candidate, 2 x kPairFetch of them per trip (as many loads in flight as the two exact rows of kPairFetch candidates were), the
+//           quantised test, a bit in a 64-bit mask.  Nothing else: no call-back, no other memory access.
+//   pass 2: the set bits in ascending order, kHitFetch per trip: the exact rows, the exact test — which alone decides what is counted and emitted — and
+//           hit(collider index of j, bmn, bmx) for the survivors; the index is word 3 of the compact row, fetched beside the exact rows (no vals[j] round trip behind them).
+// (The part a faster broad phase replaces: see DESIGN.md §9.)
+constexpr uint32_t kRowFetch = 2u * kPairFetch;
+#ifndef MI_HIT_FETCH
+#define MI_HIT_FETCH 2
+#endif
+constexpr uint32_t kHitFetch = MI_HIT_FETCH;   // set bits of pass 2 per trip (1: 58.1, 2: 55.4 us for k_bp_pairs; profiles/bp_pairs_compact_rows.txt)
+struct WalkCount { uint32_t tests = 0, passed = 0; };   // candidates tested / passed by the quantised test (read by -DMI_DBG_BP_COUNT builds only)
 template <class Hit>
-__device__ __forceinline__ void bpWalkCandidates(uint32_t s, uint32_t e, const float4& amn, const float4& amx, const float4* __restrict__ sMin, const float4* __restrict__ sMax, Hit hit) {
-    for (uint32_t j = s; j < e; j += kPairFetch) {
-        float4 bmn[kPairFetch], bmx[kPairFetch];
+__device__ __forceinline__ void bpWalkCandidates(uint32_t s, uint32_t e, const uint4& a, const float4& amn, const float4& amx, const uint4* __restrict__ sRow,
+                                                 const float4* __restrict__ sMin, const float4* __restrict__ sMax, WalkCount& wc, Hit hit) {
+    const uint32_t ra[4] = {a.x, a.y, a.z, a.w};
+    for (uint32_t w0 = s; w0 < e; w0 += 64u) {
+        const uint32_t m = min(64u, e - w0);
+        unsigned long long mask = 0ull;
+        for (uint32_t t = 0; t < m; t += kRowFetch) {
+            uint4 r[kRowFetch];
 #pragma unroll
-        for (uint32_t u = 0; u < kPairFetch; ++u) { uint32_t jj = min(j + u, e - 1u); bmn[u] = sMin[jj]; bmx[u] = sMax[jj]; }
+            for (uint32_t u = 0; u < kRowFetch; ++u) r[u] = sRow[min(w0 + t + u, e - 1u)];
+            uint32_t bits = 0u;
 #pragma unroll
-        for (uint32_t u = 0; u < kPairFetch; ++u)
-            if (j + u < e && aabbOverlap(amn, amx, bmn[u], bmx[u])) hit(j + u, bmn[u], bmx[u]);
+            for (uint32_t u = 0; u < kRowFetch; ++u) {
+                const uint32_t rb[4] = {r[u].x, r[u].y, r[u].z, r[u].w};
+                if (t + u < m && bpQuantOverlap(ra, rb)) bits |= 1u << u;
+            }
+            mask |= (unsigned long long)bits << t;
+        }
+        wc.tests += m; wc.passed += (uint32_t)__popcll(mask);
+        while (mask) {   // kHitFetch set bits per trip: their loads share one round trip
+            uint32_t jj[kHitFetch]; bool have[kHitFetch];
+#pragma unroll
+            for (uint32_t u = 0; u < kHitFetch; ++u) {
+                have[u] = mask != 0ull;
+                jj[u] = have[u] ? w0 + (uint32_t)__ffsll((long long)mask) - 1u : jj[0];   // (no further bit: the first one's rows again, not used)
+                mask &= mask - 1ull;                                                      // (0 stays 0)
+            }
+            float4 bmn[kHitFetch], bmx[kHitFetch]; uint32_t cj[kHitFetch];
+#pragma unroll
+            for (uint32_t u = 0; u < kHitFetch; ++u) { bmn[u] = sMin[jj[u]]; bmx[u] = sMax[jj[u]]; cj[u] = sRow[jj[u]].w; }
+#pragma unroll
+            for (uint32_t u = 0; u < kHitFetch; ++u)
+                if (have[u] && aabbOverlap(amn, amx, bmn[u], bmx[u])) hit(cj[u], bmn[u], bmx[u]);
+        }
     }
 }
-__device__ __forceinline__ void bpPairsGridBody(PairLds& L, const uint32_t blockId /* workgroup of the grid pass */, uint32_t nc, uint32_t blocksPerColumn, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+__device__ __forceinline__ void bpPairsGridBody(PairLds& L, const uint32_t blockId /* workgroup of the grid pass */, uint32_t nc, uint32_t blocksPerColumn, const uint32_t* __restrict__ keys, const uint4* __restrict__ sRow,
                                                 const float4* __restrict__ sMin, const float4* __restrict__ sMax,
                                                 const uint32_t* __restrict__ cellLower,
                                                 const GridParams* __restrict__ gp, uint64_t* __restrict__ pairKeys, uint32_t pairCap,
@@ -674,6 +723,7 @@ __device__ __forceinline__ void bpPairsGridBody(PairLds& L, const uint32_t block
         pairStageBegin(L);
         const uint32_t base = roundBase + ((inCol & 7u) * (blocksPerColumn >> 3) + (inCol >> 3)) * (kGridChunks * 256u);
         PairLane me; uint32_t nhit[kGridChunks];
+        WalkCount wc;
 #pragma unroll
         for (uint32_t ch = 0; ch < kGridChunks; ++ch) {
             const uint32_t i = base + ch * 256u + threadIdx.x;
@@ -681,25 +731,30 @@ __device__ __forceinline__ void bpPairsGridBody(PairLds& L, const uint32_t block
             uint32_t s, e, n = 0;
             if (key != 0xFFFFFFFFu && bpColumnRange(col, i, key, gp, cellLower, s, e) && !MI_BP_KNOCK(16) /* (knock-out harness: no candidate walk) */) {
                 const float4 amn = sMin[i], amx = sMax[i];
-                const uint32_t ci = vals[i];
-                bpWalkCandidates(s, e, amn, amx, sMin, sMax, [&](uint32_t j, const float4& bmn, const float4& bmx) {
+                const uint4 arow = sRow[i];   // the lane's OWN compact row, as the scatter wrote it (never quantised here: both sides of a test come from one function)
+                bpWalkCandidates(s, e, arow, amn, amx, sRow, sMin, sMax, wc, [&](uint32_t cj, const float4& bmn, const float4& bmx) {
                     ++me.overlaps;
                     if (MI_BP_KNOCK(17)) return;   // (no keying, no staging)
                     uint64_t pk;
-                    if (pairKey(ci, amn, amx, vals[j], bmn, bmx, axis, pk, inter)) pairStage<kPairBuf>(L, me, ch, n, pk, pairKeys, pairCap, sc);
+                    if (pairKey(arow.w, amn, amx, cj, bmn, bmx, axis, pk, inter)) pairStage<kPairBuf>(L, me, ch, n, pk, pairKeys, pairCap, sc);
                 });
             }
             nhit[ch] = n;
         }
         if (!MI_BP_KNOCK(18)) pairFlush<kGridChunks, kPairBuf>(L, me, nhit, blockId, pairKeys, pairCap, sc, sh);   // (or: no block flush)
+#ifdef MI_DBG_BP_COUNT
+        // development: candidates tested and passed by the quantised test, into the spare words of the block's shard line (pairFinishCounts sums them)
+        for (int off = 32; off >= 1; off >>= 1) { wc.tests += __shfl_xor(wc.tests, off, 64); wc.passed += __shfl_xor(wc.passed, off, 64); }
+        if ((threadIdx.x & 63u) == 0u) { ShardCounters* shard = &sh->c[blockId & (kShards - 1u)]; atomicAdd(&shard->pad[0], wc.tests); atomicAdd(&shard->pad[1], wc.passed); }
+#endif
     }
 }
 
-__global__ __launch_bounds__(256) void k_bp_pairs_grid(uint32_t nc, uint32_t blocksPerColumn, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+__global__ __launch_bounds__(256) void k_bp_pairs_grid(uint32_t nc, uint32_t blocksPerColumn, const uint32_t* __restrict__ keys, const uint4* __restrict__ sRow,
                                                        const float4* __restrict__ sMin, const float4* __restrict__ sMax, const uint32_t* __restrict__ cellLower,
                                                        const GridParams* __restrict__ gp, uint64_t* __restrict__ pairKeys, uint32_t pairCap, StepScalars* sc, Shards* sh, InterSink inter) {
     __shared__ PairLds L;
-    bpPairsGridBody(L, blockIdx.x, nc, blocksPerColumn, keys, vals, sMin, sMax, cellLower, gp, pairKeys, pairCap, sc, sh, inter);
+    bpPairsGridBody(L, blockIdx.x, nc, blocksPerColumn, keys, sRow, sMin, sMax, cellLower, gp, pairKeys, pairCap, sc, sh, inter);
 }
 
 // (Measured and not kept, round 3: the candidate rows of a workgroup's column staged in LDS — its colliders are consecutive in the cell-sorted order, so
@@ -774,7 +829,7 @@ __global__ __launch_bounds__(256) void k_bp_pairs_large(uint32_t nc, const uint3
 // issue slots half empty, the large pass (a ground and four walls against every box of a pile) is 12 us of launch floor, gathers and a block flush: as the first workgroups
 // of the grid pass's launch it runs beside that pass instead of behind it.  largeBlocks = gx * gy rounded up to a multiple of 8 (the grid pass's workgroups keep their
 // blockIdx % 8 = XCD residue); workgroups in the padding find nothing to do.
-__global__ __launch_bounds__(256) void k_bp_pairs(uint32_t largeBlocks, uint32_t gx, uint32_t gy, uint32_t nc, uint32_t blocksPerColumn, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+__global__ __launch_bounds__(256) void k_bp_pairs(uint32_t largeBlocks, uint32_t gx, uint32_t gy, uint32_t nc, uint32_t blocksPerColumn, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint4* __restrict__ sRow,
                                                   const float4* __restrict__ sMin, const float4* __restrict__ sMax, const uint32_t* __restrict__ cellLower, const GridParams* __restrict__ gp,
                                                   const uint32_t* __restrict__ largeList, const float4* __restrict__ aabbMin, const float4* __restrict__ aabbMax,
                                                   uint64_t* __restrict__ pairKeys, uint32_t pairCap, StepScalars* sc, Shards* sh, InterSink inter) {
@@ -782,7 +837,7 @@ __global__ __launch_bounds__(256) void k_bp_pairs(uint32_t largeBlocks, uint32_t
     if (blockIdx.x < largeBlocks) {
         if (blockIdx.x >= gx * gy) return;
         bpPairsLargeBody(L, blockIdx.x % gx, blockIdx.x / gx, gx, gy, nc, largeList, aabbMin, aabbMax, vals, sMin, sMax, cellLower, gp, pairKeys, pairCap, sc, sh, inter);
-    } else bpPairsGridBody(L, blockIdx.x - largeBlocks, nc, blocksPerColumn, keys, vals, sMin, sMax, cellLower, gp, pairKeys, pairCap, sc, sh, inter);
+    } else bpPairsGridBody(L, blockIdx.x - largeBlocks, nc, blocksPerColumn, keys, sRow, sMin, sMax, cellLower, gp, pairKeys, pairCap, sc, sh, inter);
 }
 // Shard totals -> StepScalars (read back by the host together with numPairs).
 // `pairBound`: what the launches / scans / buffers downstream are sized for.  A speculative step that found more pairs is
@@ -884,6 +939,9 @@ __device__ __forceinline__ uint32_t pairFinishCounts(const uint32_t t /* lane of
     uint32_t v = 0;
     if (t < kNumBuckets) { for (uint32_t k = 0; k < kShards; ++k) v += sh->c[k].bucketHist[t]; sc->bucketHist[t] = v; }
     if (t == 31) { uint32_t o = 0; for (uint32_t k = 0; k < kShards; ++k) o += sh->c[k].numOverlaps; sc->numOverlaps = o; }
+#ifdef MI_DBG_BP_COUNT
+    if (t == 30) { uint32_t a = 0, b = 0; for (uint32_t k = 0; k < kShards; ++k) { a += sh->c[k].pad[0]; b += sh->c[k].pad[1]; } sc->reserved14[0] = a; sc->reserved14[1] = b; }
+#endif
     uint32_t off = 0, nonEmpty = 0, lo = 0xFFFFFFFFu, hi = 0, largest = 0;
     for (uint32_t bk = 0; bk < kNumBuckets; ++bk) {   // every lane walks the buckets (the counts come over by shuffle), lane 0 writes
         const uint32_t n = (uint32_t)__shfl((int)v, (int)bk, 64);

@@ -283,6 +283,7 @@ struct mi_world {
     DBuf<uint32_t> largeList, isLarge, cellKeys, cellRanks, cellKeysS, cellValsS, cellCount, cellLower;
     DBuf<int> blockBounds;
     DBuf<float4> sMin, sMax;
+    DBuf<uint4> sRow;   // compact candidate rows of the grid pass, cell-sorted like sMin / sMax (bp_quant.hpp)
     DBuf<GridParams> grid;   // [2]: the grid a step uses and the one its k_pair_finish prepares for the next step
     uint32_t gridCur = 0; bool gridValid = false; uint32_t gridNextCells = 0; DBuf<char> scalarsRaw; DBuf<Shards> shards;   // scalarsRaw = [StepScalars][colouring round flags]: one read-back
     StepScalars* scalarsPtr() { return reinterpret_cast<StepScalars*>(scalarsRaw.p); }

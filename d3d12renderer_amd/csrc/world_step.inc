@@ -488,7 +488,7 @@ int mi_world::stageBroad(StepAttempt& a) {
     HIP_TRY(scanCells.run(L, cellCount.p, cellLower.p, cellCap, st, true));
     const bool skipBlocks = a.blockSkip && a.prepared;   // (the dead blocks' flags come from k_bp_prepare)
     L.launch(skipBlocks ? k_bp_scatter_sorted<true> : k_bp_scatter_sorted<false>, dim3(skipBlocks ? bodyGrid(a, divUp(nc, B)) : divUp(nc, B)), dim3(B), 0, st,
-             nc, cellKeys.p, cellRanks.p, cellLower.p, aabbMin.p, aabbMax.p, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, skipBlocks ? shard.cbLive.p : nullptr);
+             nc, cellKeys.p, cellRanks.p, cellLower.p, aabbMin.p, aabbMax.p, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, gridUse, sRow.p, skipBlocks ? shard.cbLive.p : nullptr);
     if (pairKeys.cap == 0) { HIP_TRY(pairKeys.ensure(std::max<size_t>(1u << 16, 8 * (size_t)nc))); }
     if (spec) { HIP_TRY(pairKeys.ensure(specBound(last.numPairs, 4096))); }
     if (usesInteractions && interKeys.cap == 0) HIP_TRY(interKeys.ensure(4096));
@@ -505,9 +505,9 @@ int mi_world::stageBroad(StepAttempt& a) {
 #endif
         if (knobs.fuseLarge) {   // both passes in one launch, the large one in its first workgroups (k_bp_pairs)
             const uint32_t largeBlocks = (largeGx * largeGy + 7u) & ~7u;
-            L.launch(k_bp_pairs, dim3(largeBlocks + 5u * bpc), dim3(B), 0, st, largeBlocks, largeGx, largeGy, nc, bpc, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, largeList.p, aabbMin.p, aabbMax.p, pairKeys.p, cap, sc, shards.p, inter);
+            L.launch(k_bp_pairs, dim3(largeBlocks + 5u * bpc), dim3(B), 0, st, largeBlocks, largeGx, largeGy, nc, bpc, cellKeysS.p, cellValsS.p, sRow.p, sMin.p, sMax.p, cellLower.p, gridUse, largeList.p, aabbMin.p, aabbMax.p, pairKeys.p, cap, sc, shards.p, inter);
         } else {
-            L.launch(k_bp_pairs_grid, dim3(5u * bpc), dim3(B), 0, st, nc, bpc, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, pairKeys.p, cap, sc, shards.p, inter);
+            L.launch(k_bp_pairs_grid, dim3(5u * bpc), dim3(B), 0, st, nc, bpc, cellKeysS.p, sRow.p, sMin.p, sMax.p, cellLower.p, gridUse, pairKeys.p, cap, sc, shards.p, inter);
             L.launch(k_bp_pairs_large, dim3(largeGx, largeGy), dim3(B), 0, st, nc, largeList.p, aabbMin.p, aabbMax.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, pairKeys.p, cap, sc, shards.p, inter);
         }
         // (a box pile: nearly every pair is of one type and k_pair_finish decides against partitioning — k_pair_partition then does nothing but cost its
@@ -1079,6 +1079,9 @@ void mi_world::commitStep(const StepAttempt& a) {
     lastPartitioned = hs.partitioned != 0u; havePartitionFlag = a.pairBound != 0u;
 
     counts.num_rigid_bodies = nb; counts.num_colliders = nc; counts.num_broadphase_overlaps = nc ? hs.numOverlaps : 0;
+#ifdef MI_DBG_BP_COUNT
+    fprintf(stderr, "bp_count: candidates tested %u, passed the quantised test %u, AABB overlaps (both passes) %u, small colliders %u\n", hs.reserved14[0], hs.reserved14[1], hs.numOverlaps, nc - hs.numLarge - hs.numDead);
+#endif
     manifoldsLast = a.pairBound ? hs.numManifolds : 0;
     counts.num_collisions = manifoldsLast - (manifoldsLast ? hs.numHmManifolds - hs.numHmColliders : 0u);   // terrain: one collision per collider (heightmap_collision.cpp:582-594)
     counts.num_contacts = a.pairBound ? hs.numContacts : 0;
@@ -1137,7 +1140,7 @@ int mi_world::dbgKnockBroad(uint32_t bpc, uint32_t cap, GridParams* gridUse) {
     HIP_TRY(hipMemcpyAsync(knockSc.p, scalarsPtr(), sizeof(StepScalars), hipMemcpyDeviceToDevice, st)); HIP_TRY(hipMemsetAsync(knockSh.p, 0, sizeof(Shards), st));
     const uint32_t word = (knobs.knockout >> 16) >= 0x80u ? 0u : (knobs.knockout & 0xFF0000u);   // (0x800000: nothing removed)
     return dbgKnockLaunch(knockBp, word, [&]() {
-        hipLaunchKernelGGL(k_bp_pairs_grid, dim3(5u * bpc), dim3(256), 0, st, (uint32_t)colliders.size(), bpc, cellKeysS.p, cellValsS.p, sMin.p, sMax.p, cellLower.p, gridUse, knockPairs.p, cap, reinterpret_cast<StepScalars*>(knockSc.p), reinterpret_cast<Shards*>(knockSh.p), InterSink{nullptr, 0u, nullptr});
+        hipLaunchKernelGGL(k_bp_pairs_grid, dim3(5u * bpc), dim3(256), 0, st, (uint32_t)colliders.size(), bpc, cellKeysS.p, sRow.p, sMin.p, sMax.p, cellLower.p, gridUse, knockPairs.p, cap, reinterpret_cast<StepScalars*>(knockSc.p), reinterpret_cast<Shards*>(knockSh.p), InterSink{nullptr, 0u, nullptr});
     });
 }
 // k_emit_manifolds (g_dbgKnock bits 8-12), its read-modify-write targets (per-body colour masks, the next history table, round-0 proposals, round flags) redirected
