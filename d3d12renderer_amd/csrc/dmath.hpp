@@ -41,8 +41,12 @@ struct M3 {
     MI_HD static M3 identity() { M3 m = zero(); m.m00 = m.m11 = m.m22 = 1.f; return m; }
 };
 
-MI_HD float fminr(float a, float b) { return a < b ? a : b; }   // Windows min/max macros
-MI_HD float fmaxr(float a, float b) { return a > b ? a : b; }
+// The reference's own min / max templates (src/pch.h:57-67), not the Windows macros: BOTH compare a < b.  Which argument comes back when
+// neither a < b nor b < a holds (a NaN, zeros of opposite sign) is part of the parity contract: max(0, NaN) = 0, max(NaN, 0) = NaN,
+// max(+0, -0) = +0, so clamp(0/0, 0, 1) = 0 (closestOnSegment on a zero-length segment).  Code that restates the reference passes the
+// arguments in the reference's order; tests/dmath_minmax_check.cpp holds the table.
+MI_HD float fminr(float a, float b) { return (a < b) ? a : b; }
+MI_HD float fmaxr(float a, float b) { return (a < b) ? b : a; }
 MI_HD float clampr(float v, float l, float u) { float r = fmaxr(l, v); r = fminr(u, r); return r; }  // math.h:30
 MI_HD float clamp01(float v) { return clampr(v, 0.f, 1.f); }
 MI_HD float lerpr(float l, float u, float t) { return l + t * (u - l); }

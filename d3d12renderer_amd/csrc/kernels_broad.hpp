@@ -143,8 +143,9 @@ __global__ __launch_bounds__(256) void k_world_colliders(uint32_t nc, ColliderRo
 // ------------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ uint32_t extentBin(float ext) {
-    float l = log2f(fmaxr(ext, 1e-6f)) * 8.f + 128.f;
-    return (uint32_t)fminr(fmaxr(l, 0.f), 255.f);
+    // (the grid's own arithmetic, no restatement: argument order chosen so that a NaN extent lands in bin 0, as it always has)
+    float l = log2f(fmaxr(1e-6f, ext)) * 8.f + 128.f;
+    return (uint32_t)fminr(fmaxr(0.f, l), 255.f);
 }
 __device__ __forceinline__ float extentBinUpper(uint32_t b) { return exp2f(((float)b + 1.f - 128.f) / 8.f); }
 
@@ -205,16 +206,16 @@ struct BoxInfo { float cx = 0.f, cy = 0.f, cz = 0.f, ext = 0.f; bool dead = fals
 __device__ __forceinline__ BoxInfo boxInfo(const float4& mn, const float4& mx) {
     BoxInfo b;
     b.cx = (mn.x + mx.x) * 0.5f; b.cy = (mn.y + mx.y) * 0.5f; b.cz = (mn.z + mx.z) * 0.5f;
-    b.ext = fmaxr(fmaxr(mx.x - mn.x, mx.y - mn.y), mx.z - mn.z);
+    b.ext = fmaxr(mx.z - mn.z, fmaxr(mx.y - mn.y, mx.x - mn.x));   // (own arithmetic; this order keeps what a NaN side has always given)
     b.dead = mx.x < mn.x;
     return b;
 }
 constexpr uint32_t kBoxSmall = 0u, kBoxLarge = 1u, kBoxDead = 2u;   // what isLarge[] holds: anything non-zero keeps the collider out of the grid
 __device__ __forceinline__ uint32_t boxClass(const BoxInfo& b, float largeThreshold) { return b.dead ? kBoxDead : b.ext > largeThreshold ? kBoxLarge : kBoxSmall; }
 __device__ __forceinline__ uint32_t cellKey(const GridParams& g, const BoxInfo& b) {
-    const uint32_t ix = min((uint32_t)fmaxr(0.f, (b.cx - g.origin[0]) * g.invCell), g.dims[0] - 1u);
-    const uint32_t iy = min((uint32_t)fmaxr(0.f, (b.cy - g.origin[1]) * g.invCell), g.dims[1] - 1u);
-    const uint32_t iz = min((uint32_t)fmaxr(0.f, (b.cz - g.origin[2]) * g.invCell), g.dims[2] - 1u);
+    const uint32_t ix = min((uint32_t)fmaxr((b.cx - g.origin[0]) * g.invCell, 0.f), g.dims[0] - 1u);
+    const uint32_t iy = min((uint32_t)fmaxr((b.cy - g.origin[1]) * g.invCell, 0.f), g.dims[1] - 1u);
+    const uint32_t iz = min((uint32_t)fmaxr((b.cz - g.origin[2]) * g.invCell, 0.f), g.dims[2] - 1u);
     return (ix * g.dims[1] + iy) * g.dims[2] + iz;
 }
 // Extent histogram of the LIVE colliders (it only steers the cell size, never results; its total = live colliders: the dead ones of a sharded world stay out).  A block

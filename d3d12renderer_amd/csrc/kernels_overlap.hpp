@@ -154,7 +154,7 @@ __device__ __forceinline__ bool ovCellRange(const QueryGrid& g, const OverlapVol
     uint32_t cells = 1u;
     for (int i = 0; i < 3; ++i) {
         const float l = floorf((a[i] - o[i]) * g.invCell), h = floorf((b[i] - o[i]) * g.invCell);
-        lo[i] = (uint32_t)fminr(fmaxr(l, 0.f), (float)(dim[i] - 1u)); hi[i] = (uint32_t)fminr(fmaxr(h, 0.f), (float)(dim[i] - 1u));
+        lo[i] = (uint32_t)fminr(qmax(l, 0.f), (float)(dim[i] - 1u)); hi[i] = (uint32_t)fminr(qmax(h, 0.f), (float)(dim[i] - 1u));
         cells *= hi[i] - lo[i] + 1u;
         if (cells > kOvMaxCells) return false;
     }

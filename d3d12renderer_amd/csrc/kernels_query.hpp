@@ -30,9 +30,15 @@ struct QueryGrid {
 
 __device__ __forceinline__ bool qFinite(float v) { return fabsf(v) <= FLT_MAX; }
 
+// The queries' own arithmetic (grids, slabs, the sweep's tolerances) restates no reference code: its max keeps the second argument when
+// the two do not compare (a NaN, zeros of opposite sign), whatever dmath.hpp's fmaxr, which follows the reference's template, returns.
+__device__ __forceinline__ float qmax(float a, float b) { return a > b ? a : b; }
+__device__ __forceinline__ float qclamp01(float v) { return fminr(1.f, qmax(0.f, v)); }
+__device__ __forceinline__ V3 qvmax(V3 a, V3 b) { return V3(qmax(a.x, b.x), qmax(a.y, b.y), qmax(a.z, b.z)); }
+
 __device__ __forceinline__ float qExtent(float4 mn, float4 mx) {
     if (!(qFinite(mn.x) && qFinite(mn.y) && qFinite(mn.z) && qFinite(mx.x) && qFinite(mx.y) && qFinite(mx.z))) return -1.f;
-    return fmaxr(mx.x - mn.x, fmaxr(mx.y - mn.y, mx.z - mn.z));
+    return qmax(mx.x - mn.x, qmax(mx.y - mn.y, mx.z - mn.z));
 }
 
 // Grid parameters: cell size = the mean extent of the colliders no larger than 4 x the mean extent of all; bounds = those colliders'
@@ -44,7 +50,7 @@ __device__ __forceinline__ QPartial qEmptyPartial() { QPartial p; p.sum = p.cnt 
 __device__ __forceinline__ void qCombine(QPartial& a, const QPartial& b) {
     a.sum += b.sum; a.cnt += b.cnt;
     a.mnx = fminr(a.mnx, b.mnx); a.mny = fminr(a.mny, b.mny); a.mnz = fminr(a.mnz, b.mnz);
-    a.mxx = fmaxr(a.mxx, b.mxx); a.mxy = fmaxr(a.mxy, b.mxy); a.mxz = fmaxr(a.mxz, b.mxz);
+    a.mxx = qmax(a.mxx, b.mxx); a.mxy = qmax(a.mxy, b.mxy); a.mxz = qmax(a.mxz, b.mxz);
 }
 // tree reduction of one partial per thread (blockDim.x a power of two, <= kQParamThreads); the result in sP[0]
 __device__ __forceinline__ void qBlockReduce(QPartial* sP, QPartial mine) {
@@ -99,15 +105,15 @@ __global__ __launch_bounds__(kQParamThreads) void k_q_params(uint32_t numPartial
     QueryGrid q{};
     q.largeExtent = g->largeExtent;
     if (r.cnt > 0.f) {
-        float cell = fmaxr(r.sum / r.cnt, 1e-3f);
+        float cell = qmax(r.sum / r.cnt, 1e-3f);
         const V3 lo(r.mnx, r.mny, r.mnz), hi(r.mxx, r.mxy, r.mxz);
-        const float scale = fmaxr(fmaxr(fabsf(lo.x), fabsf(hi.x)), fmaxr(fmaxr(fabsf(lo.y), fabsf(hi.y)), fmaxr(fabsf(lo.z), fabsf(hi.z))));
+        const float scale = qmax(qmax(fabsf(lo.x), fabsf(hi.x)), qmax(qmax(fabsf(lo.y), fabsf(hi.y)), qmax(fabsf(lo.z), fabsf(hi.z))));
         for (int it = 0; it < 64; ++it) {
             const float margin = 2e-3f * cell + 4e-6f * scale;
             const V3 ext = hi - lo + V3(4.f * margin);
-            const float dx = fmaxr(1.f, ceilf(ext.x / cell)), dy = fmaxr(1.f, ceilf(ext.y / cell)), dz = fmaxr(1.f, ceilf(ext.z / cell));
+            const float dx = qmax(1.f, ceilf(ext.x / cell)), dy = qmax(1.f, ceilf(ext.y / cell)), dz = qmax(1.f, ceilf(ext.z / cell));
             const double cells = (double)dx * (double)dy * (double)dz;
-            if (cells > (double)maxCells) { cell *= fmaxr(1.01f, (float)cbrt(cells / (double)maxCells) * 1.01f); continue; }
+            if (cells > (double)maxCells) { cell *= qmax(1.01f, (float)cbrt(cells / (double)maxCells) * 1.01f); continue; }
             q.minX = lo.x - 2.f * margin; q.minY = lo.y - 2.f * margin; q.minZ = lo.z - 2.f * margin;
             q.cell = cell; q.invCell = 1.f / cell; q.margin = margin;
             q.dimX = (uint32_t)dx; q.dimY = (uint32_t)dy; q.dimZ = (uint32_t)dz; q.numCells = q.dimX * q.dimY * q.dimZ;
@@ -126,7 +132,7 @@ __device__ __forceinline__ bool qCellRange(const QueryGrid& g, float4 mn, float4
     uint32_t cells = 1u;
     for (int i = 0; i < 3; ++i) {
         const float l = floorf((a[i] - g.margin - o[i]) * g.invCell), h = floorf((b[i] + g.margin - o[i]) * g.invCell);
-        lo[i] = (uint32_t)fminr(fmaxr(l, 0.f), (float)(dim[i] - 1u)); hi[i] = (uint32_t)fminr(fmaxr(h, 0.f), (float)(dim[i] - 1u));
+        lo[i] = (uint32_t)fminr(qmax(l, 0.f), (float)(dim[i] - 1u)); hi[i] = (uint32_t)fminr(qmax(h, 0.f), (float)(dim[i] - 1u));
         cells *= hi[i] - lo[i] + 1u;
         if (cells > kQMaxCellsPerCollider) return false;
     }
@@ -314,14 +320,14 @@ __device__ inline bool qTerrainWalk(const HeightmapParams& hm, V3 o, V3 d, float
     const float s = hm.chunkScale, x0 = hm.minX, z0 = hm.minZ, x1 = x0 + (float)hm.chunksPerDim * hm.chunkSize, z1 = z0 + (float)hm.chunksPerDim * hm.chunkSize;
     float tIn = 0.f, tOut = FLT_MAX;
     if (d.x == 0.f) { if (o.x < x0 || o.x > x1) return false; }
-    else { const float a = (x0 - o.x) / d.x, b = (x1 - o.x) / d.x; tIn = fmaxr(tIn, fminr(a, b)); tOut = fminr(tOut, fmaxr(a, b)); }
+    else { const float a = (x0 - o.x) / d.x, b = (x1 - o.x) / d.x; tIn = qmax(tIn, fminr(a, b)); tOut = fminr(tOut, qmax(a, b)); }
     if (d.z == 0.f) { if (o.z < z0 || o.z > z1) return false; }
-    else { const float a = (z0 - o.z) / d.z, b = (z1 - o.z) / d.z; tIn = fmaxr(tIn, fminr(a, b)); tOut = fminr(tOut, fmaxr(a, b)); }
+    else { const float a = (z0 - o.z) / d.z, b = (z1 - o.z) / d.z; tIn = qmax(tIn, fminr(a, b)); tOut = fminr(tOut, qmax(a, b)); }
     const float tDom = tOut;
     tOut = fminr(tOut, tMax);
     if (!(tIn <= tOut)) return false;
     const float px = o.x + tIn * d.x, pz = o.z + tIn * d.z;
-    int gx = (int)fminr(fmaxr(floorf((px - x0) / s), 0.f), (float)(n - 1u)), gz = (int)fminr(fmaxr(floorf((pz - z0) / s), 0.f), (float)(n - 1u));
+    int gx = (int)fminr(qmax(floorf((px - x0) / s), 0.f), (float)(n - 1u)), gz = (int)fminr(qmax(floorf((pz - z0) / s), 0.f), (float)(n - 1u));
     const int sx = d.x > 0.f ? 1 : -1, sz = d.z > 0.f ? 1 : -1;
     const float eps = 1e-3f / hm.invAmplitudeScale + 1e-5f * fabsf(o.y);
     bool found = false, blockMiss = false;
@@ -342,7 +348,7 @@ __device__ inline bool qTerrainWalk(const HeightmapParams& hm, V3 o, V3 d, float
             const float bzOut = d.z == 0.f ? FLT_MAX : ((d.z > 0.f ? bz0 + 8.f * s : bz0) - o.z) / d.z;
             const float tb = fminr(fminr(bxOut, bzOut), tDom);
             const float ya = o.y + tCell * d.y, yb = o.y + tb * d.y;
-            blockMiss = fminr(ya, yb) > hmax + eps || fmaxr(ya, yb) < hmin - eps;
+            blockMiss = fminr(ya, yb) > hmax + eps || qmax(ya, yb) < hmin - eps;
         }
         if (test && useBounds && blockMiss) test = false;
         if (test && useBounds) {
@@ -350,7 +356,7 @@ __device__ inline bool qTerrainWalk(const HeightmapParams& hm, V3 o, V3 d, float
             const float hmin = (float)(mm & 0xFFFFu) * hm.heightScale + hm.minY, hmax = (float)(mm >> 16) * hm.heightScale + hm.minY;
             const float ta = tCell, tb = fminr(tExit, tDom);
             const float ya = o.y + ta * d.y, yb = o.y + tb * d.y;
-            if (fminr(ya, yb) > hmax + eps || fmaxr(ya, yb) < hmin - eps) test = false;
+            if (fminr(ya, yb) > hmax + eps || qmax(ya, yb) < hmin - eps) test = false;
         }
         if (test)
             for (uint32_t tri = 0; tri < 2u; ++tri) {
@@ -384,7 +390,7 @@ __device__ inline V3 qLocalNormal(uint32_t type, float4 s0, float4 s1, float4 s2
         case T_SPHERE: return h - xyz(s0);
         case T_CAPSULE: {
             const V3 pa = xyz(s0), pb(s0.w, s1.x, s1.y), ab = pb - pa;
-            const float aa = dot(ab, ab), u = aa > 0.f ? clamp01(dot(h - pa, ab) / aa) : 0.f;
+            const float aa = dot(ab, ab), u = aa > 0.f ? qclamp01(dot(h - pa, ab) / aa) : 0.f;
             return h - (pa + u * ab);
         }
         case T_CYLINDER: {
@@ -458,12 +464,12 @@ __global__ __launch_bounds__(256) void k_q_raycast(uint32_t count, const float* 
             for (int a = 0; a < 3; ++a) {
                 const float lo = mn[a], hi = mn[a] + (float)dim[a] * g.cell;
                 if (d[a] == 0.f) { if (o[a] < lo || o[a] > hi) inside = false; }
-                else { const float t0 = (lo - o[a]) / d[a], t1 = (hi - o[a]) / d[a]; tIn = fmaxr(tIn, fminr(t0, t1)); tOut = fminr(tOut, fmaxr(t0, t1)); }
+                else { const float t0 = (lo - o[a]) / d[a], t1 = (hi - o[a]) / d[a]; tIn = qmax(tIn, fminr(t0, t1)); tOut = fminr(tOut, qmax(t0, t1)); }
             }
             if (inside && tIn <= tOut) {
                 int c[3], st[3];
                 for (int a = 0; a < 3; ++a) {
-                    c[a] = (int)fminr(fmaxr(floorf((o[a] + tIn * d[a] - mn[a]) * g.invCell), 0.f), (float)(dim[a] - 1u));
+                    c[a] = (int)fminr(qmax(floorf((o[a] + tIn * d[a] - mn[a]) * g.invCell), 0.f), (float)(dim[a] - 1u));
                     st[a] = d[a] > 0.f ? 1 : -1;
                 }
                 for (uint32_t it = 0; it < g.dimX + g.dimY + g.dimZ + 3u; ++it) {

@@ -61,7 +61,7 @@ __device__ inline V3 swSupport(const Shape& s, const HullSet& hs, V3 dir) {
     }
 }
 __device__ __forceinline__ float swMargin(const Shape& s) { return s.type <= T_CAPSULE ? s.radius : 0.f; }
-__device__ __forceinline__ float swMaxAbs(V3 a) { return fmaxr(fabsf(a.x), fmaxr(fabsf(a.y), fabsf(a.z))); }
+__device__ __forceinline__ float swMaxAbs(V3 a) { return qmax(fabsf(a.x), qmax(fabsf(a.y), fabsf(a.z))); }
 
 // The simplex: up to four points of the Minkowski difference (collider - volume) with their witnesses on the collider, in named slots (no runtime
 // indexing: it stays in registers).
@@ -105,7 +105,7 @@ __device__ inline bool swClosest(uint32_t n, V3 p0, V3 p1, V3 p2, V3 p3, SwWeigh
     w.w0 = 1.f; w.w1 = w.w2 = w.w3 = 0.f;
     if (n == 1u) { v = p0; return true; }
     if (n == 2u) {
-        const V3 e = p1 - p0; const float ee = sqlen(e), t = ee > 0.f ? clamp01(-dot(p0, e) / ee) : 0.f;
+        const V3 e = p1 - p0; const float ee = sqlen(e), t = ee > 0.f ? qclamp01(-dot(p0, e) / ee) : 0.f;
         w.w0 = 1.f - t; w.w1 = t; v = p0 * w.w0 + p1 * w.w1; return true;
     }
     if (n == 3u) { v = swTriangle(p0, p1, p2, w.w0, w.w1, w.w2); return true; }
@@ -146,10 +146,10 @@ __device__ __forceinline__ void swPush(SwSimplex& s, V3 y, V3 b) {
 __device__ inline Shape swClipBox(const Shape& b, V3 sweptMin, V3 sweptMax) {
     if (b.type != T_AABB && b.type != T_OBB) return b;
     const V3 ext = sweptMax - sweptMin;
-    const float grow = 0.05f * fmaxr(ext.x, fmaxr(ext.y, ext.z)) + 1e-3f;
+    const float grow = 0.05f * qmax(ext.x, qmax(ext.y, ext.z)) + 1e-3f;
     Shape r = b;
     if (b.type == T_AABB) {
-        const V3 lo = vmax(b.a, sweptMin - V3(grow)), hi = vmin(b.b, sweptMax + V3(grow));
+        const V3 lo = qvmax(b.a, sweptMin - V3(grow)), hi = vmin(b.b, sweptMax + V3(grow));
         if (lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z) { r.a = lo; r.b = hi; }   // (apart: the pair test says so on the whole box)
         return r;
     }
@@ -157,7 +157,7 @@ __device__ inline Shape swClipBox(const Shape& b, V3 sweptMin, V3 sweptMax) {
     const V3 c = rotate(conj(b.rot), (sweptMin + sweptMax) * 0.5f - b.a), h = ext * 0.5f + V3(grow);
     const V3 ex = vabs(rotate(conj(b.rot), V3(h.x, 0.f, 0.f))), ey = vabs(rotate(conj(b.rot), V3(0.f, h.y, 0.f))), ez = vabs(rotate(conj(b.rot), V3(0.f, 0.f, h.z)));
     const V3 e = ex + ey + ez;
-    const V3 lo = vmax(-b.b, c - e), hi = vmin(b.b, c + e);
+    const V3 lo = qvmax(-b.b, c - e), hi = vmin(b.b, c + e);
     if (lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z) { r.a = b.a + rotate(b.rot, (lo + hi) * 0.5f); r.b = (hi - lo) * 0.5f; }
     return r;
 }
@@ -186,8 +186,8 @@ __device__ __noinline__ SweepResult sweepPair(const Shape& A, V3 sweptMin, V3 sw
     float dist2 = FLT_MAX, tol = 0.f;
     for (uint32_t it = 0; it < kSweepMaxIter && !done; ++it) {
         const V3 pb = swSupport(B, hs, v), pa = swSupport(A, hs, -v), p = pb - pa;
-        scale = fmaxr(scale, fmaxr(swMaxAbs(pa), swMaxAbs(pb)));
-        tol = kSweepTolRel * fmaxr(scale, R);
+        scale = qmax(scale, qmax(swMaxAbs(pa), swMaxAbs(pb)));
+        tol = kSweepTolRel * qmax(scale, R);
         const float lv = len(v), vw = dot(v, x - p) - R * lv;
         const bool clip = vw > 0.f;
         if (clip) {   // the plane through C's support point along v separates x from C: clip the ray against it
@@ -254,7 +254,7 @@ __device__ __forceinline__ SweepCast swLoadCast(const float4* __restrict__ vShap
     c.d = V3(d4.x, d4.y, d4.z);
     c.centre = c.q.mn * 0.5f + c.q.mx * 0.5f; c.half = c.q.mx * 0.5f - c.q.mn * 0.5f;   // (halved first: bounds near FLT_MAX must not overflow into an infinite centre)
     const V3 end = c.q.mx + c.d, begin = c.q.mn + c.d;
-    c.sweptMin = vmin(c.q.mn, begin); c.sweptMax = vmax(c.q.mx, end);
+    c.sweptMin = vmin(c.q.mn, begin); c.sweptMax = qvmax(c.q.mx, end);
     c.valid = c.q.valid && qFinite(c.d.x) && qFinite(c.d.y) && qFinite(c.d.z) && qFinite(end.x) && qFinite(end.y) && qFinite(end.z) && qFinite(begin.x) && qFinite(begin.y) && qFinite(begin.z);
     return c;
 }
@@ -285,13 +285,13 @@ template <bool kSkip> __device__ inline unsigned long long swCandidate(const Ove
         const float pad = 1e-5f * (fabsf(o[i]) + fabsf(ca[i]) + fabsf(cb[i]) + 1.f);
         const float l = lo[i] - pad, h = hi[i] + pad;
         if (d[i] == 0.f) { if (l > 0.f || h < 0.f) return ~0ull; }
-        else { const float ta = l / d[i], tb = h / d[i]; t0 = fmaxr(t0, fminr(ta, tb)); t1 = fminr(t1, fmaxr(ta, tb)); }
+        else { const float ta = l / d[i], tb = h / d[i]; t0 = qmax(t0, fminr(ta, tb)); t1 = fminr(t1, qmax(ta, tb)); }
     }
     if (!(t0 <= t1) || !qFinite(t1)) return ~0ull;
     if (kSkip && t0 > bestT) return ~0ull;
     const SweepResult r = sweepPair(c.q.s, c.sweptMin, c.sweptMax, loadShape(s.shape, k, type), s.hs, c.d);
     if (!r.hit) return ~0ull;
-    const float t = (r.flags & kSweepInitialOverlap) ? 0.f : fmaxr(r.t, t0);
+    const float t = (r.flags & kSweepInitialOverlap) ? 0.f : qmax(r.t, t0);
     return ((unsigned long long)__float_as_uint(t + 0.f) << 32) | k;
 }
 __device__ __forceinline__ unsigned long long swWaveMin(unsigned long long key) {

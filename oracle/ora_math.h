@@ -52,8 +52,10 @@ static inline vec3& operator-=(vec3& a, vec3 b) { a = a - b; return a; }
 static inline vec3& operator*=(vec3& a, float b) { a = a * b; return a; }
 static inline vec3& operator/=(vec3& a, float b) { a = a / b; return a; }
 
-static inline float fmin2(float a, float b) { return a < b ? a : b; }
-static inline float fmax2(float a, float b) { return a > b ? a : b; }
+// The reference's min / max templates (src/pch.h:57-67): both compare a < b, so max(0, NaN) = 0, max(NaN, 0) = NaN, max(+0, -0) = +0.
+// Callers pass the arguments in the reference's order (tests/dmath_minmax_check.cpp holds the table).
+static inline float fmin2(float a, float b) { return (a < b) ? a : b; }
+static inline float fmax2(float a, float b) { return (a < b) ? b : a; }
 static inline float clampf(float v, float l, float u) { float r = fmax2(l, v); r = fmin2(u, r); return r; }  // math.h:30
 static inline float clamp01(float v) { return clampf(v, 0.f, 1.f); }
 static inline float lerpf(float l, float u, float t) { return l + t * (u - l); }  // math.h:27

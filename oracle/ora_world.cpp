@@ -1790,6 +1790,18 @@ MI_API int ora_debug_set_solve_order(World* w, const uint32_t* pairs, uint32_t c
     return MI_OK;
 }
 MI_API int ora_debug_set_sweep_axis(World* w, uint32_t axis) { if (!w || axis > 2u) return MI_ERR_INVALID_ARGUMENT; w->sortingAxis = axis; return MI_OK; }   // (mi_debug_set_sweep_axis)
+// The narrow phase of ONE oriented pair (A, B) of the last step's world colliders, as `intersect` itself decides it: the yardstick of an orientation the
+// step did not take (the contact query makes the volume A for equal types; the step makes A whichever AABB starts earlier).  points = 4 x (xyz, depth).
+MI_API int ora_debug_intersect(World* w, uint32_t a, uint32_t b, float* normal3, float* points16, uint32_t* count) {
+    if (!w || !normal3 || !points16 || !count || a >= w->wc.size() || b >= w->wc.size() || a == b) return MI_ERR_INVALID_ARGUMENT;
+    ContactManifold m; m.numContacts = 0;
+    bool boxes = w->aabbs.size() == w->wc.size();   // a pair reaches the narrow phase through the broad phase: closed AABBs (bounding_volumes.h:352-358)
+    for (int i = 0; boxes && i < 3; ++i) boxes = !(w->aabbs[a].mx[i] < w->aabbs[b].mn[i] || w->aabbs[a].mn[i] > w->aabbs[b].mx[i]);
+    *count = boxes && intersect(*w, w->wc[a], w->wc[b], m) ? m.numContacts : 0u;
+    normal3[0] = m.normal.x; normal3[1] = m.normal.y; normal3[2] = m.normal.z;
+    for (uint32_t i = 0; i < *count && i < 4u; ++i) { points16[4 * i] = m.points[i].x; points16[4 * i + 1] = m.points[i].y; points16[4 * i + 2] = m.points[i].z; points16[4 * i + 3] = m.depths[i]; }
+    return MI_OK;
+}
 MI_API uint32_t ora_axis_from_sums(const uint64_t* sums9, uint32_t numColliders) { return ora::axisFromSums(sums9, numColliders); }
 MI_API float ora_det_atan2f(float y, float x) { return det_atan2f(y, x); }
 MI_API float ora_det_acosf(float x) { return det_acosf(x); }

@@ -34,12 +34,43 @@ FAR_OFFSETS = (np.array([137.3, -211.7, 98.1]), np.array([1031.1, 877.3, -1204.9
 _HULLS = []
 
 
+PRISM_SIDES = 65
+
+
+def _outward(verts, tris):
+    """The triangles wound so that their normals point away from the vertex centroid."""
+    c = verts.mean(axis=0); out = []
+    for a, b, cc in tris:
+        n = np.cross(verts[b] - verts[a], verts[cc] - verts[a])
+        out.append((a, cc, b) if np.dot(n, verts[a] - c) < 0 else (a, b, cc))
+    return np.asarray(out, np.uint32)
+
+
+def _cube_hull():
+    """The unit cube (half-size 0.5) as a hull of 8 vertices: every support direction along an axis ties four ways, exactly."""
+    v = np.array([(x, y, z) for x in (-0.5, 0.5) for y in (-0.5, 0.5) for z in (-0.5, 0.5)], np.float64)
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    return v.astype(np.float32), _outward(v, [t for a, b, c, d in quads for t in ((a, b, c), (a, c, d))])
+
+
+def _prism_hull(n=PRISM_SIDES, radius=0.5, half=0.3):
+    """A prism over a regular n-gon, 2 n = 130 vertices: vertex i of the bottom cap (y = -half) and n + i of the top cap are mirror images, the
+    n vertices of a cap are coplanar exactly, and a scan in strides of 64 lanes visits every lane at least twice."""
+    ang = 2.0 * np.pi * np.arange(n) / n
+    ring = np.stack([radius * np.cos(ang), np.zeros(n), radius * np.sin(ang)], axis=1)
+    v = np.concatenate([ring - (0, half, 0), ring + (0, half, 0)])
+    tris = [(0, i, i + 1) for i in range(1, n - 1)] + [(n, n + i, n + i + 1) for i in range(1, n - 1)]
+    tris += [t for i in range(n) for j in [(i + 1) % n] for t in ((i, j, n + j), (i, n + j, n + i))]
+    return v.astype(np.float32), _outward(v.astype(np.float32).astype(np.float64), tris)
+
+
 def hulls():
     """The hull geometries of every matrix world: 0 = overlap_ref.volume_hull() (radius 0.6); 1 = the same 30 times larger with its vertices
-    tens of units from its origin; 2 = the same at a size of 1e-2."""
+    tens of units from its origin; 2 = the same at a size of 1e-2; 3 = the unit cube; 4 = a prism of 130 vertices (tests/contact_matrix.py)."""
     if not _HULLS:
         v, t = R.volume_hull()
-        _HULLS.extend([(v, t), ((v.astype(np.float64) * 30.0 + (25.0, 10.0, -15.0)).astype(np.float32), t), ((v.astype(np.float64) / 120.0).astype(np.float32), t)])
+        _HULLS.extend([(v, t), ((v.astype(np.float64) * 30.0 + (25.0, 10.0, -15.0)).astype(np.float32), t), ((v.astype(np.float64) / 120.0).astype(np.float32), t),
+                       _cube_hull(), _prism_hull()])
     return _HULLS
 
 
