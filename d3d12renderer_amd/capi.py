@@ -944,6 +944,17 @@ class World:
         self.L.check(self.L.fn("debug_step_graph_stats")(self.h, out), "debug_step_graph_stats")
         return tuple(int(x) for x in out)
 
+    def debug_exclusive_scan(self, values, zero_input=False):
+        """mi_debug_exclusive_scan: the step's device-wide exclusive prefix sum over a uint32 or uint64 array (uint64 = two 32-bit sums side by side), through the
+        step's own scan sites.  Returns (prefix sums, the input array as the kernel left it)."""
+        a = np.array(values, copy=True, order="C")
+        if a.dtype not in (np.uint32, np.uint64) or a.ndim != 1:
+            raise TypeError("a one-dimensional uint32 or uint64 array")
+        out = np.empty_like(a)
+        self.L.check(self.L.fn("debug_exclusive_scan")(self.h, C.c_uint32(8 * a.itemsize), C.c_void_p(a.ctypes.data if a.size else None), C.c_uint32(a.size),
+                                                       C.c_uint32(1 if zero_input else 0), C.c_void_p(out.ctypes.data if a.size else None)), "debug_exclusive_scan")
+        return out, a
+
     def solver_kind(self):
         """mi_world_get_solver_kind: 0 per-colour launches, 1 flow, 2 persistent, 3 flow + joint islands, 4 persistent, XCD-partitioned, 5 persistent, all tiles on one XCD (small piles)."""
         k = C.c_uint32()

@@ -197,6 +197,45 @@ __device__ __forceinline__ void axisWaveReduce(unsigned long long v[kAxisSums], 
     }
     if ((threadIdx.x & 63u) == 0u) { for (uint32_t c = 0; c < kAxisSums; ++c) sm[threadIdx.x >> 6][c] = v[c]; }
 }
+// ---- the same wave reductions without the LDS crossbar (k_bp_prepare): four DPP row shifts and two row broadcasts per 32-bit word, the result in lane 63 ----
+// (The __shfl_down / __shfl_xor forms above go through ds_bpermute wherever the compiler finds no DPP form: k_bp_prepare issued 158 LDS instructions per wave with them
+// and issues 19 with these, 27.2 -> 23.2 us; profiles/streaming_passes.txt.)  Every lane of the wave must be active.
+template <class Op> __device__ __forceinline__ uint32_t dppReduce63(uint32_t v, uint32_t identity, Op op) {
+    // a lane without a source (row_shr at a row's start, the rows a broadcast leaves out) reads `identity`
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, 0x111, 0xF, 0xF, false));   // row_shr:1
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, 0x112, 0xF, 0xF, false));   // row_shr:2
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, 0x114, 0xF, 0xF, false));   // row_shr:4
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, 0x118, 0xF, 0xF, false));   // row_shr:8: lane 15 of a row holds the row
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, 0x142, 0xA, 0xF, false));   // row_bcast:15 into rows 1 and 3
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, 0x143, 0xC, 0xF, false));   // row_bcast:31 into rows 2 and 3: lane 63 holds the wave
+    return v;
+}
+// The nine sums of axisAccumulate as 16-bit limbs, which a 32-bit sum over 64 lanes cannot overflow: per axis q + 2^30 (q lies in [-2^30, 2^30]; the bias comes off
+// again with the number of counted lanes), the low word of q^2 and the rest of q^2 (< 2^29), two limbs each.  Integer sums: the same nine 64-bit words as
+// axisWaveReduce, bit for bit, in sm[wave].
+__device__ __forceinline__ void axisWaveReduceDpp(bool counted, float cx, float cy, float cz, unsigned long long (*sm)[kAxisSums]) {
+    const float c[3] = {cx, cy, cz};
+    const uint32_t n = (uint32_t)__popcll(__ballot(counted));
+    auto add = [](uint32_t a, uint32_t b) { return a + b; };
+#pragma unroll
+    for (uint32_t a = 0; a < 3; ++a) {
+        unsigned long long q = 0ull, lo = 0ull, hi = 0ull;
+        if (counted) axisTerms(c[a], q, lo, hi);
+        const uint32_t u = counted ? (uint32_t)((long long)q + (1ll << 30)) : 0u;
+        const uint32_t w[3] = {u, (uint32_t)lo, (uint32_t)hi};
+        unsigned long long sum[3];
+#pragma unroll
+        for (uint32_t k = 0; k < 3; ++k) {
+            const uint32_t l0 = dppReduce63(w[k] & 0xFFFFu, 0u, add), l1 = dppReduce63(w[k] >> 16, 0u, add);
+            sum[k] = (unsigned long long)l0 + ((unsigned long long)l1 << 16);
+        }
+        if ((threadIdx.x & 63u) == 63u) {
+            sm[threadIdx.x >> 6][a] = sum[0] - ((unsigned long long)n << 30);
+            sm[threadIdx.x >> 6][3 + a] = sum[1];
+            sm[threadIdx.x >> 6][6 + a] = sum[2];
+        }
+    }
+}
 __device__ __forceinline__ unsigned long long axisBlockSum(const unsigned long long (*sm)[kAxisSums], uint32_t c) { return sm[0][c] + sm[1][c] + sm[2][c] + sm[3][c]; }
 
 // ---- what the classification kernels share, lane by lane (first step: k_axis_partials, k_bp_classify, k_bp_cell_ids; later steps: k_bp_prepare) ----
@@ -239,6 +278,14 @@ __device__ __forceinline__ void boundsWaveReduce(int v[6], int (*rows)[6]) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) boundsMerge(v, a, __shfl_xor(v[a], d, 64));
     if ((threadIdx.x & 63u) == 0u) for (int a = 0; a < 6; ++a) rows[threadIdx.x >> 6][a] = v[a];
+}
+__device__ __forceinline__ void boundsWaveReduceDpp(const int v[6], int (*rows)[6]) {   // (boundsWaveReduce without the LDS crossbar, see dppReduce63)
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        const int r = a < 3 ? (int)dppReduce63((uint32_t)v[a], (uint32_t)boundsEmpty(a), [](uint32_t x, uint32_t y) { return (uint32_t)min((int)x, (int)y); })
+                            : (int)dppReduce63((uint32_t)v[a], (uint32_t)boundsEmpty(a), [](uint32_t x, uint32_t y) { return (uint32_t)max((int)x, (int)y); });
+        if ((threadIdx.x & 63u) == 63u) rows[threadIdx.x >> 6][a] = r;
+    }
 }
 __device__ __forceinline__ int boundsOfRows(const int (*rows)[6], int a) {
     int x = rows[0][a];
@@ -412,7 +459,7 @@ __global__ __launch_bounds__(256) void k_bp_prepare(uint32_t nc, ColliderRows ro
   if (fused && blockIdx.x == 0 && threadIdx.x == 0) sc->axisCur = axisDev ? *axisDev : axisCur;
   // (one workgroup per collider block unless the world is sharded: then the workgroups stride over the blocks that are live)
   forLiveBlocks<STRIDED>(blockIdx.x, gridDim.x, (nc + 255u) / 256u, [&](uint32_t cb) { return colliderBlockLive(skip, cb); }, [&](uint32_t cb) {
-    __syncthreads();   // (the previous block's shared results have been read)
+    if constexpr (STRIDED) __syncthreads();   // (the previous block's shared results have been read; without the loop there is no previous block)
     hist[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t i = cb * 256 + threadIdx.x;
@@ -429,33 +476,34 @@ __global__ __launch_bounds__(256) void k_bp_prepare(uint32_t nc, ColliderRows ro
         }
     }
     const GridParams g = *gp;
-    unsigned long long v[kAxisSums];
     int bounds[6];
     for (int a = 0; a < 6; ++a) bounds[a] = boundsEmpty(a);
-    BoxInfo b; bool counted = false;
+    BoxInfo b; bool counted = false, keep = false;
+    uint32_t rank = 0;
     if (i < nc) {
         float4 mn, mx;
         if (fused) worldCollider(i, rows, mn, mx);
         else { mn = rows.aabbMin[i]; mx = rows.aabbMax[i]; }
         b = boxInfo(mn, mx);
+        // the cell histogram's atomic goes out as soon as its key is known; only ranks[i] waits for what it returns, and that store is the kernel's last
+        uint32_t key = 0xFFFFFFFFu;
+        if (boxClass(b, g.largeThreshold) == kBoxSmall) { key = cellKey(g, b); rank = atomicAdd(&cellCount[key], 1u); }
         counted = axisCounted(mn, mx, bodyActive, countUnowned);
         extentCount(hist, b);   // steers the NEXT step's cell size; pairFinishStats derives numDead from its total (a counter bumped once per wave of dead colliders
                                 // cost 0.3 ms in an 8-tile world, ~90 same-address atomics per us)
         // a collider that was dead in the previous step too already has (2, 0xFFFFFFFF, 0) in these rows
-        const bool stale = b.dead && bodyActivePrev && !bodyActivePrev[__float_as_uint(mx.w)];
+        keep = !(b.dead && bodyActivePrev && !bodyActivePrev[__float_as_uint(mx.w)]);
         const uint32_t cls = classifyBox(i, b, g.largeThreshold, sc, largeList, bounds);
-        uint32_t key = 0xFFFFFFFFu, rank = 0;
-        if (cls == kBoxSmall) { key = cellKey(g, b); rank = atomicAdd(&cellCount[key], 1u); }
-        if (!stale) { isLarge[i] = cls; keys[i] = key; ranks[i] = rank; }
+        if (keep) { isLarge[i] = cls; keys[i] = key; }
     }
-    axisAccumulate(counted, b.cx, b.cy, b.cz, v);
-    axisWaveReduce(v, sm);
-    boundsWaveReduce(bounds, sb);
+    axisWaveReduceDpp(counted, b.cx, b.cy, b.cz, sm);
+    boundsWaveReduceDpp(bounds, sb);
     const int anyAlive = __syncthreads_or((i < nc && !b.dead) ? 1 : 0);
     if (skip.cbLive && threadIdx.x == 0) skip.cbLive[cb] = anyAlive ? 1u : 0u;
     extentFlush(hist, sh, cb);
     if (threadIdx.x < kAxisSums) partials[cb * kAxisSums + threadIdx.x] = axisBlockSum(sm, threadIdx.x);
     if (threadIdx.x < 6) blockBounds[cb * 6 + threadIdx.x] = boundsOfRows(sb, threadIdx.x);
+    if (keep) ranks[i] = rank;
   });
 }
 

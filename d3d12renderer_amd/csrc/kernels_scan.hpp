@@ -8,28 +8,45 @@ namespace mi {
 // Device-wide exclusive prefix sum, ONE launch: chained scan with decoupled look-back.
 //   * a workgroup takes its tile number from a ticket counter (so a tile's predecessors have always started), scans its
 //     kScanTile items in registers / LDS and publishes first its AGGREGATE, then — after looking back over its predecessors'
-//     records (one wave, 64 records at a time, until an inclusive prefix is found) — its INCLUSIVE PREFIX;
-//   * a record is ONE 64-bit word (tag << 32 | 32-bit sum), tag = generation << 2 | state (1 aggregate, 2 inclusive), written
-//     and read with single relaxed agent-scope accesses: a reader that sees the tag sees the sum of the same store — no fences
-//     (a release / acquire pair at agent scope would write back / invalidate the L2 around every record);
+//     records (one wave, kScanLookWindows x 64 records per round, until an inclusive prefix is found) — its INCLUSIVE PREFIX;
+//   * a record is ONE aligned 16-byte granule (sum low word, sum high word, tag, tag), tag = generation << 2 | state (1 aggregate,
+//     2 inclusive), written with one `sc1` (agent-scope, write-through) 16-byte store and read with one `sc1` 16-byte load, as the
+//     contact solver's body granules are (kernels_solve.hpp): a reader that sees the tag sees the sum of the same store — no fences
+//     (a release / acquire pair at agent scope would write back / invalidate the L2 around every record), no second load, no check
+//     that two halves belong together;
 //   * records are never reset: a reader ignores tags of older generations, and the ticket counter only ever grows
 //     (`state[0]` = tickets handed out before this launch, `state[1]` = generation; the host clears everything long before the 30 generation bits wrap).
-// T = uint32_t (W = 1) or a 64-bit word holding two independent 32-bit sums side by side (W = 2: the narrow phase's packed
+// T = uint32_t or a 64-bit word holding two independent 32-bit sums side by side (the narrow phase's packed
 // (manifold flag, contact count); both totals stay below 2^32, so the halves never carry into each other).
 constexpr uint32_t kScanThreads = 256;
-// items per lane: the long 64-bit scan (one item per collision pair) takes 16 — half the tiles, half the look-back chain (16.3 -> 13.7 us
-// at 750 k pairs); the short 32-bit ones (cell histogram, schedule bins) are faster with 8 (6 vs 9 us)
-template <typename T> struct ScanItems { static constexpr uint32_t N = sizeof(T) == 8 ? 16u : 8u; static constexpr uint32_t Tile = kScanThreads * N; };
-__device__ __forceinline__ void scanPublish(unsigned long long* rec, uint32_t sum, uint32_t tag) {
-    __hip_atomic_store(rec, ((unsigned long long)tag << 32) | (unsigned long long)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// items per lane, measured per width (profiles/streaming_passes.txt): the 64-bit pair scan 9.8 us with 16 against 14.0 with 8 (twice the tiles, twice the tickets on one
+// counter); the short 32-bit ones (cell histogram, schedule bins) 5.4 us with 8, 5.6 with 16, 6.0 with 4
+constexpr uint32_t kScanItems64 = 16, kScanItems32 = 8;
+template <typename T> struct ScanItems { static constexpr uint32_t N = sizeof(T) == 8 ? kScanItems64 : kScanItems32; static constexpr uint32_t Tile = kScanThreads * N; };
+template <typename T> struct ScanWords { static constexpr uint32_t W = 2; };   // 64-bit words of one tile's record (the host sizes the record array with it)
+constexpr uint32_t kScanLookWindows = 4;   // windows of 64 predecessors whose records one look-back round has in flight together
+typedef uint32_t scan_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void scanPublish(scan_u32x4* rec, unsigned long long sum, uint32_t tag) {
+    scan_u32x4 g; g.x = (uint32_t)sum; g.y = (uint32_t)(sum >> 32); g.z = tag; g.w = tag;
+    asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(rec), "v"(g) : "memory");
 }
-template <typename T> struct ScanWords { static constexpr uint32_t W = sizeof(T) / 4; };
+// kScanLookWindows records per lane, all in flight before the one wait
+__device__ __forceinline__ void scanLoadRecords(const scan_u32x4* p0, const scan_u32x4* p1, const scan_u32x4* p2, const scan_u32x4* p3, scan_u32x4 (&g)[kScanLookWindows]) {
+    static_assert(kScanLookWindows == 4, "one load per window below");
+    asm volatile("global_load_dwordx4 %0, %4, off sc1\n\tglobal_load_dwordx4 %1, %5, off sc1\n\t"
+                 "global_load_dwordx4 %2, %6, off sc1\n\tglobal_load_dwordx4 %3, %7, off sc1\n\ts_waitcnt vmcnt(0)"
+                 : "=&v"(g[0]), "=&v"(g[1]), "=&v"(g[2]), "=&v"(g[3]) : "v"(p0), "v"(p1), "v"(p2), "v"(p3) : "memory");
+}
 template <typename T>
 __global__ __launch_bounds__(kScanThreads) void k_exclusive_scan(T* __restrict__ in, T* __restrict__ out, uint32_t n, unsigned long long* records,
                                                                  uint32_t* ticket, uint32_t* state /* [0] tickets handed out before this launch, [1] generation: kept ON THE DEVICE so that
                                                                  the launch has the same arguments every step (a captured HIP graph replays it) */, uint32_t zeroInput /* histograms: leave the input cleared for its next use */) {
-    constexpr uint32_t W = ScanWords<T>::W;
     constexpr uint32_t kScanItems = ScanItems<T>::N, kScanTile = ScanItems<T>::Tile;
+    constexpr uint32_t V = 16u / sizeof(T), NV = kScanItems / V;          // items of one 16-byte vector, vectors per lane
+    static_assert(kScanItems % V == 0, "a lane owns whole 16-byte vectors");
+    constexpr uint32_t kPitch = NV > 1 ? NV + 1 : 1;                        // a lane's NV vectors in LDS, plus one of padding: 16 lanes' 16-byte reads then fall on 64 different banks
+    typedef T TV __attribute__((ext_vector_type(V)));
+    __shared__ TV sData[kScanThreads * kPitch];
     __shared__ uint32_t sTile;
     __shared__ T sWave[kScanThreads / 64];
     __shared__ T sPrefix;
@@ -49,16 +66,51 @@ __global__ __launch_bounds__(kScanThreads) void k_exclusive_scan(T* __restrict__
     }
     __syncthreads();
     const uint32_t tile = sTile, gen = sGen;
-    // striped loads (thread t takes items t, t + 256, ...: every load instruction reads one contiguous span), then blocked through LDS?  Not needed:
-    // a prefix sum only needs each THREAD's items to be consecutive in the order it sums them, so thread t owns the kScanItems consecutive items
-    // starting at base and reads them as 16-byte vectors
-    const uint32_t base = tile * kScanTile + tid * kScanItems;
+    // Global memory is touched STRIPED: vector q = j * 256 + thread of the tile, so every load and store instruction of a wave covers one
+    // contiguous 1 KB span (eight whole 128-byte lines).  The sum needs each thread's items consecutive (BLOCKED: thread t owns vectors
+    // t * NV ..), so the tile crosses LDS once on the way in and once on the way out.  Blocked access to global memory (each thread reading its own
+    // consecutive items) is correct too, but every lane then has its own 128-byte line and takes 16 bytes of it per instruction, and every line is
+    // written eight times as a partial one: measured on the 64-bit pair scan (891 k items) 889 k write requests and 14.6 us against 112 k and 9.4 us
+    // with this layout, the 32-bit scans 7.4 against 5.8 us (profiles/streaming_passes.txt).
+    const size_t tileBase = (size_t)tile * kScanTile;
+    const bool whole = tileBase + kScanTile <= (size_t)n;                                       // (workgroup-uniform, like the alignment tests)
+    const bool vecIn = whole && ((uintptr_t)in & 15u) == 0u, vecOut = whole && ((uintptr_t)out & 15u) == 0u;   // callers' arrays (query offsets) need not be 16-byte aligned
+    auto slot = [](uint32_t q) -> uint32_t { return NV > 1 ? q + q / NV : q; };
+    {
+        TV x[NV];
+        if (vecIn) {
+            const TV* src = reinterpret_cast<const TV*>(in + tileBase);
+            #pragma unroll
+            for (uint32_t j = 0; j < NV; ++j) x[j] = src[j * kScanThreads + tid];
+            if (zeroInput) {
+                TV* dst = reinterpret_cast<TV*>(in + tileBase);
+                #pragma unroll
+                for (uint32_t j = 0; j < NV; ++j) dst[j * kScanThreads + tid] = TV(0);
+            }
+        } else {
+            #pragma unroll
+            for (uint32_t j = 0; j < NV; ++j) {
+                #pragma unroll
+                for (uint32_t e = 0; e < V; ++e) { const size_t i = tileBase + (size_t)(j * kScanThreads + tid) * V + e; x[j][e] = i < n ? in[i] : T(0); }
+            }
+            if (zeroInput) {
+                #pragma unroll
+                for (uint32_t j = 0; j < NV; ++j) {
+                    #pragma unroll
+                    for (uint32_t e = 0; e < V; ++e) { const size_t i = tileBase + (size_t)(j * kScanThreads + tid) * V + e; if (i < n) in[i] = T(0); }
+                }
+            }
+        }
+        #pragma unroll
+        for (uint32_t j = 0; j < NV; ++j) sData[slot(j * kScanThreads + tid)] = x[j];
+    }
+    __syncthreads();
     T v[kScanItems];
     #pragma unroll
-    for (uint32_t k = 0; k < kScanItems; ++k) v[k] = base + k < n ? in[base + k] : T(0);
-    if (zeroInput) {
-#pragma unroll
-        for (uint32_t k = 0; k < kScanItems; ++k) if (base + k < n) in[base + k] = T(0);
+    for (uint32_t j = 0; j < NV; ++j) {
+        const TV x = sData[tid * kPitch + j];
+        #pragma unroll
+        for (uint32_t e = 0; e < V; ++e) v[j * V + e] = x[e];
     }
     T local = 0;
     #pragma unroll
@@ -71,44 +123,81 @@ __global__ __launch_bounds__(kScanThreads) void k_exclusive_scan(T* __restrict__
     T waveOff = 0, aggregate = 0;
     #pragma unroll
     for (uint32_t w = 0; w < kScanThreads / 64; ++w) { if (w < wave) waveOff += sWave[w]; aggregate += sWave[w]; }
+    {   // exclusive within the tile, back into the thread's own LDS vectors (nobody else reads or writes them before the barrier below)
+        const T off = waveOff + (incl - local);
+        #pragma unroll
+        for (uint32_t j = 0; j < NV; ++j) {
+            TV x;
+            #pragma unroll
+            for (uint32_t e = 0; e < V; ++e) x[e] = off + v[j * V + e];
+            sData[tid * kPitch + j] = x;
+        }
+    }
     if (wave == 0) {
         T prefix = 0;
         const uint32_t tagAgg = (gen << 2) | 1u, tagInc = (gen << 2) | 2u;
-        auto word = [](T x, uint32_t w) -> uint32_t { return (uint32_t)((unsigned long long)x >> (32u * w)); };
+        scan_u32x4* recs = reinterpret_cast<scan_u32x4*>(records);
         if (tile == 0) {
-            if (lane < W) scanPublish(&records[lane], word(aggregate, lane), tagInc);
+            if (lane == 0) scanPublish(recs, (unsigned long long)aggregate, tagInc);
         } else {
-            if (lane < W) scanPublish(&records[(size_t)tile * W + lane], word(aggregate, lane), tagAgg);
+            if (lane == 0) scanPublish(recs + tile, (unsigned long long)aggregate, tagAgg);
             int32_t look = (int32_t)tile - 1;
-            while (true) {                                   // 64 predecessors per round, nearest first
-                const int32_t idx = look - (int32_t)lane;
-                T val = 0; uint32_t state = idx < 0 ? 3u : 0u;                 // 3: before the first tile (contributes nothing, ends the search)
-                while (state == 0u) {
-                    unsigned long long r0 = __hip_atomic_load(&records[(size_t)idx * W], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    unsigned long long r1 = W == 2 ? __hip_atomic_load(&records[(size_t)idx * W + (W - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : r0;
-                    const uint32_t t0 = (uint32_t)(r0 >> 32), t1 = (uint32_t)(r1 >> 32);
-                    if (t0 == t1 && (t0 == tagAgg || t0 == tagInc)) {      // both halves written by the same publication of this generation
-                        state = t0 & 3u;
-                        val = W == 2 ? (T)(((unsigned long long)(uint32_t)r1 << 32) | (unsigned long long)(uint32_t)r0) : (T)(uint32_t)r0;
-                    } else __builtin_amdgcn_s_sleep(1);
+            while (true) {                                   // kScanLookWindows x 64 predecessors per round, nearest first; rounds never overlap
+                T val[kScanLookWindows]; uint32_t st[kScanLookWindows]; const scan_u32x4* rp[kScanLookWindows];
+                #pragma unroll
+                for (uint32_t k = 0; k < kScanLookWindows; ++k) {
+                    const int32_t idx = look - (int32_t)(k * 64u + lane);
+                    val[k] = 0; st[k] = idx < 0 ? 3u : 0u;                     // 3: before the first tile (contributes nothing, ends the search)
+                    rp[k] = recs + (idx < 0 ? 0 : idx);
                 }
-                const unsigned long long done = __ballot(state >= 2u);       // lanes holding an inclusive prefix (or the start of the array)
-                const uint32_t first = done ? (uint32_t)__ffsll((long long)done) - 1u : 64u;
-                T contrib = lane <= first ? val : T(0);                        // everything nearer than (and including) the first inclusive record
+                T contrib; bool found;
+                while (true) {
+                    scan_u32x4 g[kScanLookWindows];
+                    scanLoadRecords(rp[0], rp[1], rp[2], rp[3], g);
+                    #pragma unroll
+                    for (uint32_t k = 0; k < kScanLookWindows; ++k)
+                        if (st[k] == 0u && (g[k].z == tagAgg || g[k].z == tagInc)) {      // a publication of this generation (a record taken earlier is not taken again)
+                            st[k] = g[k].z & 3u;
+                            val[k] = (T)(((unsigned long long)g[k].y << 32) | (unsigned long long)g[k].x);
+                        }
+                    // window by window, nearest first: everything nearer than (and including) the first inclusive record must have arrived
+                    contrib = 0; found = false; bool pending = false;
+                    #pragma unroll
+                    for (uint32_t k = 0; k < kScanLookWindows; ++k) {
+                        if (found || pending) continue;
+                        const unsigned long long done = __ballot(st[k] >= 2u), wait = __ballot(st[k] == 0u);
+                        const uint32_t first = done ? (uint32_t)__ffsll((long long)done) - 1u : 63u;
+                        const unsigned long long need = first >= 63u ? ~0ull : (2ull << first) - 1ull;
+                        if (wait & need) pending = true;
+                        else { if ((need >> lane) & 1ull) contrib += val[k]; found = done != 0ull; }
+                    }
+                    if (!pending) break;
+                    __builtin_amdgcn_s_sleep(1);
+                }
                 #pragma unroll
                 for (uint32_t d = 32; d >= 1; d >>= 1) contrib += __shfl_xor(contrib, d, 64);
                 prefix += contrib;
-                if (done) break;
-                look -= 64;
+                if (found) break;
+                look -= (int32_t)(64u * kScanLookWindows);
             }
-            if (lane < W) scanPublish(&records[(size_t)tile * W + lane], word(prefix + aggregate, lane), tagInc);
+            if (lane == 0) scanPublish(recs + tile, (unsigned long long)(prefix + aggregate), tagInc);
         }
         if (lane == 0) sPrefix = prefix;
     }
     __syncthreads();
-    const T off = sPrefix + waveOff + (incl - local);
-    #pragma unroll
-    for (uint32_t k = 0; k < kScanItems; ++k) if (base + k < n) out[base + k] = off + v[k];
+    const T prefix = sPrefix;
+    if (vecOut) {
+        TV* dst = reinterpret_cast<TV*>(out + tileBase);
+        #pragma unroll
+        for (uint32_t j = 0; j < NV; ++j) dst[j * kScanThreads + tid] = sData[slot(j * kScanThreads + tid)] + TV(prefix);
+    } else {
+        #pragma unroll
+        for (uint32_t j = 0; j < NV; ++j) {
+            const TV x = sData[slot(j * kScanThreads + tid)];
+            #pragma unroll
+            for (uint32_t e = 0; e < V; ++e) { const size_t i = tileBase + (size_t)(j * kScanThreads + tid) * V + e; if (i < n) out[i] = prefix + x[e]; }
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ poses for the caller

@@ -290,6 +290,7 @@ struct mi_world {
     uint32_t* roundFlagsPtr() { return reinterpret_cast<uint32_t*>(scalarsRaw.p + sizeof(StepScalars)); }
     DBuf<uint64_t> pairKeys, pairKeysS; DBuf<uint8_t> manKept; DBuf<uint32_t> epaQueue; DBuf<float4> epaSimplex;   // epaQueue / epaSimplex: k_narrow_gjk -> k_narrow_epa   // manKept: manifold kept its colour (already in the next step's history)
     DeviceScan<uint32_t> scanCells, scanBins; DeviceScan<unsigned long long> scanPairs, scanTerrain;   // one per scan site (own tickets / generations)
+    DBuf<unsigned long long> dbgScanIn, dbgScanOut;   // mi_debug_exclusive_scan: a host array's way through the cell histogram's / the pair scan's site
     // narrow phase
     DBuf<uint64_t> npPacked, npScan; DBuf<float4> npNormal, npPoints; DBuf<BoxHit> boxQueue;
     DBuf<uint32_t> manPair; DBuf<uint2> manBodies, manInfo; DBuf<uint4> colWork;

@@ -463,6 +463,24 @@ MI_API int mi_debug_step_graph_stats(mi_world* w, uint32_t* out4) {
     out4[0] = w->graphsEnabled ? 1u : 0u; out4[1] = w->graphHits; out4[2] = w->graphCaptures; out4[3] = w->graphPlain;
     return MI_OK;
 }
+// Tests (tests/test_gpu_scan.py): k_exclusive_scan over a host array, enqueued on the world's stream through the step's OWN scan sites (width_bits 32: the cell histogram's,
+// 64: the pair scan's) — behind whatever records, tickets and generations the steps and calls so far have left there.  zero_input != 0: `in` comes back as the kernel left it.
+MI_API int mi_debug_exclusive_scan(mi_world* w, uint32_t widthBits, void* in, uint32_t n, uint32_t zeroInput, void* out) {
+    if (!w || (widthBits != 32u && widthBits != 64u) || (n && (!in || !out))) return fail(MI_ERR_INVALID_ARGUMENT, "width_bits is 32 or 64; null array");
+    HIP_TRY(hipSetDevice(w->device));
+    if (!n) return MI_OK;
+    const size_t bytes = (size_t)n * (widthBits / 8u), words = (bytes + 7u) / 8u;
+    HIP_TRY(w->dbgScanIn.ensure(words)); HIP_TRY(w->dbgScanOut.ensure(words));
+    HIP_TRY(hipMemcpyAsync(w->dbgScanIn.p, in, bytes, hipMemcpyHostToDevice, w->stream));
+    Launcher& L = w->query.L;
+    L.begin(false, false);
+    if (widthBits == 32u) HIP_TRY(w->scanCells.run(L, reinterpret_cast<uint32_t*>(w->dbgScanIn.p), reinterpret_cast<uint32_t*>(w->dbgScanOut.p), n, w->stream, zeroInput != 0u));
+    else HIP_TRY(w->scanPairs.run(L, w->dbgScanIn.p, w->dbgScanOut.p, n, w->stream, zeroInput != 0u));
+    HIP_TRY(hipMemcpyAsync(out, w->dbgScanOut.p, bytes, hipMemcpyDeviceToHost, w->stream));
+    if (zeroInput) HIP_TRY(hipMemcpyAsync(in, w->dbgScanIn.p, bytes, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));
+    return MI_OK;
+}
 MI_API int mi_world_get_solver_kind(mi_world* w, uint32_t* out) {
     if (!w || !out) return fail(MI_ERR_INVALID_ARGUMENT, "null");
     *out = w->usedFused ? 3u : w->usedPersist ? (w->usedXcdSingle ? 5u : w->usedXcd ? 4u : 2u) : w->usedFlow ? 1u : 0u;

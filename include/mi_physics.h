@@ -567,6 +567,11 @@ MI_API int mi_world_get_solver_kind(mi_world* world, uint32_t* out_kind);
  * (HIP runtime >= 7.2; MI_GRAPH=0 / force / all).  out[0] = enabled, out[1] = steps replayed, out[2] = graphs captured,
  * out[3] = speculative steps launched plainly. */
 MI_API int mi_debug_step_graph_stats(mi_world* world, uint32_t* out4);
+/* Tests: the device-wide exclusive prefix sum of the step (k_exclusive_scan) over a host array of `n` items of width_bits = 32 or 64 (64: two independent 32-bit sums side
+ * by side, as the narrow phase packs them), run on the world's stream through the step's own scan sites (32: the cell histogram's, 64: the pair scan's), so behind the records,
+ * tickets and generations that earlier steps and calls left there.  `out` receives the n prefix sums; zero_input != 0 asks the kernel to clear its input, and `in` then
+ * receives the input array as the kernel left it.  No reference counterpart. */
+MI_API int mi_debug_exclusive_scan(mi_world* world, uint32_t width_bits, void* in, uint32_t n, uint32_t zero_input, void* out);
 /* Tests: in how many valid steps the colouring was finished by the tail inside k_bin_hist (the colouring rounds the host enqueued — what the previous step needed + 1 — left
  * manifolds uncoloured), and how many rounds ran there in total.  No reference counterpart (scheduleConstraintsSIMD is one serial pass, src/physics/constraints.cpp:51-184). */
 MI_API int mi_debug_color_tail_stats(mi_world* world, uint64_t* out_steps, uint64_t* out_rounds);
