@@ -49,7 +49,8 @@ VOLUME_CONTACT_COUNT_MASK, VOLUME_CONTACT_VOLUME_IS_B = 7, 1 << 8
 # mi_terrain_contact (mi_world_terrain_contacts): one record per contact of a volume with the heightmap terrain, in the reference's emission order
 terrain_contact_dtype = np.dtype([("point", "<f4", 3), ("depth", "<f4"), ("normal", "<f4", 3), ("volume", "<u4")])
 assert terrain_contact_dtype.itemsize == 32
-# mi_sweep_hit (mi_world_sweep): the first collider a moved volume touches; entity / collider MI_RAY_MISS and t = +inf on a miss
+# mi_sweep_hit (mi_world_sweep): the first collider a moved volume touches; entity / collider MI_RAY_MISS and t = +inf on a miss, RAY_TERRAIN (0xFFFFFFFE, object_type 1)
+# for the heightmap's collision triangles (include has QUERY_TERRAIN and the entity range contains RAY_TERRAIN)
 sweep_hit_dtype = np.dtype([("entity", "<u4"), ("collider", "<u4"), ("t", "<f4"), ("object_type", "<u4"), ("point", "<f4", 3), ("flags", "<u4"),
                             ("normal", "<f4", 3), ("volume", "<u4")])
 assert sweep_hit_dtype.itemsize == 48
@@ -409,11 +410,12 @@ class World:
         return out
 
     def sweep(self, volumes, displacements, include=QUERY_DEFAULT, entity_ranges=None):
-        """mi_world_sweep: volume i moves from its pose by t * displacements[i], t in [0, 1]; the first touch of each as a `sweep_hit_dtype` array."""
+        """mi_world_sweep: volume i moves from its pose by t * displacements[i], t in [0, 1]; the first touch of each as a `sweep_hit_dtype` array.
+        With QUERY_TERRAIN in include (the default has it) the heightmap terrain is hit too, unless the cast's entity range leaves RAY_TERRAIN out."""
         return self._sweep("world_sweep", volumes, displacements, include, entity_ranges)
 
     def debug_sweep_exhaustive(self, volumes, displacements, include=QUERY_DEFAULT, entity_ranges=None):
-        """mi_debug_sweep_exhaustive: the same records from every collider against every cast (byte for byte what sweep returns)."""
+        """mi_debug_sweep_exhaustive: the same records from every collider and every terrain triangle against every cast (byte for byte what sweep returns)."""
         return self._sweep("debug_sweep_exhaustive", volumes, displacements, include, entity_ranges)
 
     def sweep_device_async(self, n, volumes_ptr, displacements_ptr, out_ptr, include=QUERY_DEFAULT, ranges_ptr=0):

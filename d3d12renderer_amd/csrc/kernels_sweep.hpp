@@ -4,12 +4,17 @@
 //
 // Read-only with respect to the step: everything here reads query-owned rows and writes the caller's records.
 //   sweepPair             the pair test: a convex cast in the relative frame (van den Bergen's GJK ray cast against the Minkowski difference
-//                         collider - volume), spheres and capsules as a point / segment core plus a radius margin
+//                         collider - volume), spheres and capsules as a point / segment core plus a radius margin; sweepTrianglePair: the same
+//                         body against a terrain triangle (three vertices, no margin)
 //   k_q_sweep             one wave per cast: the lanes stride over the entries of the grid cells the SWEPT AABB overlaps, then over the large
 //                         list; a cast over many cells strides over all colliders instead; a candidate whose conservative entry time lies
 //                         behind the wave's best time so far is skipped
 //   k_q_sweep_exhaustive  the yardstick: every collider for every cast, rows computed for the call, nothing skipped
+//   k_q_sweep_terrain     the heightmap's collision triangles (MI_QUERY_TERRAIN), launched behind k_q_sweep: one wave per cast walks the aligned
+//                         8 x 8-cell blocks under the swept AABB, block row by block row in the direction of travel, culled by the min/max mips
+//   k_q_sweep_terrain_exhaustive  behind k_q_sweep_exhaustive: every triangle of every chunk that has heights, no mips, nothing skipped
 // Both kernels decide through swCandidate and write through swFinalise: the same winner key (t bits << 32 | collider) gives the same bytes.
+// The terrain kernels likewise: swTerrainCandidate (key = t bits << 32 | triangle), swTerrainFinalise, which merges with the colliders' record.
 // No atomics, no dependence between workgroups; every loop is bounded by a constant, the collider count or the grid.
 #pragma once
 #include "kernels_overlap.hpp"
@@ -21,6 +26,9 @@ constexpr uint32_t kSweepInitialOverlap = 1u, kSweepUnconverged = 2u;   // MI_SW
 constexpr float kSweepTolRel = 2e-6f;         // touching = closer than this times the largest coordinate seen (a few float32 ulps of the support points)
 constexpr float kSweepStallTol = 16.f;        // a search that has STALLED (see sweepPair) counts as touching within this many tolerances (stalls of rounding alone measured up to 4)
 constexpr uint32_t kSweepRecordRows = 3;      // mi_sweep_hit: three rows of 16 bytes
+constexpr int kSwTriangle = T_HULL + 1;       // a terrain triangle as the pair test's collider: vertices a, b and rot's x, y, z; this file's alone, never stored in a world row
+constexpr float kSwPad = 1e-5f;               // relative padding of the candidates' slab test
+constexpr float kSwCullPad = 2e-5f;           // ... of a box that stands for several candidates: at least the padding of every box inside it (|a| + |b| of an inner interval is at most twice the outer one's)
 
 // ---- the pair test
 struct SweepResult { bool hit; float t; V3 normal, point; uint32_t flags; };
@@ -59,6 +67,17 @@ __device__ inline V3 swSupport(const Shape& s, const HullSet& hs, V3 dir) {
             return s.a + rotate(s.rot, best);
         }
     }
+}
+// ... and of a terrain triangle (type kSwTriangle: vertices a, b and rot's x, y, z; no margin).  Not a case of the switch above: the pair test of the world's
+// shapes is compiled without it (as a seventh case it cost the sixteen-cell casts of tools/bench_sweep.py 0.7 %, measured), the terrain has an instance of its own.
+__device__ __forceinline__ V3 swTriangleSupport(const Shape& s, V3 dir) {
+    const V3 c(s.rot.x, s.rot.y, s.rot.z);
+    const float da = dot(dir, s.a), db = dot(dir, s.b), dc = dot(dir, c);
+    return da >= db ? (da >= dc ? s.a : c) : (db >= dc ? s.b : c);
+}
+template <bool kTriangle> __device__ __forceinline__ V3 swColliderSupport(const Shape& s, const HullSet& hs, V3 dir) {
+    if (kTriangle) return swTriangleSupport(s, dir);
+    return swSupport(s, hs, dir);
 }
 __device__ __forceinline__ float swMargin(const Shape& s) { return s.type <= T_CAPSULE ? s.radius : 0.f; }
 __device__ __forceinline__ float swMaxAbs(V3 a) { return qmax(fabsf(a.x), qmax(fabsf(a.y), fabsf(a.z))); }
@@ -174,18 +193,19 @@ __device__ inline Shape swClipBox(const Shape& b, V3 sweptMin, V3 sweptMax) {
 // parallel faces and edges, a cap flat on a face) and with kSweepUnconverged beyond them (measured: a box of 1e-2 on the side of a cylinder of
 // radius 15 stalls 42 tolerances = 2.5e-3 short of the touch, on a thin triangle of far-apart points of the curved side).
 // The result depends on (A, B, d) alone; one body (not inlined) serves the candidate test and the record writer of both kernels.
-__device__ __noinline__ SweepResult sweepPair(const Shape& A, V3 sweptMin, V3 sweptMax, const Shape& collider, const HullSet& hs, V3 d) {
+// kTriangle: the collider is a terrain triangle (sweepTrianglePair below); everything but its support function is the same code.
+template <bool kTriangle> __device__ __forceinline__ SweepResult sweepPairBody(const Shape& A, V3 sweptMin, V3 sweptMax, const Shape& collider, const HullSet& hs, V3 d) {
     SweepResult r; r.hit = false; r.t = 0.f; r.flags = 0u;
     const Shape B = swClipBox(collider, sweptMin, sweptMax);
     const float R = swMargin(A) + swMargin(B);
     float lambda = 0.f, scale = 1.f;
-    V3 x, n, witness, v = swSupport(A, hs, V3()) - swSupport(B, hs, V3());   // (from some point of B to some point of A)
+    V3 x, n, witness, v = swSupport(A, hs, V3()) - swColliderSupport<kTriangle>(B, hs, V3());   // (from some point of B to some point of A)
     if (sqlen(v) == 0.f) v = V3(1.f, 0.f, 0.f);
     bool clipped = false, done = false;
     SwSimplex s; s.n = 0u;
     float dist2 = FLT_MAX, tol = 0.f;
     for (uint32_t it = 0; it < kSweepMaxIter && !done; ++it) {
-        const V3 pb = swSupport(B, hs, v), pa = swSupport(A, hs, -v), p = pb - pa;
+        const V3 pb = swColliderSupport<kTriangle>(B, hs, v), pa = swSupport(A, hs, -v), p = pb - pa;
         scale = qmax(scale, qmax(swMaxAbs(pa), swMaxAbs(pb)));
         tol = kSweepTolRel * qmax(scale, R);
         const float lv = len(v), vw = dot(v, x - p) - R * lv;
@@ -232,6 +252,13 @@ __device__ __noinline__ SweepResult sweepPair(const Shape& A, V3 sweptMin, V3 sw
     r.point = witness + r.normal * swMargin(B);
     return r;
 }
+__device__ __noinline__ SweepResult sweepPair(const Shape& A, V3 sweptMin, V3 sweptMax, const Shape& collider, const HullSet& hs, V3 d) {
+    return sweepPairBody<false>(A, sweptMin, sweptMax, collider, hs, d);
+}
+// ... against a terrain triangle (swTerrainShape): one body (not inlined) for the candidate test and the record writer of both terrain kernels
+__device__ __noinline__ SweepResult sweepTrianglePair(const Shape& A, V3 sweptMin, V3 sweptMax, const Shape& triangle, const HullSet& hs, V3 d) {
+    return sweepPairBody<true>(A, sweptMin, sweptMax, triangle, hs, d);
+}
 
 // The overlap query's pair test (declared in kernels_overlap.hpp): the cast by a zero displacement.  No plane can be clipped against, so the search
 // ends at the first support plane that separates the shapes by more than the margins (apart) or once the distance is within tolerance of the
@@ -264,6 +291,23 @@ __device__ __forceinline__ OverlapVolume swSweptBounds(const SweepCast& c) {
     q.mn = c.sweptMin; q.mx = c.sweptMax;
     return q;
 }
+// One axis of the slab test: the displacement from the volume's centre o against the interval [ca, cb] grown by the volume's half-extent and a relative padding.
+__device__ __forceinline__ bool swSlabAxis(float o, float half, float d, float ca, float cb, float padRel, float& t0, float& t1) {
+    const float lo = ca - half - o, hi = cb + half - o;
+    const float pad = padRel * (fabsf(o) + fabsf(ca) + fabsf(cb) + 1.f);
+    const float l = lo - pad, h = hi + pad;
+    if (d == 0.f) return !(l > 0.f || h < 0.f);
+    const float ta = l / d, tb = h / d; t0 = qmax(t0, fminr(ta, tb)); t1 = fminr(t1, qmax(ta, tb));
+    return true;
+}
+// The slab test of a cast against the box [a, b]: false = the swept volume's AABB never meets it; t0 = the conservative entry time in [0, 1].
+__device__ __forceinline__ bool swSlab(const SweepCast& c, V3 a, V3 b, float padRel, float& t0) {
+    float t1 = 1.f; t0 = 0.f;
+    if (!swSlabAxis(c.centre.x, c.half.x, c.d.x, a.x, b.x, padRel, t0, t1)) return false;
+    if (!swSlabAxis(c.centre.y, c.half.y, c.d.y, a.y, b.y, padRel, t0, t1)) return false;
+    if (!swSlabAxis(c.centre.z, c.half.z, c.d.z, a.z, b.z, padRel, t0, t1)) return false;
+    return t0 <= t1 && qFinite(t1);
+}
 // THE candidate test: collider k against the cast -> key = t bits << 32 | k, or ~0.  Object type, entity range, a finite AABB, the slab test of the
 // displacement against the collider's AABB grown by the volume's half-extents (a conservative entry time; padded by a few ulps), then sweepPair.
 // The reported t is never below the entry time (both are lower bounds of the true time), so with kSkip a candidate whose entry lies strictly
@@ -275,19 +319,8 @@ template <bool kSkip> __device__ inline unsigned long long swCandidate(const Ove
     const uint32_t ent = s.cEntity[k];
     if (ent < c.q.lo || ent >= c.q.hi) return ~0ull;
     if (!(qExtent(a, b) >= 0.f)) return ~0ull;
-    const float lo[3] = {a.x - c.half.x - c.centre.x, a.y - c.half.y - c.centre.y, a.z - c.half.z - c.centre.z};
-    const float hi[3] = {b.x + c.half.x - c.centre.x, b.y + c.half.y - c.centre.y, b.z + c.half.z - c.centre.z};
-    const float d[3] = {c.d.x, c.d.y, c.d.z};
-    const float o[3] = {c.centre.x, c.centre.y, c.centre.z}, ca[3] = {a.x, a.y, a.z}, cb[3] = {b.x, b.y, b.z};
-    float t0 = 0.f, t1 = 1.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float pad = 1e-5f * (fabsf(o[i]) + fabsf(ca[i]) + fabsf(cb[i]) + 1.f);
-        const float l = lo[i] - pad, h = hi[i] + pad;
-        if (d[i] == 0.f) { if (l > 0.f || h < 0.f) return ~0ull; }
-        else { const float ta = l / d[i], tb = h / d[i]; t0 = qmax(t0, fminr(ta, tb)); t1 = fminr(t1, qmax(ta, tb)); }
-    }
-    if (!(t0 <= t1) || !qFinite(t1)) return ~0ull;
+    float t0;
+    if (!swSlab(c, xyz(a), xyz(b), kSwPad, t0)) return ~0ull;
     if (kSkip && t0 > bestT) return ~0ull;
     const SweepResult r = sweepPair(c.q.s, c.sweptMin, c.sweptMax, loadShape(s.shape, k, type), s.hs, c.d);
     if (!r.hit) return ~0ull;
@@ -387,6 +420,161 @@ __global__ __launch_bounds__(64 * kOvWaves) void k_q_sweep_exhaustive(uint32_t c
         for (uint32_t k = lane; k < s.nc; k += 64u) best = min(best, swCandidate<false>(s, c, k, 0.f));
     best = swWaveMin(best);
     if (lane == 0u) swFinalise(s, c, best, vPos[v], v, out);
+}
+
+// ---- the terrain (MI_QUERY_TERRAIN): the heightmap's collision triangles, (A, B, C) and (C, B, D) of every cell of a chunk that has heights, what the
+// ray cast hits (qTerrainTriangle); two-sided surfaces without volume.  A launch of its own behind the collider kernel, whose record it merges with:
+// k_q_sweep stays what it is, a world without terrain pays nothing; a terrain hit does not prune the collider pass this way.
+// The rule of qTerrainIncluded (the host launches these kernels only for a world with a heightmap)
+__device__ __forceinline__ bool swTerrainIncluded(const SweepCast& c) {
+    return c.valid && (c.q.include & kQueryTerrain) && kRayTerrain >= c.q.lo && kRayTerrain < c.q.hi;
+}
+// a vertex coordinate along x or z in hmVertex's arithmetic (the same bits): vertex v (0..128) of chunk `chunk`
+__device__ __forceinline__ float swTerrainCoord(const HeightmapParams& hm, uint32_t chunk, uint32_t v, float mapMin) {
+    return (float)v * hm.chunkScale + ((float)chunk * hm.chunkSize + mapMin);
+}
+__device__ __forceinline__ float swTerrainHeight(const HeightmapParams& hm, uint32_t h) { return (float)h * hm.heightScale + (0.f + hm.minY); }
+// triangle `tri` of cell (gx, gz) (of a chunk that has heights) as sweepTrianglePair's collider, loaded as qTerrainTriangle loads it
+__device__ __forceinline__ Shape swTerrainShape(const HeightmapParams& hm, uint32_t gx, uint32_t gz, uint32_t tri) {
+    const uint32_t cx = gx >> 7, cz = gz >> 7, qx = gx & 127u, qz = gz & 127u;
+    const uint16_t* heights = hm.heights + (size_t)hm.chunkSlot[cz * hm.chunksPerDim + cx] * kHmVerts * kHmVerts;
+    const V3 chunkMin = V3((float)cx * hm.chunkSize, 0.f, (float)cz * hm.chunkSize) + V3(hm.minX, hm.minY, hm.minZ);
+    const V3 b = hmVertex(hm, heights, chunkMin, qx, qz + 1u), c = hmVertex(hm, heights, chunkMin, qx + 1u, qz);
+    const V3 e = tri ? hmVertex(hm, heights, chunkMin, qx + 1u, qz + 1u) : hmVertex(hm, heights, chunkMin, qx, qz);
+    Shape s; s.type = kSwTriangle; s.radius = 0.f; s.hull = 0u;
+    s.a = tri ? c : e; s.b = b;
+    const V3 third = tri ? e : c;
+    s.rot = Q4(third.x, third.y, third.z, 0.f);
+    return s;
+}
+// THE terrain candidate test: the slab test of swCandidate against the triangle's AABB, then sweepTrianglePair -> key = t bits << 32 | (gz * n + gx) * 2 + tri, or ~0
+template <bool kSkip> __device__ inline unsigned long long swTerrainCandidate(const HeightmapParams& hm, const HullSet& hs, const SweepCast& c, uint32_t gx, uint32_t gz,
+                                                                             uint32_t tri, float bestT) {
+    const Shape T = swTerrainShape(hm, gx, gz, tri);
+    const V3 third(T.rot.x, T.rot.y, T.rot.z);
+    float t0;
+    if (!swSlab(c, vmin(vmin(T.a, T.b), third), qvmax(qvmax(T.a, T.b), third), kSwPad, t0)) return ~0ull;
+    if (kSkip && t0 > bestT) return ~0ull;
+    const SweepResult r = sweepTrianglePair(c.q.s, c.sweptMin, c.sweptMax, T, hs, c.d);
+    if (!r.hit) return ~0ull;
+    const float t = (r.flags & kSweepInitialOverlap) ? 0.f : qmax(r.t, t0);
+    return ((unsigned long long)__float_as_uint(t + 0.f) << 32) | ((gz * (hm.chunksPerDim * kHmSegs) + gx) * 2u + tri);
+}
+// THE terrain record writer (one lane): merges with the record the collider kernel wrote for this cast — the terrain replaces it only when that is a miss or
+// its t is strictly greater (as float bits: both are non-negative), so a collider wins a tie —, then the winner's pair test once more and the three rows
+__device__ inline void swTerrainFinalise(const HeightmapParams& hm, const HullSet& hs, const SweepCast& c, unsigned long long key, float4 pose, uint32_t v, uint4* out) {
+    if (key == ~0ull) return;
+    const uint32_t tBits = (uint32_t)(key >> 32), index = (uint32_t)key, n = hm.chunksPerDim * kHmSegs;
+    const uint4 have = out[kSweepRecordRows * (size_t)v];
+    if (have.x != kRayMiss && !(have.z > tBits)) return;
+    const uint32_t cell = index >> 1;
+    const SweepResult r = sweepTrianglePair(c.q.s, c.sweptMin, c.sweptMax, swTerrainShape(hm, cell % n, cell / n, index & 1u), hs, c.d);
+    V3 p, nrm;
+    const float dl = len(c.d);
+    if (r.flags & kSweepInitialOverlap) { p = V3(pose.x, pose.y, pose.z); if (dl > 0.f) nrm = c.d * (-1.f / dl); }
+    else { p = r.point; nrm = r.normal; }
+    out[kSweepRecordRows * (size_t)v] = make_uint4(kRayTerrain, kRayTerrain, tBits, OBJ_STATIC);
+    out[kSweepRecordRows * (size_t)v + 1] = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), r.flags);
+    out[kSweepRecordRows * (size_t)v + 2] = make_uint4(__float_as_uint(nrm.x), __float_as_uint(nrm.y), __float_as_uint(nrm.z), v);
+}
+
+// ---- exhaustive: one wave per cast, the lanes over every triangle (32 cells of one row at a time: one chunk), nothing skipped
+__global__ __launch_bounds__(64 * kOvWaves) void k_q_sweep_terrain_exhaustive(uint32_t count, uint32_t include, HeightmapParams hm, HullSet hs, const float4* __restrict__ vShape,
+                                                                             const float4* __restrict__ vMin, const float4* __restrict__ vMax, const uint32_t* __restrict__ vRange,
+                                                                             const float4* __restrict__ vPos, const float4* __restrict__ disp, uint4* out) {
+    const uint32_t lane = threadIdx.x & 63u, v = blockIdx.x * kOvWaves + (threadIdx.x >> 6);
+    if (v >= count) return;
+    const SweepCast c = swLoadCast(vShape, vMin, vMax, vRange, disp, v, include);
+    if (!swTerrainIncluded(c)) return;
+    const uint32_t n = hm.chunksPerDim * kHmSegs;
+    unsigned long long best = ~0ull;
+    for (uint32_t gz = 0; gz < n; ++gz)
+        for (uint32_t gx0 = 0; gx0 < n; gx0 += 32u) {
+            if (hm.chunkSlot[(gz >> 7) * hm.chunksPerDim + (gx0 >> 7)] == 0xFFFFFFFFu) continue;
+            best = min(best, swTerrainCandidate<false>(hm, hs, c, gx0 + (lane >> 1), gz, lane & 1u, 0.f));
+        }
+    best = swWaveMin(best);
+    if (lane == 0u) swTerrainFinalise(hm, hs, c, best, vPos[v], v, out);
+}
+
+// ---- accelerated: one wave per cast.  bestT starts at the t of the colliders' record.  The cells under the XZ footprint of the swept AABB (padded, clipped to the
+// map) are walked in aligned 8 x 8 blocks, block row by block row along the dominant horizontal axis of the displacement in the direction of travel; a lane
+// takes a block of the row (its box: the block's extent and the height range of mip level 3), the 64 lanes then the 64 cells of every surviving block (mip level 0).
+// Every culling box contains the padded box of every triangle it stands for (the same vertex arithmetic, kSwCullPad), so its entry time is a lower bound
+// of theirs: what is dropped lies strictly behind bestT or is never met, and the winner is the exhaustive kernel's.  The walk ends at the first block row
+// entered behind bestT along the dominant axis (monotone along the walk).  Every loop is bounded by the map's dimensions.
+__global__ __launch_bounds__(64 * kOvWaves) void k_q_sweep_terrain(uint32_t count, uint32_t include, HeightmapParams hm, HullSet hs, const float4* __restrict__ vShape,
+                                                                  const float4* __restrict__ vMin, const float4* __restrict__ vMax, const uint32_t* __restrict__ vRange,
+                                                                  const float4* __restrict__ vPos, const float4* __restrict__ disp, uint4* out) {
+    const uint32_t lane = threadIdx.x & 63u, v = blockIdx.x * kOvWaves + (threadIdx.x >> 6);
+    if (v >= count) return;
+    const SweepCast c = swLoadCast(vShape, vMin, vMax, vRange, disp, v, include);
+    if (!swTerrainIncluded(c)) return;
+    const uint4 have = out[kSweepRecordRows * (size_t)v];
+    float bestT = have.x == kRayMiss ? __uint_as_float(0x7F800000u) : __uint_as_float(have.z);
+    const uint32_t n = hm.chunksPerDim * kHmSegs;
+    // the footprint in cells, [lo, hi] per horizontal axis
+    uint32_t cellLo[2], cellHi[2];
+    const float mapMin[2] = {hm.minX, hm.minZ}, sMin[2] = {c.sweptMin.x, c.sweptMin.z}, sMax[2] = {c.sweptMax.x, c.sweptMax.z};
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const float mapMax = mapMin[a] + (float)hm.chunksPerDim * hm.chunkSize;
+        const float pad = kSwCullPad * (qmax(fabsf(sMin[a]), fabsf(sMax[a])) + 2.f * qmax(fabsf(mapMin[a]), fabsf(mapMax)) + 1.f);
+        const float fl = (sMin[a] - pad - mapMin[a]) / hm.chunkScale, fh = (sMax[a] + pad - mapMin[a]) / hm.chunkScale;
+        if (!(fh >= 0.f) || !(fl <= (float)n)) return;   // beside the map
+        cellLo[a] = (uint32_t)fminr(qmax(floorf(fl), 0.f), (float)(n - 1u));
+        cellHi[a] = (uint32_t)fminr(qmax(floorf(fh), 0.f), (float)(n - 1u));
+    }
+    const bool domX = fabsf(c.d.x) >= fabsf(c.d.z);
+    const int u = domX ? 0 : 1, w = 1 - u;   // the dominant axis and the other one (0 = x, 1 = z)
+    const float dU = domX ? c.d.x : c.d.z, oU = domX ? c.centre.x : c.centre.z, halfU = domX ? c.half.x : c.half.z;
+    const uint32_t uLo = cellLo[u] >> 3, uHi = cellHi[u] >> 3, wLo = cellLo[w] >> 3, wHi = cellHi[w] >> 3;
+    const uint32_t* __restrict__ mips = hm.mips;
+    unsigned long long best = ~0ull;
+    for (uint32_t r = 0; r <= uHi - uLo; ++r) {
+        const uint32_t bu = dU < 0.f ? uHi - r : uLo + r;
+        if (dU != 0.f) {
+            float t0 = 0.f, t1 = 1.f;
+            swSlabAxis(oU, halfU, dU, swTerrainCoord(hm, bu >> 4, (bu & 15u) * 8u, mapMin[u]), swTerrainCoord(hm, bu >> 4, (bu & 15u) * 8u + 8u, mapMin[u]), kSwCullPad, t0, t1);
+            if (t0 > bestT || t0 > 1.f) break;
+        }
+        for (uint32_t w0 = wLo; w0 <= wHi; w0 += 64u) {
+            const uint32_t bw = w0 + lane;
+            bool alive = bw <= wHi;
+            if (alive) {
+                const uint32_t bx = domX ? bu : bw, bz = domX ? bw : bu;
+                const uint32_t slot = hm.chunkSlot[(bz >> 4) * hm.chunksPerDim + (bx >> 4)];
+                alive = slot != 0xFFFFFFFFu;
+                if (alive) {
+                    const uint32_t mm = mips[(size_t)slot * kHmMipEntries + hmMipOffset(3u) + (bz & 15u) * (kHmSegs >> 3) + (bx & 15u)];
+                    const V3 mn(swTerrainCoord(hm, bx >> 4, (bx & 15u) * 8u, hm.minX), swTerrainHeight(hm, mm & 0xFFFFu), swTerrainCoord(hm, bz >> 4, (bz & 15u) * 8u, hm.minZ));
+                    const V3 mx(swTerrainCoord(hm, bx >> 4, (bx & 15u) * 8u + 8u, hm.minX), swTerrainHeight(hm, mm >> 16), swTerrainCoord(hm, bz >> 4, (bz & 15u) * 8u + 8u, hm.minZ));
+                    float t0;
+                    alive = swSlab(c, mn, mx, kSwCullPad, t0) && !(t0 > bestT);
+                }
+            }
+            for (unsigned long long m = __ballot(alive); m; m &= m - 1ull) {
+                const uint32_t bs = w0 + (uint32_t)__ffsll((long long)m) - 1u;
+                const uint32_t bx = domX ? bu : bs, bz = domX ? bs : bu;
+                const uint32_t gx = bx * 8u + (lane & 7u), gz = bz * 8u + (lane >> 3);
+                if (gx >= cellLo[0] && gx <= cellHi[0] && gz >= cellLo[1] && gz <= cellHi[1]) {
+                    const uint32_t slot = hm.chunkSlot[(gz >> 7) * hm.chunksPerDim + (gx >> 7)];
+                    const uint32_t mm = mips[(size_t)slot * kHmMipEntries + (gz & 127u) * kHmSegs + (gx & 127u)];
+                    const V3 mn(swTerrainCoord(hm, gx >> 7, gx & 127u, hm.minX), swTerrainHeight(hm, mm & 0xFFFFu), swTerrainCoord(hm, gz >> 7, gz & 127u, hm.minZ));
+                    const V3 mx(swTerrainCoord(hm, gx >> 7, (gx & 127u) + 1u, hm.minX), swTerrainHeight(hm, mm >> 16), swTerrainCoord(hm, gz >> 7, (gz & 127u) + 1u, hm.minZ));
+                    float t0;
+                    if (swSlab(c, mn, mx, kSwCullPad, t0) && !(t0 > bestT)) {
+                        best = min(best, swTerrainCandidate<true>(hm, hs, c, gx, gz, 0u, bestT));
+                        best = min(best, swTerrainCandidate<true>(hm, hs, c, gx, gz, 1u, bestT));
+                    }
+                }
+                const float tb = swBestT(best);
+                if (tb < bestT) bestT = tb;
+            }
+        }
+    }
+    best = swWaveMin(best);
+    if (lane == 0u) swTerrainFinalise(hm, hs, c, best, vPos[v], v, out);
 }
 
 }  // namespace mi

@@ -192,6 +192,12 @@ int mi_world::sweepEnqueue(uint32_t count, const uint32_t* volumesDev, const flo
     else
         L.launch(k_q_sweep, grid, block, 0, stream, count, include, s, (const float4*)v.shape.p, (const float4*)v.mn.p, (const float4*)v.mx.p, (const uint32_t*)v.range.p,
                  (const float4*)v.cPos.p, displacementsDev, (const QueryGrid*)g.grid.p, (const uint32_t*)g.start.p, (const uint32_t*)g.entries.p, (const uint32_t*)g.large.p, outDev);
+    // the terrain: the matching kernel behind the collider kernel, merging into its records; it reads the heightmap buffers themselves (no cache of its own)
+    if (heightmap && (include & kQueryTerrain)) {
+        if (hmParams.chunksPerDim > 256u) return fail(MI_ERR_UNSUPPORTED, "sweep query: a heightmap of more than 256 chunks per dimension (the triangle index has 32 bits)");
+        L.launch(exhaustive ? k_q_sweep_terrain_exhaustive : k_q_sweep_terrain, grid, block, 0, stream, count, include, hmParams, s.hs, (const float4*)v.shape.p, (const float4*)v.mn.p,
+                 (const float4*)v.mx.p, (const uint32_t*)v.range.p, (const float4*)v.cPos.p, displacementsDev, outDev);
+    }
     if (L.firstError != hipSuccess) return fail(MI_ERR_DEVICE, std::string("sweep query: ") + hipGetErrorString(L.firstError));
     return MI_OK;
 }

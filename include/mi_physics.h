@@ -398,17 +398,33 @@ MI_API int mi_debug_overlap_exhaustive(mi_world* world, uint32_t count, const mi
  *   - Accuracy (float32, measured against a float64 reference; "coordinates" = the largest |coordinate| of the cast, at least 1): t times
  *     the displacement's length is within 5e-6 x coordinates of the true travelled distance (1.1e-4 x in the unconverged case above) and
  *     passes it by no more than 2e-7 x coordinates; point lies within 1e-7 x coordinates of the collider's surface.
- *   - Not hit: the terrain (MI_QUERY_TERRAIN is accepted and ignored, as by mi_world_overlap; sweeps against the heightmap are out of
- *     scope) and cloth.  Also out of scope: rotation during the sweep, all-hits and any-hit variants.
+ *   - The terrain (MI_QUERY_TERRAIN) is what the ray cast hits: the heightmap's collision triangles, two per cell, (A, B, C) and
+ *     (C, B, D).  They are two-sided surfaces with no volume below them; chunks without heights are holes; outside the map there is
+ *     nothing.  It is tested when the world has a heightmap, include has MI_QUERY_TERRAIN and the cast's entity range contains
+ *     MI_RAY_TERRAIN (a NULL range means the whole scene): the ray cast's rule.  In every other case the call does what it does without
+ *     the bit.  A terrain hit has entity = collider = MI_RAY_TERRAIN and object_type = MI_OBJECT_STATIC_COLLIDER; t is the fraction of
+ *     the displacement, point lies on the triangle, normal is unit, points from the terrain towards the volume and has
+ *     dot(normal, displacement) <= 0: a volume that comes from below gets a normal that points down.  Spheres and capsules keep their
+ *     point / segment-plus-radius treatment; on flat ground the normal of a round volume of radius r is within 2 sqrt(tolerance / r) of
+ *     the surface's (the distance tolerance above; the touch may be found on a neighbouring triangle that far beside the foot point).
+ *     A collider wins a tie in t against the terrain, as in the ray cast; among triangles the lowest (gz * n + gx) * 2 + tri wins
+ *     (n = chunks per dimension x 128), so both kernels give the same point and normal.  Initial overlap (the volume touches a triangle at
+ *     its pose) is reported as for colliders.  A volume wholly below the surface touches no triangle: it is cast from where it is and
+ *     can hit the surface from below; for penetration against the terrain call mi_world_terrain_contacts.  Accuracy on the terrain, as
+ *     above and per unit of coordinates: see INTEGRATION.md, section 6f.  The terrain is tested in a launch of its own behind the
+ *     colliders': a terrain hit does not shorten the collider pass.  Heightmaps of more than 256 chunks per dimension return
+ *     MI_ERR_UNSUPPORTED when the terrain is asked for.
+ *   - Not hit: cloth.  Also out of scope: rotation during the sweep, all-hits and any-hit variants, and the terrain in mi_world_overlap
+ *     and mi_world_volume_contacts.
  *   - Result: one record per cast, out[count].
  */
 typedef struct mi_sweep_hit {   /* 48 bytes, 16-byte aligned rows: usable from the host and as a device buffer */
-    uint32_t entity, collider;  /* MI_RAY_MISS when nothing is hit; collider = world collider index */
+    uint32_t entity, collider;  /* MI_RAY_MISS when nothing is hit; collider = world collider index; both MI_RAY_TERRAIN for the heightmap */
     float t;                    /* fraction of the displacement in [0,1]; +inf on a miss */
-    uint32_t object_type;       /* mi_object_type of the collider; 0 on a miss */
-    float point[3];             /* world space, on the collider's surface (0 on a miss) */
+    uint32_t object_type;       /* mi_object_type of the collider (MI_OBJECT_STATIC_COLLIDER for the terrain); 0 on a miss */
+    float point[3];             /* world space, on the collider's surface or the terrain triangle (0 on a miss) */
     uint32_t flags;             /* MI_SWEEP_* */
-    float normal[3];            /* world space, unit, from the collider towards the volume (0 on a miss) */
+    float normal[3];            /* world space, unit, from the collider or the terrain towards the volume (0 on a miss) */
     uint32_t volume;            /* index of the cast */
 } mi_sweep_hit;
 enum { MI_SWEEP_INITIAL_OVERLAP = 1, MI_SWEEP_UNCONVERGED = 2 };
@@ -420,7 +436,8 @@ MI_API int mi_world_sweep(mi_world* world, uint32_t count, const mi_query_volume
 MI_API int mi_world_sweep_device_async(mi_world* world, uint32_t count, const mi_query_volume* volumes_dev, const float* displacements4_dev,
                                        uint32_t include, const uint32_t* ranges2_dev, mi_sweep_hit* out_dev);
 /* The same result from every collider tested against every cast, without the grid, without skipping by the best time so far and from
- * collider rows computed for the call (the yardstick of the accelerated path): byte for byte equal. */
+ * collider rows computed for the call, and from every terrain triangle without the height mips (the yardstick of the accelerated path):
+ * byte for byte equal. */
 MI_API int mi_debug_sweep_exhaustive(mi_world* world, uint32_t count, const mi_query_volume* volumes, const float* displacements3,
                                      uint32_t include, const uint32_t* entity_ranges2, mi_sweep_hit* out);
 

@@ -152,8 +152,11 @@ public:
         return r;
     }
     // The first collider each volume touches when it moves from its pose by t * displacement, t in [0, 1] (mi_world_sweep): one record per volume with t, the
-    // point on the collider and the normal from the collider towards the volume; entity MI_RAY_MISS on a miss; read-only.
-    // entityRanges: empty = the whole scene, otherwise one [lo, hi) pair of entity ids per volume (2 x volumes.size() words)
+    // point on the collider and the normal from the collider towards the volume; entity MI_RAY_MISS on a miss; read-only.  With MI_QUERY_TERRAIN in include (the
+    // default has it) the heightmap's collision triangles are hit as well: entity = collider = MI_RAY_TERRAIN, the normal from the terrain towards the volume.
+    // entityRanges: empty = the whole scene, otherwise one [lo, hi) pair of entity ids per volume (2 x volumes.size() words); the terrain is hit only by a
+    // cast whose range contains MI_RAY_TERRAIN
+    // sweepSphere / sweepCapsule: one cast of the whole scene, the terrain included by default (a ground probe: a capsule cast down)
     std::vector<mi_sweep_hit> sweep(const std::vector<mi_query_volume>& volumes, const std::vector<vec3>& displacements, uint32_t include = MI_QUERY_DEFAULT,
                                     const std::vector<uint32_t>& entityRanges = {}) {
         if (displacements.size() != volumes.size()) throw std::invalid_argument("sweep: one displacement per volume");
