@@ -13,8 +13,10 @@
 //   k_q_sweep_terrain     the heightmap's collision triangles (MI_QUERY_TERRAIN), launched behind k_q_sweep: one wave per cast walks the aligned
 //                         8 x 8-cell blocks under the swept AABB, block row by block row in the direction of travel, culled by the min/max mips
 //   k_q_sweep_terrain_exhaustive  behind k_q_sweep_exhaustive: every triangle of every chunk that has heights, no mips, nothing skipped
-// Both kernels decide through swCandidate and write through swFinalise: the same winner key (t bits << 32 | collider) gives the same bytes.
-// The terrain kernels likewise: swTerrainCandidate (key = t bits << 32 | triangle), swTerrainFinalise, which merges with the colliders' record.
+// Both kernels decide through swCandidate (admission: kernels_overlap.hpp's ovAdmit, shared with the overlap predicate) and write through swFinalise:
+// the same winner key (t bits << 32 | collider) gives the same bytes.  The terrain kernels likewise: swTerrainCandidate (key = t bits << 32 | triangle),
+// swTerrainFinalise, which merges with the colliders' record.  Colliders and terrain share the candidate tail (swCandidateKey: slab test, skip, pair
+// test, key) and the record tail (swWriteRecord: point and normal of an initial overlap, the three rows).
 // No atomics, no dependence between workgroups; every loop is bounded by a constant, the collider count or the grid.
 #pragma once
 #include "kernels_overlap.hpp"
@@ -308,24 +310,24 @@ __device__ __forceinline__ bool swSlab(const SweepCast& c, V3 a, V3 b, float pad
     if (!swSlabAxis(c.centre.z, c.half.z, c.d.z, a.z, b.z, padRel, t0, t1)) return false;
     return t0 <= t1 && qFinite(t1);
 }
-// THE candidate test: collider k against the cast -> key = t bits << 32 | k, or ~0.  Object type, entity range, a finite AABB, the slab test of the
-// displacement against the collider's AABB grown by the volume's half-extents (a conservative entry time; padded by a few ulps), then sweepPair.
-// The reported t is never below the entry time (both are lower bounds of the true time), so with kSkip a candidate whose entry lies strictly
-// behind bestT cannot win and is not evaluated.
-template <bool kSkip> __device__ inline unsigned long long swCandidate(const OverlapScene& s, const SweepCast& c, uint32_t k, float bestT) {
-    const float4 a = s.mn[k], b = s.mx[k];
-    const uint32_t tag = __float_as_uint(a.w), type = tag & 0xFFu, obj = (tag >> 8) & 0xFFu;
-    if (!(c.q.include & qFlagOf(obj))) return ~0ull;
-    const uint32_t ent = s.cEntity[k];
-    if (ent < c.q.lo || ent >= c.q.hi) return ~0ull;
-    if (!(qExtent(a, b) >= 0.f)) return ~0ull;
+// THE candidate tail of colliders and terrain triangles: the candidate's box [mn, mx], its index in the key and `pair()`, its pair test (sweepPair or
+// sweepTrianglePair) -> key = t bits << 32 | index, or ~0.  The slab test of the displacement against the box grown by the volume's half-extents (a
+// conservative entry time; padded by a few ulps), then the pair test.  The reported t is never below the entry time (both are lower bounds of the
+// true time), so with kSkip a candidate whose entry lies strictly behind bestT cannot win and is not evaluated.
+template <bool kSkip, class Pair> __device__ __forceinline__ unsigned long long swCandidateKey(const SweepCast& c, V3 mn, V3 mx, uint32_t index, float bestT, Pair pair) {
     float t0;
-    if (!swSlab(c, xyz(a), xyz(b), kSwPad, t0)) return ~0ull;
+    if (!swSlab(c, mn, mx, kSwPad, t0)) return ~0ull;
     if (kSkip && t0 > bestT) return ~0ull;
-    const SweepResult r = sweepPair(c.q.s, c.sweptMin, c.sweptMax, loadShape(s.shape, k, type), s.hs, c.d);
+    const SweepResult r = pair();
     if (!r.hit) return ~0ull;
     const float t = (r.flags & kSweepInitialOverlap) ? 0.f : qmax(r.t, t0);
-    return ((unsigned long long)__float_as_uint(t + 0.f) << 32) | k;
+    return ((unsigned long long)__float_as_uint(t + 0.f) << 32) | index;
+}
+// THE candidate test: collider k against the cast -> key = t bits << 32 | k, or ~0.  ovAdmit (object type, entity range, a finite AABB), then the tail.
+template <bool kSkip> __device__ inline unsigned long long swCandidate(const OverlapScene& s, const SweepCast& c, uint32_t k, float bestT) {
+    float4 a, b; uint32_t tag;
+    if (!ovAdmit(s, c.q, k, a, b, tag)) return ~0ull;
+    return swCandidateKey<kSkip>(c, xyz(a), xyz(b), k, bestT, [&] { return sweepPair(c.q.s, c.sweptMin, c.sweptMax, loadShape(s.shape, k, tag & 0xFFu), s.hs, c.d); });
 }
 __device__ __forceinline__ unsigned long long swWaveMin(unsigned long long key) {
 #pragma unroll
@@ -336,29 +338,33 @@ __device__ __forceinline__ unsigned long long swWaveMin(unsigned long long key) 
     }
     return key;
 }
-// THE record writer (one lane): the winner's pair test once more (it depends on the pair alone: the same bits), three rows of 16 bytes
-__device__ inline void swFinalise(const OverlapScene& s, const SweepCast& c, unsigned long long key, float4 pose, uint32_t v, uint4* __restrict__ out) {
-    uint32_t ent = kRayMiss, col = kRayMiss, obj = 0u, flags = 0u;
-    float t = __uint_as_float(0x7F800000u);   // +inf
-    V3 p, n;
-    if (key != ~0ull) {
-        col = (uint32_t)key; t = __uint_as_float((uint32_t)(key >> 32));
-        const uint32_t tag = __float_as_uint(s.mn[col].w);
-        ent = s.cEntity[col]; obj = (tag >> 8) & 0xFFu;
-        const SweepResult r = sweepPair(c.q.s, c.sweptMin, c.sweptMax, loadShape(s.shape, col, tag & 0xFFu), s.hs, c.d);
-        flags = r.flags;
-        const float dl = len(c.d);
-        if (flags & kSweepInitialOverlap) { p = V3(pose.x, pose.y, pose.z); if (dl > 0.f) n = c.d * (-1.f / dl); }
-        else { p = r.point; n = r.normal; }
-    }
-    out[kSweepRecordRows * (size_t)v] = make_uint4(ent, col, __float_as_uint(t), obj);
-    out[kSweepRecordRows * (size_t)v + 1] = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), flags);
+// THE record tail (one lane) of colliders and terrain: row 0 is the caller's (who was hit, at what t); a cast that starts in touch reports the volume's
+// position and the reversed direction of travel, any other the pair test's point and normal; three rows of 16 bytes
+__device__ __forceinline__ void swWriteRecord(const SweepCast& c, const SweepResult& r, uint4 row0, float4 pose, uint32_t v, uint4* out) {
+    V3 p = r.point, n = r.normal;
+    const float dl = len(c.d);
+    if (r.flags & kSweepInitialOverlap) { p = V3(pose.x, pose.y, pose.z); n = dl > 0.f ? c.d * (-1.f / dl) : V3(); }
+    out[kSweepRecordRows * (size_t)v] = row0;
+    out[kSweepRecordRows * (size_t)v + 1] = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), r.flags);
     out[kSweepRecordRows * (size_t)v + 2] = make_uint4(__float_as_uint(n.x), __float_as_uint(n.y), __float_as_uint(n.z), v);
+}
+// THE record writer (one lane): the winner's pair test once more (it depends on the pair alone: the same bits), then the tail; a miss is all zeros behind row 0
+__device__ inline void swFinalise(const OverlapScene& s, const SweepCast& c, unsigned long long key, float4 pose, uint32_t v, uint4* __restrict__ out) {
+    uint4 row0 = make_uint4(kRayMiss, kRayMiss, 0x7F800000u /* +inf */, 0u);
+    SweepResult r{};   // (a miss: no flags, point and normal zero)
+    if (key != ~0ull) {
+        const uint32_t col = (uint32_t)key, tag = __float_as_uint(s.mn[col].w);
+        row0 = make_uint4(s.cEntity[col], col, (uint32_t)(key >> 32), (tag >> 8) & 0xFFu);
+        r = sweepPair(c.q.s, c.sweptMin, c.sweptMax, loadShape(s.shape, col, tag & 0xFFu), s.hs, c.d);
+    }
+    swWriteRecord(c, r, row0, pose, v, out);
 }
 __device__ __forceinline__ float swBestT(unsigned long long key) { return __uint_as_float((uint32_t)(swWaveMin(key) >> 32)); }   // (~0: a NaN pattern, nothing is "behind" it)
 
 // ---- accelerated: one wave per cast over the grid cells of the swept AABB (the dedup rule of ovGridWalk: a collider is taken from the entry in the
-// lowest cell of the intersection of its range with the cast's), then the large list; or the stride over all colliders
+// lowest cell of the intersection of its range with the cast's), then the large list; or the stride over all colliders.  The walk is written out here
+// and in ovGridWalk: as one enumerator with a visitor, and the rows and the grid passed as two structs, it cost the one-cell casts of
+// tools/bench_sweep.py 7 % at unchanged registers and occupancy (profiles/query_device_walk_ab.txt).
 __global__ __launch_bounds__(64 * kOvWaves) void k_q_sweep(uint32_t count, uint32_t include, OverlapScene s, const float4* __restrict__ vShape, const float4* __restrict__ vMin,
                                                           const float4* __restrict__ vMax, const uint32_t* __restrict__ vRange, const float4* __restrict__ vPos,
                                                           const float4* __restrict__ disp, const QueryGrid* __restrict__ grid, const uint32_t* __restrict__ start,
@@ -447,21 +453,16 @@ __device__ __forceinline__ Shape swTerrainShape(const HeightmapParams& hm, uint3
     s.rot = Q4(third.x, third.y, third.z, 0.f);
     return s;
 }
-// THE terrain candidate test: the slab test of swCandidate against the triangle's AABB, then sweepTrianglePair -> key = t bits << 32 | (gz * n + gx) * 2 + tri, or ~0
+// THE terrain candidate test: the candidate tail on the triangle's AABB with sweepTrianglePair -> key = t bits << 32 | (gz * n + gx) * 2 + tri, or ~0
 template <bool kSkip> __device__ inline unsigned long long swTerrainCandidate(const HeightmapParams& hm, const HullSet& hs, const SweepCast& c, uint32_t gx, uint32_t gz,
                                                                              uint32_t tri, float bestT) {
     const Shape T = swTerrainShape(hm, gx, gz, tri);
     const V3 third(T.rot.x, T.rot.y, T.rot.z);
-    float t0;
-    if (!swSlab(c, vmin(vmin(T.a, T.b), third), qvmax(qvmax(T.a, T.b), third), kSwPad, t0)) return ~0ull;
-    if (kSkip && t0 > bestT) return ~0ull;
-    const SweepResult r = sweepTrianglePair(c.q.s, c.sweptMin, c.sweptMax, T, hs, c.d);
-    if (!r.hit) return ~0ull;
-    const float t = (r.flags & kSweepInitialOverlap) ? 0.f : qmax(r.t, t0);
-    return ((unsigned long long)__float_as_uint(t + 0.f) << 32) | ((gz * (hm.chunksPerDim * kHmSegs) + gx) * 2u + tri);
+    return swCandidateKey<kSkip>(c, vmin(vmin(T.a, T.b), third), qvmax(qvmax(T.a, T.b), third), (gz * (hm.chunksPerDim * kHmSegs) + gx) * 2u + tri, bestT,
+                                 [&] { return sweepTrianglePair(c.q.s, c.sweptMin, c.sweptMax, T, hs, c.d); });
 }
 // THE terrain record writer (one lane): merges with the record the collider kernel wrote for this cast — the terrain replaces it only when that is a miss or
-// its t is strictly greater (as float bits: both are non-negative), so a collider wins a tie —, then the winner's pair test once more and the three rows
+// its t is strictly greater (as float bits: both are non-negative), so a collider wins a tie —, then the winner's pair test once more and the record tail
 __device__ inline void swTerrainFinalise(const HeightmapParams& hm, const HullSet& hs, const SweepCast& c, unsigned long long key, float4 pose, uint32_t v, uint4* out) {
     if (key == ~0ull) return;
     const uint32_t tBits = (uint32_t)(key >> 32), index = (uint32_t)key, n = hm.chunksPerDim * kHmSegs;
@@ -469,13 +470,7 @@ __device__ inline void swTerrainFinalise(const HeightmapParams& hm, const HullSe
     if (have.x != kRayMiss && !(have.z > tBits)) return;
     const uint32_t cell = index >> 1;
     const SweepResult r = sweepTrianglePair(c.q.s, c.sweptMin, c.sweptMax, swTerrainShape(hm, cell % n, cell / n, index & 1u), hs, c.d);
-    V3 p, nrm;
-    const float dl = len(c.d);
-    if (r.flags & kSweepInitialOverlap) { p = V3(pose.x, pose.y, pose.z); if (dl > 0.f) nrm = c.d * (-1.f / dl); }
-    else { p = r.point; nrm = r.normal; }
-    out[kSweepRecordRows * (size_t)v] = make_uint4(kRayTerrain, kRayTerrain, tBits, OBJ_STATIC);
-    out[kSweepRecordRows * (size_t)v + 1] = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), r.flags);
-    out[kSweepRecordRows * (size_t)v + 2] = make_uint4(__float_as_uint(nrm.x), __float_as_uint(nrm.y), __float_as_uint(nrm.z), v);
+    swWriteRecord(c, r, make_uint4(kRayTerrain, kRayTerrain, tBits, OBJ_STATIC), pose, v, out);
 }
 
 // ---- exhaustive: one wave per cast, the lanes over every triangle (32 cells of one row at a time: one chunk), nothing skipped

@@ -450,8 +450,8 @@ struct mi_world {
             DeviceScan<uint32_t> scan;
             DBuf<uint32_t> candOffsets;
         } vol;
-        // The exhaustive yardstick's own collider rows, computed per call (it does not trust `built`).  Sized by the collider count; overlapEnqueue() and sweepEnqueue() grow them
-        // when called with exhaustive = true.
+        // The exhaustive yardstick's own collider rows, computed per call (it does not trust `built`).  Sized by the collider count; exhaustiveRowsEnqueue() alone grows
+        // and writes them, for the overlap and sweep calls with exhaustive = true.
         struct Exhaustive { DBuf<float4> shape, mn, mx; DBuf<QPartial> partials; } exh;
         // Contact queries: candidates (boxes-only overlap records), one 96-byte slot and one flag per candidate, the GJK queue, the scan over the flags.
         // Sized by `cap` candidates; contactsReserve() alone grows them (mi_world_volume_contacts_reserve, or a blocking call once it knows its candidate total).
@@ -478,6 +478,7 @@ struct mi_world {
     } query;
     int queryBuild();
     OverlapScene overlapScene(bool exhaustive) const;
+    int exhaustiveRowsEnqueue(bool launch);
     int volumeRowsEnqueue(uint32_t count, const uint32_t* volumesDev, const uint32_t* rangesDev);
     int terrainEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t* offsetsDev, float4* recordsDev, uint32_t capacity, uint32_t* totalDev);
     int overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t include, const uint32_t* rangesDev, uint32_t* offsetsDev, uint4* hitsDev, uint32_t capacity,

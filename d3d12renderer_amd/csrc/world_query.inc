@@ -123,6 +123,16 @@ OverlapScene mi_world::overlapScene(bool exhaustive) const {
     else { s.shape = query.built.shape.p; s.mn = query.built.mn.p; s.mx = query.built.mx.p; }
     return s;
 }
+// The exhaustive yardstick's own world rows at the current poses (one launch on the begun launcher): it does not trust the cache.  launch = false: the rows
+// an earlier pass of the same call computed stand.
+int mi_world::exhaustiveRowsEnqueue(bool launch) {
+    QueryCache::Exhaustive& x = query.exh;
+    const uint32_t nc = (uint32_t)colliders.size();
+    HIP_TRY(x.shape.ensure(3 * (size_t)std::max(nc, 1u))); HIP_TRY(x.mn.ensure(std::max(nc, 1u))); HIP_TRY(x.mx.ensure(std::max(nc, 1u)));
+    HIP_TRY(x.partials.ensure(divUp(std::max(nc, 1u), 256)));
+    if (nc && launch) query.L.launch(k_q_colliders, dim3(divUp(nc, 256)), dim3(256), 0, stream, nc, colliderRows(bPos.p, bRot.p, x.shape.p, x.mn.p, x.mx.p), x.partials.p);
+    return MI_OK;
+}
 // The volumes of a call as collider rows (two launches on the begun launcher): what every volume family tests with.
 int mi_world::volumeRowsEnqueue(uint32_t count, const uint32_t* volumesDev, const uint32_t* rangesDev) {
     QueryCache::VolumeRows& v = query.vol;
@@ -140,18 +150,13 @@ int mi_world::volumeRowsEnqueue(uint32_t count, const uint32_t* volumesDev, cons
 // enqueued in between).  boxesOnly: ovTest without overlapCheck — the candidates of the contact query.
 int mi_world::overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_t include, const uint32_t* rangesDev, uint32_t* offsetsDev, uint4* hitsDev,
                              uint32_t capacity, uint32_t* totalDev, bool exhaustive, uint32_t passes, bool boxesOnly) {
-    QueryCache::VolumeRows& v = query.vol; QueryCache::Exhaustive& x = query.exh; const QueryCache::Built& g = query.built;
-    const uint32_t nc = (uint32_t)colliders.size();
+    QueryCache::VolumeRows& v = query.vol; const QueryCache::Built& g = query.built;
     const bool first = (passes & kOvPassCount) != 0u;
     if (!exhaustive && first) { int rc = queryBuild(); if (rc != MI_OK) return rc; }
     HIP_TRY(v.count.ensure((size_t)count + 1));
     Launcher& L = query.L;
     L.begin(false, false);
-    if (exhaustive) {   // its own world rows at the current poses: the yardstick does not trust the cache
-        HIP_TRY(x.shape.ensure(3 * (size_t)std::max(nc, 1u))); HIP_TRY(x.mn.ensure(std::max(nc, 1u))); HIP_TRY(x.mx.ensure(std::max(nc, 1u)));
-        HIP_TRY(x.partials.ensure(divUp(std::max(nc, 1u), 256)));
-        if (nc && first) L.launch(k_q_colliders, dim3(divUp(nc, 256)), dim3(256), 0, stream, nc, colliderRows(bPos.p, bRot.p, x.shape.p, x.mn.p, x.mx.p), x.partials.p);
-    }
+    if (exhaustive) { int rc = exhaustiveRowsEnqueue(first); if (rc != MI_OK) return rc; }
     const OverlapScene s = overlapScene(exhaustive);
     const dim3 grid(divUp(count, kOvWaves)), block(64 * kOvWaves);
     if (first) { int rc = volumeRowsEnqueue(count, volumesDev, rangesDev); if (rc != MI_OK) return rc; }
@@ -173,16 +178,11 @@ int mi_world::overlapEnqueue(uint32_t count, const uint32_t* volumesDev, uint32_
 // ---- shape casts.  Volume rows (two launches), then one launch: a wave per cast writes its record.  The exhaustive yardstick computes its own world rows first,
 // as the overlap yardstick does.  displacementsDev: one row of 16 bytes per cast (w ignored).
 int mi_world::sweepEnqueue(uint32_t count, const uint32_t* volumesDev, const float4* displacementsDev, uint32_t include, const uint32_t* rangesDev, uint4* outDev, bool exhaustive) {
-    QueryCache::VolumeRows& v = query.vol; QueryCache::Exhaustive& x = query.exh; const QueryCache::Built& g = query.built;
-    const uint32_t nc = (uint32_t)colliders.size();
+    QueryCache::VolumeRows& v = query.vol; const QueryCache::Built& g = query.built;
     if (!exhaustive) { int rc = queryBuild(); if (rc != MI_OK) return rc; }
     Launcher& L = query.L;
     L.begin(false, false);
-    if (exhaustive) {
-        HIP_TRY(x.shape.ensure(3 * (size_t)std::max(nc, 1u))); HIP_TRY(x.mn.ensure(std::max(nc, 1u))); HIP_TRY(x.mx.ensure(std::max(nc, 1u)));
-        HIP_TRY(x.partials.ensure(divUp(std::max(nc, 1u), 256)));
-        if (nc) L.launch(k_q_colliders, dim3(divUp(nc, 256)), dim3(256), 0, stream, nc, colliderRows(bPos.p, bRot.p, x.shape.p, x.mn.p, x.mx.p), x.partials.p);
-    }
+    if (exhaustive) { int rc = exhaustiveRowsEnqueue(true); if (rc != MI_OK) return rc; }
     const OverlapScene s = overlapScene(exhaustive);
     int rc = volumeRowsEnqueue(count, volumesDev, rangesDev); if (rc != MI_OK) return rc;
     const dim3 grid(divUp(count, kOvWaves)), block(64 * kOvWaves);
