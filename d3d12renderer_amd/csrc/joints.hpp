@@ -944,14 +944,9 @@ struct JointType {
     std::vector<uint32_t> colorOffsets; // [0..65] boundaries into order (64 = overflow colour)
     std::vector<uint32_t> colorOf;      // colour of every joint of this type
     std::vector<uint8_t> inIsland;      // joint is solved by k_joint_islands
-    typename J::Pod* dPods = nullptr; uint2* dBodies = nullptr; uint32_t* dOrder = nullptr; typename J::Upd* dUpd = nullptr; float4* dAcc = nullptr;
-    size_t dCap = 0;
-    ~JointType() { release(); }
-    void release() {
-        if (dPods) (void)hipFree(dPods); if (dBodies) (void)hipFree(dBodies); if (dOrder) (void)hipFree(dOrder); if (dUpd) (void)hipFree(dUpd); if (dAcc) (void)hipFree(dAcc);
-        if (dIdentity) (void)hipFree(dIdentity); dIdentity = nullptr; identityCap = 0;
-        dPods = nullptr; dBodies = nullptr; dOrder = nullptr; dUpd = nullptr; dAcc = nullptr; dCap = 0;
-    }
+    DBuf<typename J::Pod> dPods; DBuf<uint2> dBodies; DBuf<uint32_t> dOrder; DBuf<typename J::Upd> dUpd;
+    DBuf<float4> dAcc;   // exchanged between workgroups as tagged sc1 granules: uncached memory serves those fastest (see world.hip, gVel)
+    JointType() { dAcc.flags = hipDeviceMallocUncached; }
     // Greedy colouring in descending hash32 priority with 64-bit per-body colour masks (same rule as the contact schedule).
     void computeOrder(const std::vector<float>& invMass) {
         uint32_t n = (uint32_t)bodies.size();
@@ -985,58 +980,45 @@ struct JointType {
     hipError_t upload(hipStream_t st) {
         size_t n = pods.size();
         if (!n) return hipSuccess;
-        if (n > dCap) {
-            release();
-            hipError_t e;
-            if ((e = hipMalloc((void**)&dPods, n * sizeof(typename J::Pod))) != hipSuccess) return e;
-            if ((e = hipMalloc((void**)&dBodies, n * sizeof(uint2))) != hipSuccess) return e;
-            if ((e = hipMalloc((void**)&dOrder, n * sizeof(uint32_t))) != hipSuccess) return e;
-            if ((e = hipMalloc((void**)&dUpd, n * sizeof(typename J::Upd))) != hipSuccess) return e;
-            // exchanged between workgroups as tagged sc1 granules: uncached memory serves those fastest (see world.hip, gVel)
-            if ((e = hipExtMallocWithFlags((void**)&dAcc, 2 * n * sizeof(float4), hipDeviceMallocUncached)) != hipSuccess) return e;
-            dCap = n;
-        }
         hipError_t e;
-        if ((e = hipMemcpyAsync(dPods, pods.data(), n * sizeof(typename J::Pod), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(dBodies, bodies.data(), n * sizeof(uint2), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+        if ((e = dPods.ensure(n)) != hipSuccess || (e = dBodies.ensure(n)) != hipSuccess || (e = dOrder.ensure(n)) != hipSuccess || (e = dUpd.ensure(n)) != hipSuccess || (e = dAcc.ensure(2 * n)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(dPods.p, pods.data(), n * sizeof(typename J::Pod), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(dBodies.p, bodies.data(), n * sizeof(uint2), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
         if (order.empty()) return hipSuccess;
-        return hipMemcpyAsync(dOrder, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        return hipMemcpyAsync(dOrder.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     }
     // mi_debug_set_solve_order: the reference's order — every joint of the type, one after the other, in pool order
-    uint32_t* dIdentity = nullptr; size_t identityCap = 0;
+    DBuf<uint32_t> dIdentity;
     hipError_t launchSolveReference(mi::Launcher& L, const mi::BodyView& bv, hipStream_t st) {
         const uint32_t n = (uint32_t)pods.size();
         if (!n) return hipSuccess;
-        if (n > identityCap) {
-            if (dIdentity) (void)hipFree(dIdentity);
-            dIdentity = nullptr; identityCap = 0;
-            hipError_t e = hipMalloc((void**)&dIdentity, n * sizeof(uint32_t)); if (e != hipSuccess) return e;
-            std::vector<uint32_t> id(n); for (uint32_t i = 0; i < n; ++i) id[i] = i;
-            e = hipMemcpy(dIdentity, id.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice); if (e != hipSuccess) return e;
-            identityCap = n;
+        if (n > dIdentity.cap) {
+            hipError_t e = dIdentity.ensure(n); if (e != hipSuccess) return e;
+            std::vector<uint32_t> id(dIdentity.cap); for (uint32_t i = 0; i < (uint32_t)id.size(); ++i) id[i] = i;
+            e = hipMemcpy(dIdentity.p, id.data(), id.size() * sizeof(uint32_t), hipMemcpyHostToDevice); if (e != hipSuccess) { dIdentity.reset(); return e; }
         }
-        L.launch(mi::k_joint_solve_serial<J>, dim3(1), dim3(64), 0, st, 0u, n, dIdentity, dBodies, dUpd, bv);
+        L.launch(mi::k_joint_solve_serial<J>, dim3(1), dim3(64), 0, st, 0u, n, dIdentity.p, dBodies.p, dUpd.p, bv);
         return hipSuccess;
     }
     bool podsDirty = false;   // mi_constraint_update since the last upload: only the POD array changed (motors, limits), not the topology
     bool deviceNewer = false; // mi_constraints_update_device_async since the last pull: dPods holds PODs the host mirror has not seen (JointSet::pullDeviceWrites)
     hipError_t uploadPods(hipStream_t st) {
         podsDirty = false;
-        if (pods.empty() || !dPods) return hipSuccess;
-        return hipMemcpyAsync(dPods, pods.data(), pods.size() * sizeof(typename J::Pod), hipMemcpyHostToDevice, st);
+        if (pods.empty() || !dPods.p) return hipSuccess;
+        return hipMemcpyAsync(dPods.p, pods.data(), pods.size() * sizeof(typename J::Pod), hipMemcpyHostToDevice, st);
     }
     void launchInit(mi::Launcher& L, uint32_t dummy, const mi::BodyView& bv, float dt, hipStream_t st) {
         uint32_t n = (uint32_t)pods.size();
-        if (n) L.launch(mi::k_joint_init<J>, dim3((n + 63) / 64), dim3(64), 0, st, n, dummy, dPods, dBodies, dUpd, dAcc, bv, dt);
+        if (n) L.launch(mi::k_joint_init<J>, dim3((n + 63) / 64), dim3(64), 0, st, n, dummy, dPods.p, dBodies.p, dUpd.p, dAcc.p, bv, dt);
     }
     void launchSolve(mi::Launcher& L, const mi::BodyView& bv, hipStream_t st) {
         if (order.empty()) return;
         for (int c = 0; c < 64; ++c) {
             uint32_t s0 = colorOffsets[c], s1 = colorOffsets[c + 1];
-            if (s1 > s0) L.launch(mi::k_joint_solve<J>, dim3((s1 - s0 + 63) / 64), dim3(64), 0, st, s0, s1, dOrder, dBodies, dUpd, bv);
+            if (s1 > s0) L.launch(mi::k_joint_solve<J>, dim3((s1 - s0 + 63) / 64), dim3(64), 0, st, s0, s1, dOrder.p, dBodies.p, dUpd.p, bv);
         }
         uint32_t o0 = colorOffsets[64], o1 = colorOffsets[65];
-        if (o1 > o0) L.launch(mi::k_joint_solve_serial<J>, dim3(1), dim3(64), 0, st, o0, o1, dOrder, dBodies, dUpd, bv);
+        if (o1 > o0) L.launch(mi::k_joint_solve_serial<J>, dim3(1), dim3(64), 0, st, o0, o1, dOrder.p, dBodies.p, dUpd.p, bv);
     }
 };
 
@@ -1044,7 +1026,25 @@ struct JointSet {
     JointType<mi::DistanceJ> distance; JointType<mi::BallJ> ball; JointType<mi::FixedJ> fixed;
     JointType<mi::HingeJ> hinge; JointType<mi::ConeJ> cone; JointType<mi::SliderJ> slider;
 
-    size_t count() const { return distance.pods.size() + ball.pods.size() + fixed.pods.size() + hinge.pods.size() + cone.pods.size() + slider.pods.size(); }
+    // THE list of the six types, in the reference's solve order (constraints.cpp:3764-3769) = the MI_CONSTRAINT_* numbering.  Everything that
+    // enumerates the types goes through it: the order of the joint launches in a step, of the POD sections in a checkpoint, of an island's groups.
+    // f(type, JointType<...>&) for every type in order until one returns non-zero (a hipError_t, a status, a bool); that value, else zero.
+    template <class S, class F> static auto firstOf(S& s, F&& f) {
+        auto r = f((uint32_t)MI_CONSTRAINT_DISTANCE, s.distance);
+        if (!r) r = f((uint32_t)MI_CONSTRAINT_BALL, s.ball);
+        if (!r) r = f((uint32_t)MI_CONSTRAINT_FIXED, s.fixed);
+        if (!r) r = f((uint32_t)MI_CONSTRAINT_HINGE, s.hinge);
+        if (!r) r = f((uint32_t)MI_CONSTRAINT_CONE_TWIST, s.cone);
+        if (!r) r = f((uint32_t)MI_CONSTRAINT_SLIDER, s.slider);
+        return r;
+    }
+    template <class F> auto tryEach(F&& f) { return firstOf(*this, f); }
+    template <class F> void each(F&& f) { firstOf(*this, [&](uint32_t type, auto& l) { f(type, l); return false; }); }
+    template <class F> void each(F&& f) const { firstOf(*this, [&](uint32_t type, const auto& l) { f(type, l); return false; }); }
+    // f(JointType<...>&) on the pool of a run-time `type`; false: not one of the six
+    template <class F> bool withType(uint32_t type, F&& f) { return firstOf(*this, [&](uint32_t t, auto& l) { if (t != type) return false; f(l); return true; }); }
+
+    size_t count() const { size_t n = 0; each([&](uint32_t, const auto& l) { n += l.pods.size(); }); return n; }
     int add(mi_world& w, uint32_t type, uint32_t ea, uint32_t eb, const void* pod, uint32_t bytes, uint32_t* out);
     int update(uint32_t type, uint32_t id, const void* pod, uint32_t bytes);
     uint64_t nextSeq = 0;
@@ -1056,21 +1056,19 @@ struct JointSet {
     int upload(mi_world& w, hipStream_t st);
     // articulated islands (k_joint_islands)
     uint32_t numIslands = 0;
-    mi::IslandDesc* dIslands = nullptr; mi::IslandStep* dSteps = nullptr; uint32_t* dIslandBodies = nullptr;
-    uint8_t* dBodyJ = nullptr;          // [bodies + 1]: 1 = dynamic body of an island (one extra version per sweep in the fused solver)
-    uint32_t* dBodyIsland = nullptr;    // [bodies + 1]: island of a dynamic island body, else 0xFFFFFFFF (private islands: IslandPrivate)
-    uint32_t* dIslState = nullptr;      // [3][islands]: shared / count / fill of this step
-    uint4* dIslEntries = nullptr;       // [islands][kIslandMaxContacts]
-    mi::IslandPrivate islandPrivate() const { return mi::IslandPrivate{dBodyIsland, dIslState, dIslState ? dIslState + numIslands : nullptr, dIslState ? dIslState + 2 * (size_t)numIslands : nullptr, dIslEntries}; }
-    bool allInIslands() const { return numIslands && distance.order.empty() && ball.order.empty() && fixed.order.empty() && hinge.order.empty() && cone.order.empty() && slider.order.empty(); }
+    // (null while there is no island: releaseIslands; read as such by islandPrivate and the step)
+    DBuf<mi::IslandDesc> dIslands; DBuf<mi::IslandStep> dSteps; DBuf<uint32_t> dIslandBodies;
+    DBuf<uint8_t> dBodyJ;               // [bodies + 1]: 1 = dynamic body of an island (one extra version per sweep in the fused solver)
+    DBuf<uint32_t> dBodyIsland;         // [bodies + 1]: island of a dynamic island body, else 0xFFFFFFFF (private islands: IslandPrivate)
+    DBuf<uint32_t> dIslState;           // [3][islands]: shared / count / fill of this step
+    DBuf<uint4> dIslEntries;            // [islands][kIslandMaxContacts]
+    mi::IslandPrivate islandPrivate() const { uint32_t* s = dIslState.p; return mi::IslandPrivate{dBodyIsland.p, s, s ? s + numIslands : nullptr, s ? s + 2 * (size_t)numIslands : nullptr, dIslEntries.p}; }
+    mi::IslandUpd islandUpd() const { return mi::IslandUpd{distance.dUpd.p, ball.dUpd.p, fixed.dUpd.p, hinge.dUpd.p, cone.dUpd.p, slider.dUpd.p}; }
+    mi::IslandAcc islandAcc() const { return mi::IslandAcc{hinge.dAcc.p, cone.dAcc.p, slider.dAcc.p}; }
+    bool allInIslands() const { bool all = numIslands != 0; each([&](uint32_t, const auto& l) { all = all && l.order.empty(); }); return all; }
     void buildIslands(const std::vector<float>& invMass, std::vector<mi::IslandDesc>& islands, std::vector<mi::IslandStep>& steps, std::vector<uint32_t>& islandBodies);
-    ~JointSet() { releaseIslands(); }
-    void releaseIslands() {
-        if (dIslands) (void)hipFree(dIslands); if (dSteps) (void)hipFree(dSteps); if (dIslandBodies) (void)hipFree(dIslandBodies); if (dBodyJ) (void)hipFree(dBodyJ);
-        if (dBodyIsland) (void)hipFree(dBodyIsland); if (dIslState) (void)hipFree(dIslState); if (dIslEntries) (void)hipFree(dIslEntries);
-        dIslands = nullptr; dSteps = nullptr; dIslandBodies = nullptr; dBodyJ = nullptr; dBodyIsland = nullptr; dIslState = nullptr; dIslEntries = nullptr; numIslands = 0;
-    }
-    bool podsDirty() const { return distance.podsDirty || ball.podsDirty || fixed.podsDirty || hinge.podsDirty || cone.podsDirty || slider.podsDirty; }
+    void releaseIslands() { dIslands.reset(); dSteps.reset(); dIslandBodies.reset(); dBodyJ.reset(); dBodyIsland.reset(); dIslState.reset(); dIslEntries.reset(); numIslands = 0; }
+    bool podsDirty() const { bool dirty = false; each([&](uint32_t, const auto& l) { dirty = dirty || l.podsDirty; }); return dirty; }
     int uploadPods(hipStream_t st);
     // mi_constraints_update_device_async writes PODs on the device only.  The ONE invariant that comes with it: before the host mirror (`pods`) of a type
     // is read (get, checkpoint), written (update, create, destroy) or re-sent (upload), the device array is pulled back — pullDeviceWrites, called there.

@@ -27,6 +27,7 @@
 #include "kernels.hpp"
 #include "gjk.hpp"
 #include "launcher.hpp"
+#include "dbuf.hpp"
 #include "joints.hpp"
 #include "heightmap.hpp"
 #include "cloth.hpp"
@@ -47,29 +48,6 @@ static int fail(int code, const std::string& msg) { g_lastError = msg; return co
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) return fail(MI_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
-
-// ------------------------------------------------------------------------------------------------
-// Device buffer (grow-only)
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    unsigned flags = 0;   // hipExtMallocWithFlags flags (0 = plain hipMalloc)
-    ~DBuf() { if (p) (void)hipFree(p); }
-    hipError_t ensure(size_t n, bool keep = false, hipStream_t st = nullptr) {
-        if (n <= cap) return hipSuccess;
-        size_t ncap = std::max(n, cap + cap / 2);
-        T* np = nullptr;
-        hipError_t e = flags ? hipExtMallocWithFlags((void**)&np, ncap * sizeof(T), flags) : hipMalloc((void**)&np, ncap * sizeof(T));
-        if (e != hipSuccess) return e;
-        if (keep && p && cap) { e = hipMemcpyAsync(np, p, cap * sizeof(T), hipMemcpyDeviceToDevice, st); if (e != hipSuccess) return e; (void)hipStreamSynchronize(st); }
-        if (p) (void)hipFree(p);
-        p = np; cap = ncap;
-        return hipSuccess;
-    }
-    void swap(DBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(flags, o.flags); }
-};
 
 // One scan site: the record arrays, ticket counter and generation of k_exclusive_scan (kernels.hpp).  Nothing is reset between
 // launches; the records are zeroed when (re)allocated and when the 32-bit generation wraps.

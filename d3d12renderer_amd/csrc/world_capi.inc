@@ -75,9 +75,8 @@ MI_API int mi_entity_destroy(mi_world* w, uint32_t entity) {
         const uint32_t p = (uint32_t)e.rb, last = (uint32_t)w->bodies.size() - 1u;
         if (p != last) {
             w->bodies[p] = w->bodies[last]; w->entities[w->bodies[p].entity].rb = (int)p;
-            JointSet& j = w->joints;   // the reference derives body pairs from the entities every step (physics.cpp:789-806): re-point the cached ones
-            auto fix = [&](auto& t) { for (uint2& b : t.bodies) { if (b.x == last) b.x = p; if (b.y == last) b.y = p; } };
-            fix(j.distance); fix(j.ball); fix(j.fixed); fix(j.hinge); fix(j.cone); fix(j.slider);
+            // the reference derives body pairs from the entities every step (physics.cpp:789-806): re-point the cached ones
+            w->joints.each([&](uint32_t, auto& t) { for (uint2& b : t.bodies) { if (b.x == last) b.x = p; if (b.y == last) b.y = p; } });
         }
         w->bodies.pop_back();
     }
@@ -425,27 +424,19 @@ template <class JT> static int podIndices(JT& l, uint32_t count, const uint32_t*
 }
 MI_API int mi_constraints_to_device_indices(mi_world* w, uint32_t type, uint32_t count, const uint32_t* ids, uint32_t* out) {
     if (!w || (count && (!ids || !out))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
-    JointSet& j = w->joints;
-    switch (type) {
-        case MI_CONSTRAINT_DISTANCE: return podIndices(j.distance, count, ids, out);
-        case MI_CONSTRAINT_BALL: return podIndices(j.ball, count, ids, out);
-        case MI_CONSTRAINT_FIXED: return podIndices(j.fixed, count, ids, out);
-        case MI_CONSTRAINT_HINGE: return podIndices(j.hinge, count, ids, out);
-        case MI_CONSTRAINT_CONE_TWIST: return podIndices(j.cone, count, ids, out);
-        case MI_CONSTRAINT_SLIDER: return podIndices(j.slider, count, ids, out);
-    }
-    return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
+    int rc = MI_OK;
+    return w->joints.withType(type, [&](auto& l) { rc = podIndices(l, count, ids, out); }) ? rc : fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
 }
 extern "C++" {
 template <class JT> static int podsScatter(mi_world* w, JT& l, uint32_t count, const uint32_t* idxDev, const void* podsDev, uint32_t podBytes) {
     typedef typename std::remove_reference<decltype(l.pods[0])>::type P;
     static_assert(sizeof(P) % 4 == 0, "PODs are arrays of 32-bit words");
     if (podBytes != sizeof(P)) return fail(MI_ERR_INVALID_ARGUMENT, "constraint pod size mismatch (the packed mi_*_constraint)");
-    if (l.pods.empty() || !l.dPods) return fail(MI_ERR_INVALID_ARGUMENT, "no constraint of this type");
+    if (l.pods.empty() || !l.dPods.p) return fail(MI_ERR_INVALID_ARGUMENT, "no constraint of this type");
     if (l.podsDirty) { HIP_TRY(l.uploadPods(w->stream)); HIP_TRY(hipStreamSynchronize(w->stream)); }   // a host update still waiting for the next step: it goes first, or that step's re-upload would undo this call
     const uint32_t words = (uint32_t)(sizeof(P) / 4u);
     const size_t total = (size_t)count * words;
-    k_scatter_pods<<<(uint32_t)((total + 255u) / 256u), 256, 0, w->stream>>>(count, words, idxDev, static_cast<const uint32_t*>(podsDev), (uint32_t)l.pods.size(), reinterpret_cast<uint32_t*>(l.dPods));
+    k_scatter_pods<<<(uint32_t)((total + 255u) / 256u), 256, 0, w->stream>>>(count, words, idxDev, static_cast<const uint32_t*>(podsDev), (uint32_t)l.pods.size(), reinterpret_cast<uint32_t*>(l.dPods.p));
     HIP_TRY(hipGetLastError());
     l.deviceNewer = true;
     return MI_OK;
@@ -456,16 +447,7 @@ MI_API int mi_constraints_update_device_async(mi_world* w, uint32_t type, uint32
     if (w->shard.enabled) return fail(MI_ERR_UNSUPPORTED, "mi_constraints_update_device_async: not on a sharded world");
     if (!count) return MI_OK;
     int rc = ensureUploaded(w); if (rc != MI_OK) return rc;
-    JointSet& j = w->joints;
-    switch (type) {
-        case MI_CONSTRAINT_DISTANCE: return podsScatter(w, j.distance, count, idxDev, podsDev, podBytes);
-        case MI_CONSTRAINT_BALL: return podsScatter(w, j.ball, count, idxDev, podsDev, podBytes);
-        case MI_CONSTRAINT_FIXED: return podsScatter(w, j.fixed, count, idxDev, podsDev, podBytes);
-        case MI_CONSTRAINT_HINGE: return podsScatter(w, j.hinge, count, idxDev, podsDev, podBytes);
-        case MI_CONSTRAINT_CONE_TWIST: return podsScatter(w, j.cone, count, idxDev, podsDev, podBytes);
-        case MI_CONSTRAINT_SLIDER: return podsScatter(w, j.slider, count, idxDev, podsDev, podBytes);
-    }
-    return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
+    return w->joints.withType(type, [&](auto& l) { rc = podsScatter(w, l, count, idxDev, podsDev, podBytes); }) ? rc : fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
 }
 
 MI_API int mi_world_step_fixed(mi_world* w, const mi_step_settings* s, float dt, uint32_t n) {

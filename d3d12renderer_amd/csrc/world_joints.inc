@@ -29,37 +29,21 @@ static int jointAddTo(mi_world& w, JT& l, uint32_t ea, uint32_t eb, const void* 
 int JointSet::destroy(uint32_t type, uint32_t id) {
     { int rc = pullDeviceWrites(); if (rc != MI_OK) return rc; }
     bool ok = false;
-    switch (type) {
-        case MI_CONSTRAINT_DISTANCE: ok = distance.destroy(id); break;
-        case MI_CONSTRAINT_BALL: ok = ball.destroy(id); break;
-        case MI_CONSTRAINT_FIXED: ok = fixed.destroy(id); break;
-        case MI_CONSTRAINT_HINGE: ok = hinge.destroy(id); break;
-        case MI_CONSTRAINT_CONE_TWIST: ok = cone.destroy(id); break;
-        case MI_CONSTRAINT_SLIDER: ok = slider.destroy(id); break;
-    }
+    withType(type, [&](auto& l) { ok = l.destroy(id); });
     return ok ? MI_OK : fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type or id");
 }
-void JointSet::destroyAll() { (void)pullDeviceWrites(); distance.clearAll(); ball.clearAll(); fixed.clearAll(); hinge.clearAll(); cone.clearAll(); slider.clearAll(); }
+void JointSet::destroyAll() { (void)pullDeviceWrites(); each([](uint32_t, auto& l) { l.clearAll(); }); }
 void JointSet::destroyOfEntity(uint32_t entity) {
     struct Hit { uint64_t seq; uint32_t type, handle; };
     std::vector<Hit> hits;
-    auto scan = [&](uint32_t type, const auto& l) { for (size_t d = 0; d < l.pods.size(); ++d) if (l.ents[d].x == entity || l.ents[d].y == entity) hits.push_back(Hit{l.seq[d], type, l.handleAt[d]}); };
-    scan(MI_CONSTRAINT_DISTANCE, distance); scan(MI_CONSTRAINT_BALL, ball); scan(MI_CONSTRAINT_FIXED, fixed);
-    scan(MI_CONSTRAINT_HINGE, hinge); scan(MI_CONSTRAINT_CONE_TWIST, cone); scan(MI_CONSTRAINT_SLIDER, slider);
+    each([&](uint32_t type, const auto& l) { for (size_t d = 0; d < l.pods.size(); ++d) if (l.ents[d].x == entity || l.ents[d].y == entity) hits.push_back(Hit{l.seq[d], type, l.handleAt[d]}); });
     std::sort(hits.begin(), hits.end(), [](const Hit& x, const Hit& y) { return x.seq > y.seq; });   // the entity's edge list is newest first
     for (const Hit& h : hits) (void)destroy(h.type, h.handle);
 }
 int JointSet::add(mi_world& w, uint32_t type, uint32_t ea, uint32_t eb, const void* pod, uint32_t bytes, uint32_t* out) {
     { int rc = pullDeviceWrites(); if (rc != MI_OK) return rc; }
-    switch (type) {
-        case MI_CONSTRAINT_DISTANCE: return jointAddTo(w, distance, ea, eb, pod, bytes, out);
-        case MI_CONSTRAINT_BALL: return jointAddTo(w, ball, ea, eb, pod, bytes, out);
-        case MI_CONSTRAINT_FIXED: return jointAddTo(w, fixed, ea, eb, pod, bytes, out);
-        case MI_CONSTRAINT_HINGE: return jointAddTo(w, hinge, ea, eb, pod, bytes, out);
-        case MI_CONSTRAINT_CONE_TWIST: return jointAddTo(w, cone, ea, eb, pod, bytes, out);
-        case MI_CONSTRAINT_SLIDER: return jointAddTo(w, slider, ea, eb, pod, bytes, out);
-    }
-    return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
+    int rc = MI_OK;
+    return withType(type, [&](auto& l) { rc = jointAddTo(w, l, ea, eb, pod, bytes, out); }) ? rc : fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
 }
 template <class JT> static int jointCopy(JT& l, uint32_t id, void* dst, const void* src, uint32_t bytes) {
     typedef typename std::remove_reference<decltype(l.pods[0])>::type P;
@@ -69,51 +53,32 @@ template <class JT> static int jointCopy(JT& l, uint32_t id, void* dst, const vo
 }
 int JointSet::update(uint32_t type, uint32_t id, const void* pod, uint32_t bytes) {
     { int rc = pullDeviceWrites(); if (rc != MI_OK) return rc; }   // (the re-upload sends the WHOLE array: what the device wrote into other constraints must be in it)
-    switch (type) {
-        case MI_CONSTRAINT_DISTANCE: distance.podsDirty = true; return jointCopy(distance, id, nullptr, pod, bytes);
-        case MI_CONSTRAINT_BALL: ball.podsDirty = true; return jointCopy(ball, id, nullptr, pod, bytes);
-        case MI_CONSTRAINT_FIXED: fixed.podsDirty = true; return jointCopy(fixed, id, nullptr, pod, bytes);
-        case MI_CONSTRAINT_HINGE: hinge.podsDirty = true; return jointCopy(hinge, id, nullptr, pod, bytes);
-        case MI_CONSTRAINT_CONE_TWIST: cone.podsDirty = true; return jointCopy(cone, id, nullptr, pod, bytes);
-        case MI_CONSTRAINT_SLIDER: slider.podsDirty = true; return jointCopy(slider, id, nullptr, pod, bytes);
-    }
-    return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
+    int rc = MI_OK;
+    return withType(type, [&](auto& l) { l.podsDirty = true; rc = jointCopy(l, id, nullptr, pod, bytes); }) ? rc : fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
 }
 // Brings the host mirror up to date with what mi_constraints_update_device_async wrote (per type; a no-op otherwise).  Positions in dPods are positions
 // in `pods` as long as no constraint of the type was created or destroyed since the upload — and both pull first.
 int JointSet::pullDeviceWrites() {
-    if (!(distance.deviceNewer || ball.deviceNewer || fixed.deviceNewer || hinge.deviceNewer || cone.deviceNewer || slider.deviceNewer)) return MI_OK;
+    if (!tryEach([](uint32_t, auto& t) { return t.deviceNewer; })) return MI_OK;
     HIP_TRY(hipSetDevice(mirrorDevice));
-    auto pull = [&](auto& t) -> hipError_t {
+    auto pull = [&](uint32_t, auto& t) -> hipError_t {
         if (!t.deviceNewer) return hipSuccess;
         t.deviceNewer = false;
-        if (t.pods.empty() || !t.dPods || t.pods.size() > t.dCap) return hipSuccess;
-        return hipMemcpyAsync(t.pods.data(), t.dPods, t.pods.size() * sizeof(t.pods[0]), hipMemcpyDeviceToHost, mirrorStream);
+        if (t.pods.empty() || !t.dPods.p || t.pods.size() > t.dPods.cap) return hipSuccess;
+        return hipMemcpyAsync(t.pods.data(), t.dPods.p, t.pods.size() * sizeof(t.pods[0]), hipMemcpyDeviceToHost, mirrorStream);
     };
-    HIP_TRY(pull(distance)); HIP_TRY(pull(ball)); HIP_TRY(pull(fixed)); HIP_TRY(pull(hinge)); HIP_TRY(pull(cone)); HIP_TRY(pull(slider));
+    HIP_TRY(tryEach(pull));   // every pull enqueued, ONE wait
     HIP_TRY(hipStreamSynchronize(mirrorStream));
     return MI_OK;
 }
 int JointSet::uploadPods(hipStream_t st) {   // the host copy is authoritative for the PODs (unless pullDeviceWrites has something to fetch: the callers that dirty it pull first)
-    if (distance.podsDirty) HIP_TRY(distance.uploadPods(st));
-    if (ball.podsDirty) HIP_TRY(ball.uploadPods(st));
-    if (fixed.podsDirty) HIP_TRY(fixed.uploadPods(st));
-    if (hinge.podsDirty) HIP_TRY(hinge.uploadPods(st));
-    if (cone.podsDirty) HIP_TRY(cone.uploadPods(st));
-    if (slider.podsDirty) HIP_TRY(slider.uploadPods(st));
+    HIP_TRY(tryEach([&](uint32_t, auto& l) { return l.podsDirty ? l.uploadPods(st) : hipSuccess; }));
     return MI_OK;
 }
 int JointSet::get(uint32_t type, uint32_t id, void* pod, uint32_t bytes) {
     { int rc = pullDeviceWrites(); if (rc != MI_OK) return rc; }
-    switch (type) {
-        case MI_CONSTRAINT_DISTANCE: return jointCopy(distance, id, pod, nullptr, bytes);
-        case MI_CONSTRAINT_BALL: return jointCopy(ball, id, pod, nullptr, bytes);
-        case MI_CONSTRAINT_FIXED: return jointCopy(fixed, id, pod, nullptr, bytes);
-        case MI_CONSTRAINT_HINGE: return jointCopy(hinge, id, pod, nullptr, bytes);
-        case MI_CONSTRAINT_CONE_TWIST: return jointCopy(cone, id, pod, nullptr, bytes);
-        case MI_CONSTRAINT_SLIDER: return jointCopy(slider, id, pod, nullptr, bytes);
-    }
-    return fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
+    int rc = MI_OK;
+    return withType(type, [&](auto& l) { rc = jointCopy(l, id, pod, nullptr, bytes); }) ? rc : fail(MI_ERR_INVALID_ARGUMENT, "bad constraint type");
 }
 static void put3(float* f, V3 v) { f[0] = v.x; f[1] = v.y; f[2] = v.z; }
 static void put4(float* f, Q4 q) { f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w; }
@@ -180,43 +145,40 @@ int JointSet::upload(mi_world& w, hipStream_t st) {
     mirrorStream = st; mirrorDevice = w.device;
     if (!count()) {   // the last constraint may just have been deleted: nothing of the previous topology may survive
         releaseIslands();
-        distance.order.clear(); ball.order.clear(); fixed.order.clear(); hinge.order.clear(); cone.order.clear(); slider.order.clear();
+        each([](uint32_t, auto& l) { l.order.clear(); });
         return MI_OK;
     }
     std::vector<float> invMass(w.bodies.size());
     for (size_t i = 0; i < w.bodies.size(); ++i) invMass[i] = w.bodies[i].invMass;
-    distance.computeOrder(invMass); ball.computeOrder(invMass); fixed.computeOrder(invMass);
-    hinge.computeOrder(invMass); cone.computeOrder(invMass); slider.computeOrder(invMass);
+    each([&](uint32_t, auto& l) { l.computeOrder(invMass); });
     {
         std::vector<IslandDesc> islands; std::vector<IslandStep> steps; std::vector<uint32_t> islandBodies;
         buildIslands(invMass, islands, steps, islandBodies);
         releaseIslands();
         if (!islands.empty()) {
-            HIP_TRY(hipMalloc((void**)&dIslands, islands.size() * sizeof(IslandDesc)));
-            HIP_TRY(hipMalloc((void**)&dSteps, steps.size() * sizeof(IslandStep))); HIP_TRY(hipMalloc((void**)&dIslandBodies, islandBodies.size() * sizeof(uint32_t)));
-            HIP_TRY(hipMemcpyAsync(dIslands, islands.data(), islands.size() * sizeof(IslandDesc), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(dSteps, steps.data(), steps.size() * sizeof(IslandStep), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(dIslandBodies, islandBodies.data(), islandBodies.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(dIslands.ensure(islands.size())); HIP_TRY(dSteps.ensure(steps.size())); HIP_TRY(dIslandBodies.ensure(islandBodies.size()));
+            HIP_TRY(hipMemcpyAsync(dIslands.p, islands.data(), islands.size() * sizeof(IslandDesc), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(dSteps.p, steps.data(), steps.size() * sizeof(IslandStep), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(dIslandBodies.p, islandBodies.data(), islandBodies.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             std::vector<uint8_t> bodyJ(invMass.size() + 1, 0);
             for (uint32_t b : islandBodies) if (b < invMass.size() && invMass[b] != 0.f) bodyJ[b] = 1;
-            HIP_TRY(hipMalloc((void**)&dBodyJ, bodyJ.size()));
-            HIP_TRY(hipMemcpyAsync(dBodyJ, bodyJ.data(), bodyJ.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(dBodyJ.ensure(bodyJ.size()));
+            HIP_TRY(hipMemcpyAsync(dBodyJ.p, bodyJ.data(), bodyJ.size(), hipMemcpyHostToDevice, st));
             // private islands (joints.hpp): island of every dynamic island body; per-step state and the islands' manifold lists
             std::vector<uint32_t> bodyIsland(invMass.size() + 1, 0xFFFFFFFFu);
             for (uint32_t i = 0; i < (uint32_t)islands.size(); ++i)
                 for (uint32_t k = 0; k < islands[i].numBodies; ++k) { const uint32_t b = islandBodies[islands[i].bodyBegin + k]; if (b < invMass.size() && invMass[b] != 0.f) bodyIsland[b] = i; }
-            HIP_TRY(hipMalloc((void**)&dBodyIsland, bodyIsland.size() * sizeof(uint32_t)));
-            HIP_TRY(hipMemcpyAsync(dBodyIsland, bodyIsland.data(), bodyIsland.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMalloc((void**)&dIslState, 3 * islands.size() * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc((void**)&dIslEntries, islands.size() * (size_t)mi::kIslandMaxContacts * sizeof(uint4)));
+            HIP_TRY(dBodyIsland.ensure(bodyIsland.size()));
+            HIP_TRY(hipMemcpyAsync(dBodyIsland.p, bodyIsland.data(), bodyIsland.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(dIslState.ensure(3 * islands.size()));
+            HIP_TRY(dIslEntries.ensure(islands.size() * (size_t)mi::kIslandMaxContacts));
             HIP_TRY(hipStreamSynchronize(st));   // the staging vectors are locals
             numIslands = (uint32_t)islands.size();
         }
     }
-    distance.finishOrder(); ball.finishOrder(); fixed.finishOrder(); hinge.finishOrder(); cone.finishOrder(); slider.finishOrder();
-    HIP_TRY(distance.upload(st)); HIP_TRY(ball.upload(st)); HIP_TRY(fixed.upload(st));
-    HIP_TRY(hinge.upload(st)); HIP_TRY(cone.upload(st)); HIP_TRY(slider.upload(st));
-    distance.podsDirty = ball.podsDirty = fixed.podsDirty = hinge.podsDirty = cone.podsDirty = slider.podsDirty = false;
+    each([](uint32_t, auto& l) { l.finishOrder(); });
+    HIP_TRY(tryEach([&](uint32_t, auto& l) { return l.upload(st); }));
+    each([](uint32_t, auto& l) { l.podsDirty = false; });
     return MI_OK;
 }
 // Connected components of the joint graph over DYNAMIC bodies; an island small enough for one wave gets a program of
@@ -228,16 +190,16 @@ void JointSet::buildIslands(const std::vector<float>& invMass, std::vector<Islan
     auto find = [&](uint32_t x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
     struct Ref { uint32_t type, joint, color; uint2 bodies; };
     std::vector<Ref> all;
-    auto collect = [&](uint32_t type, const std::vector<uint2>& bodies, const std::vector<uint32_t>& colorOf) {
-        for (uint32_t j = 0; j < (uint32_t)bodies.size(); ++j) {
-            uint2 b = bodies[j];
+    uint8_t* flags[6];   // by type: JointType::inIsland
+    each([&](uint32_t type, auto& l) {
+        flags[type] = l.inIsland.data();
+        for (uint32_t j = 0; j < (uint32_t)l.bodies.size(); ++j) {
+            uint2 b = l.bodies[j];
             bool dynA = b.x < nb && invMass[b.x] != 0.f, dynB = b.y < nb && invMass[b.y] != 0.f;
             if (dynA && dynB) parent[find(b.x)] = find(b.y);
-            all.push_back(Ref{type, j, colorOf[j], b});
+            all.push_back(Ref{type, j, l.colorOf[j], b});
         }
-    };
-    collect(0, distance.bodies, distance.colorOf); collect(1, ball.bodies, ball.colorOf); collect(2, fixed.bodies, fixed.colorOf);
-    collect(3, hinge.bodies, hinge.colorOf); collect(4, cone.bodies, cone.colorOf); collect(5, slider.bodies, slider.colorOf);
+    });
     // joints by island root (a joint between two non-dynamic bodies does nothing; it stays with the per-colour kernels)
     std::vector<std::vector<uint32_t>> byRoot(nb);
     for (uint32_t r = 0; r < (uint32_t)all.size(); ++r) {
@@ -245,7 +207,6 @@ void JointSet::buildIslands(const std::vector<float>& invMass, std::vector<Islan
         bool dynA = ref.bodies.x < nb && invMass[ref.bodies.x] != 0.f, dynB = ref.bodies.y < nb && invMass[ref.bodies.y] != 0.f;
         if (dynA || dynB) byRoot[find(dynA ? ref.bodies.x : ref.bodies.y)].push_back(r);
     }
-    uint8_t* flags[6] = {distance.inIsland.data(), ball.inIsland.data(), fixed.inIsland.data(), hinge.inIsland.data(), cone.inIsland.data(), slider.inIsland.data()};
     for (uint32_t root = 0; root < nb; ++root) {
         std::vector<uint32_t>& js = byRoot[root];
         if (js.empty()) continue;
@@ -279,23 +240,20 @@ int JointSet::initialize(mi_world& w, float dt, hipStream_t st) {
     BodyView bv = bodyView(w);
     uint32_t dummy = (uint32_t)w.bodies.size();
     mi::Launcher& L = w.L;
-    distance.launchInit(L, dummy, bv, dt, st); ball.launchInit(L, dummy, bv, dt, st); fixed.launchInit(L, dummy, bv, dt, st);
-    hinge.launchInit(L, dummy, bv, dt, st); cone.launchInit(L, dummy, bv, dt, st); slider.launchInit(L, dummy, bv, dt, st);
+    each([&](uint32_t, auto& l) { l.launchInit(L, dummy, bv, dt, st); });
     return MI_OK;
 }
 int JointSet::solveIterationReference(mi_world& w, hipStream_t st) {
     if (!count()) return MI_OK;
     BodyView bv = bodyView(w);
     mi::Launcher& L = w.L;
-    HIP_TRY(distance.launchSolveReference(L, bv, st)); HIP_TRY(ball.launchSolveReference(L, bv, st)); HIP_TRY(fixed.launchSolveReference(L, bv, st));
-    HIP_TRY(hinge.launchSolveReference(L, bv, st)); HIP_TRY(cone.launchSolveReference(L, bv, st)); HIP_TRY(slider.launchSolveReference(L, bv, st));
+    HIP_TRY(tryEach([&](uint32_t, auto& l) { return l.launchSolveReference(L, bv, st); }));
     return MI_OK;
 }
 void JointSet::solveIteration(mi_world& w, hipStream_t st) {
     if (!count()) return;
     BodyView bv = bodyView(w);
     mi::Launcher& L = w.L;
-    if (numIslands) L.launch(k_joint_islands, dim3(numIslands), dim3(64), 0, st, dIslands, dSteps, dIslandBodies, IslandUpd{distance.dUpd, ball.dUpd, fixed.dUpd, hinge.dUpd, cone.dUpd, slider.dUpd}, bv);
-    distance.launchSolve(L, bv, st); ball.launchSolve(L, bv, st); fixed.launchSolve(L, bv, st);
-    hinge.launchSolve(L, bv, st); cone.launchSolve(L, bv, st); slider.launchSolve(L, bv, st);
+    if (numIslands) L.launch(k_joint_islands, dim3(numIslands), dim3(64), 0, st, dIslands.p, dSteps.p, dIslandBodies.p, islandUpd(), bv);
+    each([&](uint32_t, auto& l) { l.launchSolve(L, bv, st); });
 }

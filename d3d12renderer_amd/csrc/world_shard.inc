@@ -54,8 +54,7 @@ int mi_world::shardBuildRoots() {
     std::vector<uint32_t> parent(nb);
     for (uint32_t i = 0; i < nb; ++i) parent[i] = i;
     auto find = [&](uint32_t x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
-    auto link = [&](const auto& t) { for (const uint2& b : t.bodies) { uint32_t x = find(b.x), y = find(b.y); if (x != y) parent[std::max(x, y)] = std::min(x, y); } };
-    link(joints.distance); link(joints.ball); link(joints.fixed); link(joints.hinge); link(joints.cone); link(joints.slider);
+    joints.each([&](uint32_t, const auto& t) { for (const uint2& b : t.bodies) { uint32_t x = find(b.x), y = find(b.y); if (x != y) parent[std::max(x, y)] = std::min(x, y); } });
     for (uint32_t i = 0; i < nb; ++i) parent[i] = find(i);
     HIP_TRY(shard.root.ensure(std::max(nb, 1u))); HIP_TRY(shard.active.ensure(std::max(nb, 1u)));
     if (nb) HIP_TRY(hipMemcpy(shard.root.p, parent.data(), (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice));

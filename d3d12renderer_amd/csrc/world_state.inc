@@ -18,8 +18,6 @@ constexpr uint32_t kCheckpointHasShard = 1u;
 struct CheckpointShard { uint32_t numRanks, rank, tilesX, tilesZ, bordersPending, knownBytes; };
 template <class T> void put(std::vector<uint8_t>& out, const T* p, size_t n) { const uint8_t* b = reinterpret_cast<const uint8_t*>(p); out.insert(out.end(), b, b + n * sizeof(T)); }
 template <class T> bool take(const uint8_t*& p, const uint8_t* end, T* out, size_t n) { if ((size_t)(end - p) < n * sizeof(T)) return false; std::memcpy(out, p, n * sizeof(T)); p += n * sizeof(T); return true; }
-template <class JT> void putPods(std::vector<uint8_t>& out, const JT& j) { if (!j.pods.empty()) put(out, j.pods.data(), j.pods.size()); }
-template <class JT> bool takePods(const uint8_t*& p, const uint8_t* end, JT& j) { return j.pods.empty() || take(p, end, j.pods.data(), j.pods.size()); }
 }
 }
 MI_API int mi_world_save_checkpoint(mi_world* w, void* out, uint64_t capacity, uint64_t* out_size) {
@@ -41,15 +39,14 @@ MI_API int mi_world_save_checkpoint(mi_world* w, void* out, uint64_t capacity, u
     h.sapAxis = w->sapAxis; h.timer = w->timer; h.eventsEnabled = w->eventsEnabled ? 1u : 0u;
     h.reserved = w->shard.enabled ? kCheckpointHasShard : 0u;
     const JointSet& j = w->joints;
-    h.jointCounts[0] = (uint32_t)j.distance.pods.size(); h.jointCounts[1] = (uint32_t)j.ball.pods.size(); h.jointCounts[2] = (uint32_t)j.fixed.pods.size();
-    h.jointCounts[3] = (uint32_t)j.hinge.pods.size(); h.jointCounts[4] = (uint32_t)j.cone.pods.size(); h.jointCounts[5] = (uint32_t)j.slider.pods.size();
+    j.each([&](uint32_t type, const auto& l) { h.jointCounts[type] = (uint32_t)l.pods.size(); });
     std::vector<uint8_t> blob;
     put(blob, &h, 1);
     for (const HEntity& e : w->entities) { put(blob, &e.pos, 1); put(blob, &e.rot, 1); }
     for (const HBody& b : w->bodies) { put(blob, &b.p0, 1); put(blob, &b.r0, 1); put(blob, &b.p1, 1); put(blob, &b.r1, 1); put(blob, &b.linVel, 1); put(blob, &b.angVel, 1); put(blob, &b.force, 1); put(blob, &b.torque, 1); }
     if (!keys.empty()) { put(blob, keys.data(), keys.size()); put(blob, vals.data(), vals.size()); }
     if (!w->prevTriggerOverlaps.empty()) put(blob, w->prevTriggerOverlaps.data(), w->prevTriggerOverlaps.size());
-    putPods(blob, j.distance); putPods(blob, j.ball); putPods(blob, j.fixed); putPods(blob, j.hinge); putPods(blob, j.cone); putPods(blob, j.slider);
+    j.each([&](uint32_t, const auto& l) { if (!l.pods.empty()) put(blob, l.pods.data(), l.pods.size()); });
     {   // cloths: particle state (positions incl. inverse mass, previous positions, velocities, force accumulators) and the editable properties
         const uint32_t numCloths = (uint32_t)w->cloths.size();
         put(blob, &numCloths, 1);
@@ -92,16 +89,16 @@ MI_API int mi_world_load_checkpoint(mi_world* w, const void* data, uint64_t size
         if (!take(p, end, &h, 1) || h.magic != kCheckpointMagic || h.version != 1) return fail(MI_ERR_INVALID_ARGUMENT, "not a checkpoint of this library version");
         JointSet& j = w->joints;
         { int prc = j.pullDeviceWrites(); if (prc != MI_OK) return prc; }   // (the blob's PODs replace the mirror; nothing newer may be pulled over them later)
-        const uint32_t jc[6] = {(uint32_t)j.distance.pods.size(), (uint32_t)j.ball.pods.size(), (uint32_t)j.fixed.pods.size(), (uint32_t)j.hinge.pods.size(), (uint32_t)j.cone.pods.size(), (uint32_t)j.slider.pods.size()};
+        uint32_t jc[6]; uint64_t podBytes = 0;   // the POD section: the types' arrays one after the other
+        j.each([&](uint32_t type, const auto& l) { jc[type] = (uint32_t)l.pods.size(); podBytes += (uint64_t)l.pods.size() * sizeof(l.pods[0]); });
         if (h.numEntities != w->entities.size() || h.numBodies != w->bodies.size() || h.numColliders != w->colliders.size() || std::memcmp(jc, h.jointCounts, sizeof(jc)) != 0)
             return fail(MI_ERR_INVALID_ARGUMENT, "checkpoint belongs to a different scene (entity / body / collider / constraint counts differ)");
         // exact size the header implies (64-bit arithmetic; the cloth section is checked against the world's own cloths)
         const uint64_t entityBytes = sizeof(w->entities[0].pos) + sizeof(w->entities[0].rot);
         const uint64_t bodyBytes = sizeof(HBody::p0) + sizeof(HBody::r0) + sizeof(HBody::p1) + sizeof(HBody::r1) + sizeof(HBody::linVel) + sizeof(HBody::angVel) + sizeof(HBody::force) + sizeof(HBody::torque);
-        auto podBytes = [](const auto& t) -> uint64_t { return t.pods.empty() ? 0ull : (uint64_t)t.pods.size() * sizeof(t.pods[0]); };
         uint64_t expect = sizeof(CheckpointHeader) + (uint64_t)h.numEntities * entityBytes + (uint64_t)h.numBodies * bodyBytes
                         + (uint64_t)h.numHistory * (sizeof(unsigned long long) + sizeof(uint32_t)) + (uint64_t)h.numTriggerOverlaps * sizeof(w->prevTriggerOverlaps[0])
-                        + podBytes(j.distance) + podBytes(j.ball) + podBytes(j.fixed) + podBytes(j.hinge) + podBytes(j.cone) + podBytes(j.slider) + sizeof(uint32_t);
+                        + podBytes + sizeof(uint32_t);
         for (const mi_world::HCloth* c : w->cloths) {
             const uint64_t n = (uint64_t)c->desc.grid_size_x * c->desc.grid_size_y;
             expect += sizeof(mi_cloth_desc) + 2 * sizeof(float) + 4 * n * sizeof(float4) + (uint64_t)c->restInvMass.size() * sizeof(c->restInvMass[0]);
@@ -124,9 +121,8 @@ MI_API int mi_world_load_checkpoint(mi_world* w, const void* data, uint64_t size
         okay = okay && take(p, end, keys.data(), keys.size()) && take(p, end, vals.data(), vals.size());
         auto overlaps = w->prevTriggerOverlaps; overlaps.resize(h.numTriggerOverlaps);
         okay = okay && take(p, end, overlaps.data(), overlaps.size());
-        auto pDistance = j.distance.pods; auto pBall = j.ball.pods; auto pFixed = j.fixed.pods; auto pHinge = j.hinge.pods; auto pCone = j.cone.pods; auto pSlider = j.slider.pods;
-        auto takeVec = [&](auto& v) { return v.empty() || take(p, end, v.data(), v.size()); };
-        okay = okay && takeVec(pDistance) && takeVec(pBall) && takeVec(pFixed) && takeVec(pHinge) && takeVec(pCone) && takeVec(pSlider);
+        std::vector<uint8_t> podSection((size_t)podBytes);   // staged whole (sized by the world's own pools, which the header's counts equal); copied into the pools type by type at commit
+        okay = okay && take(p, end, podSection.data(), podSection.size());
         uint32_t numCloths = 0;
         okay = okay && take(p, end, &numCloths, 1);
         if (!okay) return fail(MI_ERR_INVALID_ARGUMENT, "truncated checkpoint");
@@ -176,7 +172,8 @@ MI_API int mi_world_load_checkpoint(mi_world* w, const void* data, uint64_t size
         for (size_t i = 0; i < es.size(); ++i) { w->entities[i].pos = es[i].pos; w->entities[i].rot = es[i].rot; }
         for (size_t i = 0; i < bs.size(); ++i) { HBody& b = w->bodies[i]; b.p0 = bs[i].p0; b.r0 = bs[i].r0; b.p1 = bs[i].p1; b.r1 = bs[i].r1; b.linVel = bs[i].linVel; b.angVel = bs[i].angVel; b.force = bs[i].force; b.torque = bs[i].torque; }
         w->prevTriggerOverlaps = std::move(overlaps);
-        j.distance.pods = std::move(pDistance); j.ball.pods = std::move(pBall); j.fixed.pods = std::move(pFixed); j.hinge.pods = std::move(pHinge); j.cone.pods = std::move(pCone); j.slider.pods = std::move(pSlider);
+        const uint8_t* podAt = podSection.data();
+        j.each([&](uint32_t, auto& l) { const size_t n = l.pods.size() * sizeof(l.pods[0]); if (n) std::memcpy(l.pods.data(), podAt, n); podAt += n; });
         for (size_t k = 0; k < cs.size(); ++k) {
             mi_world::HCloth* c = w->cloths[k]; ClothState& t = cs[k];
             const uint32_t n = c->desc.grid_size_x * c->desc.grid_size_y;

@@ -777,19 +777,19 @@ int mi_world::stageConstraintInit(StepAttempt& a) {
     // the persistent kernel keeps the accumulated impulses in LDS while they fit: k_contact_init then need not write the impulse granules
     a.persistPlan = !fused && a.useFlow && persistSolver && joints.count() == 0 && tilesLaunch && !exactSeamStep();
     a.persistMaxSlots = a.persistPlan ? persistSlots(a) : 0u;
-    const bool privateIslands = fused && privateIslandsEnabled && !shard.enabled && joints.dBodyIsland && nmBound && tilesLaunch;
+    const bool privateIslands = fused && privateIslandsEnabled && !shard.enabled && joints.dBodyIsland.p && nmBound && tilesLaunch;
     const IslandPrivate islandPriv = a.islandPriv = privateIslands ? joints.islandPrivate() : IslandPrivate{nullptr, nullptr, nullptr, nullptr, nullptr};
     const bool impNeeded = !(a.persistPlan && persistImpLds && a.persistMaxSlots * (4u * 512u + 24u) <= 38u * 1024u);
     if (nmBound) {
         HIP_TRY(slotMeta.ensure((size_t)tilesCap * 64)); HIP_TRY(slotNormal.ensure((size_t)tilesCap * 64)); HIP_TRY(slotMass.ensure((size_t)tilesCap * 64));
         HIP_TRY(rows.ensure((size_t)ctCap * kRows * 64)); HIP_TRY(imp.ensure((size_t)ctCap * 64));
         if (privateIslands) {   // which joint islands are private this step (joints.hpp "PRIVATE islands"): their manifolds go to the island's own workgroup
-            HIP_TRY(L.memsetAsync(joints.dIslState, 0, 3 * (size_t)joints.numIslands * sizeof(uint32_t), st));
+            HIP_TRY(L.memsetAsync(joints.dIslState.p, 0, 3 * (size_t)joints.numIslands * sizeof(uint32_t), st));
             L.launch(k_island_classify, dim3(divUp(nmBound, B)), dim3(B), 0, st, sc, colWork.p, color.p, islandPriv);
         }
         if (tilesLaunch)
             L.launch(k_contact_init, dim3(xcdPlan ? 8u * xcdListCap : tilesLaunch), dim3(64), 0, st, sc, nb, a.dt, xcdPlan ? xcdInfo.p : tileInfo.p, order.p, manPair.p, manBodies.p, manInfo.p, npNormal.p, npPoints.p,
-                                                      gPos.p, gInvI.p, xcdPlan ? gVelL.p : gVel.p /* same content here; the cached copy */, color.p, bodyUsed.p, fused ? joints.dBodyJ : nullptr, rows.p, impNeeded ? imp.p : nullptr, slotMeta.p, slotNormal.p, slotMass.p,
+                                                      gPos.p, gInvI.p, xcdPlan ? gVelL.p : gVel.p /* same content here; the cached copy */, color.p, bodyUsed.p, fused ? joints.dBodyJ.p : nullptr, rows.p, impNeeded ? imp.p : nullptr, slotMeta.p, slotNormal.p, slotMass.p,
                                                       xcdPlan ? reinterpret_cast<uint8_t*>(bodyOwner.p) : nullptr, xcdListCap, xcdPlan ? 8u * xcdListCap : tilesCap, islandPriv);
     }
     return joints.initialize(*this, a.dt, st);   // (through L)
@@ -813,11 +813,11 @@ int mi_world::solveFused(StepAttempt& a) {
     const uint32_t perLaunch = per * iters < 0x7FFFFFFFull ? iters : 1u;
     solveLaunches = (iters + perLaunch - 1) / perLaunch;
     BodyView bv{gPos.p, gInvI.p, gVel.p, bRot.p, bCogInvMass.p, shard.enabled ? shard.active.p : nullptr};
-    const IslandUpd iu{joints.distance.dUpd, joints.ball.dUpd, joints.fixed.dUpd, joints.hinge.dUpd, joints.cone.dUpd, joints.slider.dUpd};
-    const IslandAcc ia{joints.hinge.dAcc, joints.cone.dAcc, joints.slider.dAcc};
+    const IslandUpd iu = joints.islandUpd();
+    const IslandAcc ia = joints.islandAcc();
     for (uint32_t it = 0; it < iters; it += perLaunch) {
         int rc = profileBegin(); if (rc != MI_OK) return rc;
-        L.launch(k_solve_flow_islands, dim3((uint32_t)(per * perLaunch)), dim3(64), 0, stream, it, perLaunch, joints.numIslands, joints.dIslands, joints.dSteps, joints.dIslandBodies, iu, ia, bv, bodyUsed.p,
+        L.launch(k_solve_flow_islands, dim3((uint32_t)(per * perLaunch)), dim3(64), 0, stream, it, perLaunch, joints.numIslands, joints.dIslands.p, joints.dSteps.p, joints.dIslandBodies.p, iu, ia, bv, bodyUsed.p,
                                                                                tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, scalarsPtr(), a.islandPriv, iters);
         profileEnd();
     }
@@ -857,7 +857,7 @@ int mi_world::solveFlow(StepAttempt& a) {
     const uint32_t perLaunch = joints.count() == 0 && !exactSeam && (uint64_t)std::max(tilesLaunch, 1u) * iters < 0x7FFFFFFFull ? iters : 1u;
     solveLaunches = tilesLaunch ? (iters + perLaunch - 1) / perLaunch : 0;
     for (uint32_t it = 0; it < iters; it += perLaunch) {
-        if (perLaunch == 1) joints.solveIteration(*this, st);   // distance, ball, fixed, hinge, cone-twist, slider (constraints.cpp:3764-3769)
+        if (perLaunch == 1) joints.solveIteration(*this, st);   // the six types in JointSet's order (constraints.cpp:3764-3769)
         if (!tilesLaunch) { if (exactSeam) { int rcx = shardSweepExchange(it); if (rcx != MI_OK) return rcx; } continue; }
         int rc = profileBegin(); if (rc != MI_OK) return rc;
         L.launch(k_contact_solve_flow, dim3(tilesLaunch * perLaunch), dim3(64), 0, st, it, perLaunch, tileDesc.p, slotMeta.p, slotNormal.p, slotMass.p, rows.p, imp.p, gVel.p, scalarsPtr());

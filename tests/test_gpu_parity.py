@@ -401,6 +401,54 @@ def test_gpu_constraint_deletion_matches_oracle(mi_lib, oracle_mod):
     run(30)
 
 
+@pytest.mark.gpu
+def test_gpu_every_joint_type_through_every_entry_point(mi_lib, oracle_mod):
+    """get / update / destroy / device indices of each of the six constraint types (joint_zoo: the smallest scene with every type present more than
+    once), an unknown type refused, then per-entity and wholesale deletion while the scene runs — GPU world and canonical oracle side by side, bytes equal.
+    (The unknown type goes to constraint_get through the C ABI itself: the binding's get_constraint looks its dtype up first and never gets there.
+    The deletion of id 0 moves the type's last handle into dense slot 0, which is handle 2 only for the three types with three joints.)"""
+    import ctypes as C
+    sc = scenes.joint_zoo(copies=1)
+    g = sc.populate(gpu_world(mi_lib)); o = sc.populate(oracle_mod.create_world(oracle_mod.ORDER_CANONICAL))
+    both = (g, o)
+    for t in range(len(capi.CONSTRAINT_DTYPES)):
+        before = [g.get_constraint(t, i) for i in range(3)]
+        for i in range(3):
+            assert o.get_constraint(t, i).tobytes() == before[i].tobytes(), f"type {t}, id {i}"
+        edited = before[1].copy(); edited["local_anchor_a"] *= np.float32(0.9)   # (every POD has the field; the distance chains anchor at the origin)
+        for w in both:
+            w.update_constraint(t, 1, edited)
+            assert w.get_constraint(t, 1).tobytes() == edited.tobytes(), f"type {t}: update"
+            w.destroy_constraint(t, 0)
+            with pytest.raises(mi_lib.PhysicsError):
+                w.get_constraint(t, 0)
+            assert w.get_constraint(t, 2).tobytes() == before[2].tobytes(), f"type {t}: id 2 after the deletion of id 0"
+            assert w.get_constraint(t, 1).tobytes() == edited.tobytes()
+        # swap-and-pop moves the type's LAST handle into dense slot 0: handle 2 where the type has three joints (distance, ball, fixed), else handle n - 1
+        n = [c[0] for c in sc.global_constraints].count(t)
+        assert n >= 3 and list(g.constraints_to_device_indices(t, [1, 2, n - 1])) == [1, 0 if n == 3 else 2, 0], f"type {t}: dense slots after the deletion of id 0"
+    for w in both:
+        with pytest.raises((mi_lib.PhysicsError, IndexError)):
+            w.get_constraint(6, 0)
+        with pytest.raises(mi_lib.PhysicsError):
+            buf = np.zeros(128, np.uint8)
+            w.L.check(w.L.fn("constraint_get")(w.h, C.c_uint32(6), C.c_uint32(0), buf.ctypes.data_as(C.c_void_p), C.c_uint32(28)), "constraint_get")
+        with pytest.raises(mi_lib.PhysicsError):
+            w.destroy_constraint(6, 0)
+    s = sc.settings()
+    def run(n):
+        for i in range(n):
+            for w in both: w.step_fixed(s, sc.dt, 1)
+            assert g.counts() == o.counts(), f"step {i} of {n}"
+        for x, y in zip(g.physics_transforms() + g.velocities(), o.physics_transforms() + o.velocities()):
+            assert x.tobytes() == y.tobytes()
+    run(30)
+    for w in both: w.destroy_entity_constraints(22)
+    run(20)
+    for w in both: w.destroy_all_constraints()
+    run(10)
+
+
 @pytest.mark.parametrize("iters", [(0, 1, 0), (2, 3, 1)])
 def test_gpu_cloth_matches_oracle(mi_lib, oracle_mod, iters):
     """cloth_component on the device (one workgroup per cloth, 12-colour Gauss-Seidel passes, per-vertex wind gather) against
@@ -825,7 +873,10 @@ def test_gpu_body_state_exchange_api(mi_lib):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("make,victims", [(lambda: scenes.shape_zoo(), [3, 77, 143, 10, 11, 142]), (lambda: scenes.ragdolls(3, 3), [5, 20, 55, 0, 100]),
-                                          (lambda: scenes.zones(), [4, 111, 60, 113, 108])], ids=["zoo", "ragdolls", "zones"])
+                                          (lambda: scenes.zones(), [4, 111, 60, 113, 108]),
+                                          # a link of the distance, fixed, cone-twist, slider, hinge and ball chains and a kinematic anchor: the body swapped into
+                                          # every hole belongs to a slider chain, so the re-pointing and the per-entity deletion run over all six joint pools
+                                          (lambda: scenes.joint_zoo(copies=1), [1, 10, 30, 45, 22, 5, 12])], ids=["zoo", "ragdolls", "zones", "joint_zoo"])
 def test_gpu_entity_deletion_matches_oracle(mi_lib, oracle_mod, make, victims):
     """mi_entity_destroy = game_scene::deleteEntity (scene.cpp:124-150) while the simulation runs: bodies with one and several
     colliders, bodies with joints, triggers, a force field.  The pools follow EnTT's swap-and-pop (the oracle's deletion is pinned

@@ -92,7 +92,8 @@ def test_gpu_yaml_scene_matches_oracle(mi_lib, oracle_mod):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("make,events", [(lambda: scenes.zones(), True), (lambda: scenes.ragdolls(3, 3), False), (lambda: scenes.terrain_field(6, 2, 6), False)])
+@pytest.mark.parametrize("make,events", [(lambda: scenes.zones(), True), (lambda: scenes.ragdolls(3, 3), False), (lambda: scenes.terrain_field(6, 2, 6), False),
+                                         (lambda: scenes.joint_zoo(copies=1), False)])   # every joint type in the POD section
 def test_gpu_checkpoint_resume_is_bit_identical(mi_lib, oracle_mod, make, events):
     """Save after 70 steps, load into a FRESH world built from the same scene, continue: poses, velocities, counts and events
     equal the uninterrupted run (and the oracle) bit for bit — colour history, SAP axis, trigger overlaps, accumulators, motor
@@ -119,6 +120,16 @@ def test_gpu_checkpoint_resume_is_bit_identical(mi_lib, oracle_mod, make, events
             assert a.poll_events().tobytes() == o.poll_events().tobytes()
     a.set_cloth_properties(0, 4.0, 0.7, 0.5, 0.9); o.set_cloth_properties(0, 4.0, 0.7, 0.5, 0.9)
     blob = a.save_checkpoint()
+    joint_types = [c[0] for c in sc.constraints] + [c[0] for c in sc.global_constraints]
+    if joint_types:
+        # the POD section's place and order: after the header (68 bytes), entities (28 each), bodies (104), history (12) and trigger overlaps (8);
+        # the six types in CONSTRAINT_DTYPES order, each in pool order = creation order (nothing was deleted)
+        import struct
+        _, _, ne, nb, _, nhist, ntrig, _ = struct.unpack_from("<8I", blob, 0)
+        at = 68 + 28 * ne + 104 * nb + 12 * nhist + 8 * ntrig
+        pods = b"".join(a.get_constraint(t, i).tobytes() for t in range(len(capi.CONSTRAINT_DTYPES)) for i in range(joint_types.count(t)))
+        assert len(pods) == sum(capi.CONSTRAINT_DTYPES[t].itemsize for t in joint_types) > 0
+        assert blob[at:at + len(pods)] == pods, "constraint PODs are not where / in the order the checkpoint format has them"
     b = build(mi_lib.create_world(0))
     if events:
         b.enable_events()
