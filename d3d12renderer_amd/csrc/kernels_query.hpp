@@ -293,28 +293,69 @@ __device__ __forceinline__ unsigned long long qTestCollider(const QueryScene& s,
 }
 
 // ---- terrain: the collision triangles of heightmap.hpp, (A, B, C) and (C, B, D) of cell (qx, qz); a point on a shared edge belongs to both
-__device__ __forceinline__ void qTerrainTriangle(const HeightmapParams& hm, uint32_t gx, uint32_t gz, uint32_t tri, V3& p0, V3& n, V3& corner) {
+// the four vertices of cell (gx, gz), of a chunk that has heights: a (qx, qz), b (qx, qz + 1), c (qx + 1, qz), e (qx + 1, qz + 1)
+__device__ __forceinline__ void qTerrainCellVertices(const HeightmapParams& hm, uint32_t gx, uint32_t gz, V3& a, V3& b, V3& c, V3& e) {
     const uint32_t cx = gx >> 7, cz = gz >> 7, qx = gx & 127u, qz = gz & 127u;
     const uint16_t* heights = hm.heights + (size_t)hm.chunkSlot[cz * hm.chunksPerDim + cx] * kHmVerts * kHmVerts;
     const V3 chunkMin = V3((float)cx * hm.chunkSize, 0.f, (float)cz * hm.chunkSize) + V3(hm.minX, hm.minY, hm.minZ);
-    const V3 a = hmVertex(hm, heights, chunkMin, qx, qz), b = hmVertex(hm, heights, chunkMin, qx, qz + 1u), c = hmVertex(hm, heights, chunkMin, qx + 1u, qz);
-    corner = a;
-    if (tri == 0u) { p0 = a; n = cross(b - a, c - a); }
-    else { const V3 d = hmVertex(hm, heights, chunkMin, qx + 1u, qz + 1u); p0 = c; n = cross(b - c, d - c); }
+    a = hmVertex(hm, heights, chunkMin, qx, qz); b = hmVertex(hm, heights, chunkMin, qx, qz + 1u);
+    c = hmVertex(hm, heights, chunkMin, qx + 1u, qz); e = hmVertex(hm, heights, chunkMin, qx + 1u, qz + 1u);
 }
-__device__ __forceinline__ bool qRayTerrainTriangle(const HeightmapParams& hm, uint32_t gx, uint32_t gz, uint32_t tri, V3 o, V3 d, float& t) {
-    V3 p0, n, corner; qTerrainTriangle(hm, gx, gz, tri, p0, n, corner);
+// the upward normal (not unit) of triangle `tri` of the cell
+__device__ __forceinline__ V3 qTerrainNormal(const HeightmapParams& hm, uint32_t gx, uint32_t gz, uint32_t tri) {
+    V3 a, b, c, e; qTerrainCellVertices(hm, gx, gz, a, b, c, e);
+    return tri == 0u ? cross(b - a, c - a) : cross(b - c, e - c);
+}
+// The ray against the two triangles of cell (gx, gz), which its footprint crosses from parameter ta to tb.  Watertight by construction: the decision
+// is a change of sign of the ray's height above the surface between SAMPLES, and every sample on the cell's rim is one both neighbours compute
+// from the same numbers: the same t (one cell's exit is the next one's entry), the same two vertex heights, the same coordinate along the
+// edge relative to the same vertex.  The cell's diagonal, where the footprint crosses it (tDiag), is sampled once for both triangles.  So a
+// ray whose samples begin above the surface and end below it finds the sign change in exactly one place, whatever o + t d rounds to at
+// coordinates of thousands.  Only where the ray begins (entry 0) there is no rim sample: the plane of the triangle under it is, at the
+// ray's point relative to the cell's corner (the plane's height times the cell's area: only signs are compared).
+// t is the crossing of the owning triangle's plane, held to that triangle's piece of [ta, tb]: never a neighbour's plane beyond a rounding
+// of the rim.  A sample of exactly zero counts for both sides: an origin on the surface is a hit at t = 0.
+__device__ __forceinline__ float qRayOverEdge(float oy, float dy, float r0, float dr, float s, float h0, float h1, float t) {
+    const float f = qclamp01(fmaf(t, dr, r0) / s);   // along the edge from the vertex of h0; fmaf by name: no contraction to differ between two inlined copies
+    return fmaf(-f, h1 - h0, fmaf(t, dy, oy - h0));
+}
+__device__ __forceinline__ bool qSignChange(float g0, float g1) { return (g0 <= 0.f && g1 >= 0.f) || (g0 >= 0.f && g1 <= 0.f); }
+// entry: 0 the ray begins in this cell (at ta), 1 it came in through an x line, 2 through a z line; exitX: it leaves through an x line (at tb)
+__device__ inline bool qRayTerrainCell(const HeightmapParams& hm, uint32_t gx, uint32_t gz, V3 o, V3 d, float ta, float tb, int entry, bool exitX, float& t, uint32_t& tri) {
+    V3 a, b, c, e; qTerrainCellVertices(hm, gx, gz, a, b, c, e);
+    const float s = hm.chunkScale, rx = o.x - a.x, rz = o.z - a.z;   // relative to the cell's corner before anything is multiplied
+    // the footprint is on triangle 0's side of the diagonal while rx + rz + t (d.x + d.z) < s
+    const float along = d.x + d.z, left = s - rx - rz;
+    const uint32_t first = (along > 0.f || (along == 0.f && left >= 0.f)) ? 0u : 1u;
+    const float tDiag = along != 0.f ? left / along : FLT_MAX;
+    const V3 n0 = cross(b - a, c - a), n1 = cross(b - c, e - c);
+    const uint32_t kA = ta < tDiag ? first : 1u - first;
+    const bool lowX = d.x > 0.f, lowZ = d.z > 0.f;               // the side it comes in through; it leaves through the other
+    const V3 start(fmaf(ta, d.x, rx), fmaf(ta, d.y, o.y - a.y), fmaf(ta, d.z, rz));   // the ray's point at ta from the corner, as the rim samples take it
+    const float gA = entry == 0 ? (kA == 0u ? dot(start, n0) : dot(start - (c - a), n1))
+                   : entry == 1 ? (lowX ? qRayOverEdge(o.y, d.y, rz, d.z, s, a.y, b.y, ta) : qRayOverEdge(o.y, d.y, rz, d.z, s, c.y, e.y, ta))
+                                : (lowZ ? qRayOverEdge(o.y, d.y, rx, d.x, s, a.y, c.y, ta) : qRayOverEdge(o.y, d.y, rx, d.x, s, b.y, e.y, ta));
+    const float gB = exitX ? (lowX ? qRayOverEdge(o.y, d.y, rz, d.z, s, c.y, e.y, tb) : qRayOverEdge(o.y, d.y, rz, d.z, s, a.y, b.y, tb))
+                           : (lowZ ? qRayOverEdge(o.y, d.y, rx, d.x, s, b.y, e.y, tb) : qRayOverEdge(o.y, d.y, rx, d.x, s, a.y, c.y, tb));
+    float lo = ta, hi = tb;
+    tri = kA;
+    if (tDiag > ta && tDiag < tb) {
+        const float gD = qRayOverEdge(o.y, d.y, rx, d.x, s, b.y, c.y, tDiag);
+        if (qSignChange(gA, gD)) hi = tDiag;
+        else if (qSignChange(gD, gB)) { lo = tDiag; tri = 1u - first; }
+        else return false;
+    } else if (!qSignChange(gA, gB)) return false;
+    const V3 p0 = tri == 0u ? a : c, n = tri == 0u ? n0 : n1;
     const float dn = dot(d, n);
-    if (dn == 0.f) return false;
-    t = dot(p0 - o, n) / dn;
-    const V3 p = o + t * d;
-    const float u = (p.x - corner.x) / hm.chunkScale, v = (p.z - corner.z) / hm.chunkScale, e = 1e-4f;
-    return tri == 0u ? (u >= -e && v >= -e && u + v <= 1.f + e) : (u <= 1.f + e && v <= 1.f + e && u + v >= 1.f - e);
+    t = dn != 0.f ? dot(p0 - o, n) / dn : lo;
+    if (!(t >= lo)) t = lo;
+    if (t > hi) t = hi;
+    return true;
 }
-// 2D DDA over the terrain cells from t = 0 on; stops after the first cell that holds a hit (and behind tMax).  useBounds: an 8 x 8-cell block
-// whose height range (the mips' level 3) the ray's y range over the block misses by more than a tolerance is crossed without testing its cells, and so is
-// a cell whose own range (level 0) it misses; only such cells are not tested, so the hit is the one the walk without them finds.  Out: the
-// best t and its triangle.
+// 2D DDA over the terrain cells from t = 0 on; ends at the first cell that holds a crossing: the ray's first, and behind tMax a miss, so which
+// crossing is found does not depend on tMax.  useBounds: an 8 x 8-cell block whose height range (the mips' level 3) the ray's y range over
+// the block misses by more than a tolerance is crossed without testing its cells, and so is a cell whose own range (level 0) it misses; only
+// such cells are not tested, so the hit is the one the walk without them finds.  Out: t and its triangle.
 __device__ inline bool qTerrainWalk(const HeightmapParams& hm, V3 o, V3 d, float tMax, bool useBounds, float& bestT, uint32_t& bestCell, uint32_t& bestTri) {
     const uint32_t n = hm.chunksPerDim * kHmSegs;
     const float s = hm.chunkScale, x0 = hm.minX, z0 = hm.minZ, x1 = x0 + (float)hm.chunksPerDim * hm.chunkSize, z1 = z0 + (float)hm.chunksPerDim * hm.chunkSize;
@@ -330,8 +371,9 @@ __device__ inline bool qTerrainWalk(const HeightmapParams& hm, V3 o, V3 d, float
     int gx = (int)fminr(qmax(floorf((px - x0) / s), 0.f), (float)(n - 1u)), gz = (int)fminr(qmax(floorf((pz - z0) / s), 0.f), (float)(n - 1u));
     const int sx = d.x > 0.f ? 1 : -1, sz = d.z > 0.f ? 1 : -1;
     const float eps = 1e-3f / hm.invAmplitudeScale + 1e-5f * fabsf(o.y);
-    bool found = false, blockMiss = false;
+    bool blockMiss = false;
     float tCell = tIn;
+    int entry = 0;
     int blockX = -1, blockZ = -1;
     for (uint32_t it = 0; it < 2u * n + 2u; ++it) {
         const float tx = d.x == 0.f ? FLT_MAX : (x0 + (float)(gx + (sx > 0 ? 1 : 0)) * s - o.x) / d.x;
@@ -358,20 +400,18 @@ __device__ inline bool qTerrainWalk(const HeightmapParams& hm, V3 o, V3 d, float
             const float ya = o.y + ta * d.y, yb = o.y + tb * d.y;
             if (fminr(ya, yb) > hmax + eps || qmax(ya, yb) < hmin - eps) test = false;
         }
-        if (test)
-            for (uint32_t tri = 0; tri < 2u; ++tri) {
-                float t;
-                if (qRayTerrainTriangle(hm, (uint32_t)gx, (uint32_t)gz, tri, o, d, t) && t >= 0.f && t <= tMax && t < FLT_MAX && (!found || t < bestT)) {
-                    bestT = t + 0.f; bestCell = (uint32_t)gz * n + (uint32_t)gx; bestTri = tri; found = true;
-                }
-            }
-        if (found && bestT <= tExit) break;
-        if (!found && tExit > tOut) break;   // (once a hit is found, the walk ends by the rule above in both ray kernels alike)
-        if (tx < tz) { gx += sx; if (gx < 0 || gx >= (int)n) break; }
-        else { gz += sz; if (gz < 0 || gz >= (int)n) break; }
+        float t; uint32_t tri;
+        if (test && qRayTerrainCell(hm, (uint32_t)gx, (uint32_t)gz, o, d, tCell, tExit, entry, tx < tz, t, tri)) {
+            if (!(t <= tMax && t < FLT_MAX)) return false;
+            bestT = t + 0.f; bestCell = (uint32_t)gz * n + (uint32_t)gx; bestTri = tri;
+            return true;
+        }
+        if (tExit > tOut) break;
+        if (tx < tz) { gx += sx; entry = 1; if (gx < 0 || gx >= (int)n) break; }
+        else { gz += sz; entry = 2; if (gz < 0 || gz >= (int)n) break; }
         tCell = tExit;
     }
-    return found;
+    return false;
 }
 
 // ---- the one finalisation both ray kernels use: the hit record of the winner (key = t bits << 32 | collider, kRayTerrain for the terrain)
@@ -426,7 +466,7 @@ __device__ inline void qFinalise(const QueryScene& s, const QueryRay& q, unsigne
         if (col == kRayTerrain) {
             ent = kRayTerrain; obj = OBJ_STATIC;
             const uint32_t nn = s.hm.chunksPerDim * kHmSegs;
-            V3 p0, corner; qTerrainTriangle(s.hm, terrainCell % nn, terrainCell / nn, terrainTri, p0, n, corner);
+            n = qTerrainNormal(s.hm, terrainCell % nn, terrainCell / nn, terrainTri);
         } else {
             const uint32_t type = s.cTypeBody[2 * col], body = s.cTypeBody[2 * col + 1];
             ent = s.cEntity[col]; obj = qObjectType(s, col, body);

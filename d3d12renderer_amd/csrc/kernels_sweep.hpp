@@ -429,7 +429,7 @@ __global__ __launch_bounds__(64 * kOvWaves) void k_q_sweep_exhaustive(uint32_t c
 }
 
 // ---- the terrain (MI_QUERY_TERRAIN): the heightmap's collision triangles, (A, B, C) and (C, B, D) of every cell of a chunk that has heights, what the
-// ray cast hits (qTerrainTriangle); two-sided surfaces without volume.  A launch of its own behind the collider kernel, whose record it merges with:
+// ray cast hits (qTerrainCellVertices); two-sided surfaces without volume.  A launch of its own behind the collider kernel, whose record it merges with:
 // k_q_sweep stays what it is, a world without terrain pays nothing; a terrain hit does not prune the collider pass this way.
 // The rule of qTerrainIncluded (the host launches these kernels only for a world with a heightmap)
 __device__ __forceinline__ bool swTerrainIncluded(const SweepCast& c) {
@@ -440,7 +440,7 @@ __device__ __forceinline__ float swTerrainCoord(const HeightmapParams& hm, uint3
     return (float)v * hm.chunkScale + ((float)chunk * hm.chunkSize + mapMin);
 }
 __device__ __forceinline__ float swTerrainHeight(const HeightmapParams& hm, uint32_t h) { return (float)h * hm.heightScale + (0.f + hm.minY); }
-// triangle `tri` of cell (gx, gz) (of a chunk that has heights) as sweepTrianglePair's collider, loaded as qTerrainTriangle loads it
+// triangle `tri` of cell (gx, gz) (of a chunk that has heights) as sweepTrianglePair's collider, loaded as qTerrainCellVertices loads it
 __device__ __forceinline__ Shape swTerrainShape(const HeightmapParams& hm, uint32_t gx, uint32_t gz, uint32_t tri) {
     const uint32_t cx = gx >> 7, cz = gz >> 7, qx = gx & 127u, qz = gz & 127u;
     const uint16_t* heights = hm.heights + (size_t)hm.chunkSlot[cz * hm.chunksPerDim + cx] * kHmVerts * kHmVerts;

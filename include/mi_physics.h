@@ -276,7 +276,11 @@ MI_API int mi_world_test_interactions(mi_world* world, uint32_t count, const flo
  *     hulls; a capsule or cylinder whose axis lies within 1e-3 rad of -y is placed about 1e-4 rad off (rotateFromTo next to its half turn);
  *     a cylinder's side of radius r stays invisible where r^2 - (distance from the axis)^2 < 1e-6.
  *   - The terrain: the heightmap's collision triangles (two per cell, as heightmap contacts use them; not the bilinear
- *     mi_heightmap_get_height surface, which they meet at the grid vertices and edges); chunks without heights are holes.
+ *     mi_heightmap_get_height surface, which they meet at the grid vertices and edges); chunks without heights are holes.  The
+ *     surface is watertight: a ray whose segment crosses it is a hit wherever the origin lies, on a shared edge or vertex as anywhere
+ *     else (the decision is a change of sign of the ray's height above the surface between points on the cells' rims that neighbouring
+ *     cells compute alike, not an inclusion test of a rounded hit point per triangle).  It is hit from below as from above, with the
+ *     triangle's upward normal; t is the crossing of the hit triangle's plane.  Accuracy: INTEGRATION.md, section 6b.
  *   - Closest hit = smallest t; ties go to the lowest world collider index; a collider wins a tie against the terrain.  A hit
  *     with t > max_t is a miss; so is a ray with a zero or non-finite direction or origin (never an error).  Cloth is not hit.
  *   - entity_ranges2 NULL = the whole scene, otherwise ray i sees the colliders of entities [lo_i, hi_i) only (the terrain, entity
