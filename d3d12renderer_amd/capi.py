@@ -55,6 +55,11 @@ sweep_hit_dtype = np.dtype([("entity", "<u4"), ("collider", "<u4"), ("t", "<f4")
                             ("normal", "<f4", 3), ("volume", "<u4")])
 assert sweep_hit_dtype.itemsize == 48
 SWEEP_INITIAL_OVERLAP, SWEEP_UNCONVERGED = 1, 2
+# mi_distance_hit (mi_world_distance): the collider nearest to a volume with the two closest points; entity / collider MI_RAY_MISS and distance = +inf on a miss
+distance_hit_dtype = np.dtype([("entity", "<u4"), ("collider", "<u4"), ("distance", "<f4"), ("object_type", "<u4"), ("point_collider", "<f4", 3), ("flags", "<u4"),
+                               ("point_volume", "<f4", 3), ("volume", "<u4"), ("normal", "<f4", 3), ("pad", "<u4")])
+assert distance_hit_dtype.itemsize == 64
+DISTANCE_OVERLAP, DISTANCE_UNCONVERGED = 1, 2
 MI_ERR_CAPACITY = -5
 QUERY_ALL = QUERY_RIGID_BODIES | QUERY_STATIC | QUERY_TERRAIN | QUERY_TRIGGERS | QUERY_FORCE_FIELDS
 
@@ -423,6 +428,31 @@ class World:
         world's stream without a host synchronisation."""
         self.L.check(self.L.fn("world_sweep_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_void_p(displacements_ptr), C.c_uint32(include),
                                                             C.c_void_p(ranges_ptr or None), C.c_void_p(out_ptr)), "world_sweep_device_async")
+
+    # --- distance scene queries (the collider nearest to a volume, the distance and the two closest points; read-only)
+    def _distance(self, name, volumes, max_distances, include, entity_ranges):
+        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distances, np.float32), (len(v),))) if max_distances is not None else None
+        r = np.ascontiguousarray(entity_ranges, dtype=np.uint32).reshape(len(v), 2) if entity_ranges is not None else None
+        out = np.zeros(len(v), dtype=distance_hit_dtype)
+        self.L.check(self.L.fn(name)(self.h, C.c_uint32(len(v)), _ptr(v), _ptr(m), C.c_uint32(include), _ptr(r), _ptr(out)), name)
+        return out
+
+    def distance(self, volumes, max_distances=None, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_world_distance: per volume the nearest collider no farther than max_distances (None = unbounded, a scalar or one per volume) as a
+        `distance_hit_dtype` array: distance, the closest points on the collider and on the volume, the unit direction between them.  Touching
+        shapes report distance 0 with DISTANCE_OVERLAP.  The terrain is not reported."""
+        return self._distance("world_distance", volumes, max_distances, include, entity_ranges)
+
+    def debug_distance_exhaustive(self, volumes, max_distances=None, include=QUERY_DEFAULT, entity_ranges=None):
+        """mi_debug_distance_exhaustive: the same records from every collider against every volume (byte for byte what distance returns)."""
+        return self._distance("debug_distance_exhaustive", volumes, max_distances, include, entity_ranges)
+
+    def distance_device_async(self, n, volumes_ptr, out_ptr, max_distances_ptr=0, include=QUERY_DEFAULT, ranges_ptr=0):
+        """mi_world_distance_device_async: device buffers (volumes: n x 96 bytes; max distances: n float32 or 0 for unbounded; out: n x 64 bytes), enqueued
+        on the world's stream without a host synchronisation."""
+        self.L.check(self.L.fn("world_distance_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_void_p(max_distances_ptr or None), C.c_uint32(include),
+                                                               C.c_void_p(ranges_ptr or None), C.c_void_p(out_ptr)), "world_distance_device_async")
 
     # --- contact-manifold scene queries (where a shape touches the world, along which normal, how deep; read-only)
     def volume_contacts(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):

@@ -35,6 +35,7 @@
 #include "kernels_query.hpp"
 #include "kernels_overlap.hpp"
 #include "kernels_sweep.hpp"
+#include "kernels_distance.hpp"
 #include "kernels_contacts_query.hpp"
 #include "kernels_terrain_query.hpp"
 
@@ -449,9 +450,9 @@ struct mi_world {
         // Staging of the blocking variants: inputs copied in, results copied out.  Sized by the call's ray / volume count and record capacity; the blocking
         // entry points grow it.  One set serves every family: a blocking call synchronises before it returns, so two never use it at once.
         struct Blocking {
-            DBuf<float> rays; DBuf<uint32_t> hits;   // ray casts; the displacement rows of a shape cast (rays)
+            DBuf<float> rays; DBuf<uint32_t> hits;   // ray casts; the displacement rows of a shape cast and the largest distances of a distance query (rays)
             DBuf<uint32_t> ranges;                   // the optional entity ranges of any family
-            DBuf<uint32_t> volumes, offsets, totals; DBuf<uint4> records;   // volume queries: mi_overlap_hit is one row of 16 bytes, mi_terrain_contact two, mi_sweep_hit three, mi_volume_contact six
+            DBuf<uint32_t> volumes, offsets, totals; DBuf<uint4> records;   // volume queries: mi_overlap_hit is one row of 16 bytes, mi_terrain_contact two, mi_sweep_hit three, mi_distance_hit four, mi_volume_contact six
         } host;
     } query;
     int queryBuild();
@@ -464,6 +465,7 @@ struct mi_world {
     int contactsReserve(uint32_t maxCandidates);
     int contactsEnqueue(uint32_t count, uint32_t bound, uint32_t capacity, uint4* contactsDev, uint32_t* offsetsDev, uint32_t* totals2Dev, bool exhaustive);
     int sweepEnqueue(uint32_t count, const uint32_t* volumesDev, const float4* displacementsDev, uint32_t include, const uint32_t* rangesDev, uint4* outDev, bool exhaustive);
+    int distanceEnqueue(uint32_t count, const uint32_t* volumesDev, const float* maxDistancesDev, uint32_t include, const uint32_t* rangesDev, uint4* outDev, bool exhaustive);
 };
 
 int mi_world::init(int dev) {

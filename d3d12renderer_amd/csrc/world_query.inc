@@ -1,6 +1,6 @@
 // Part of world.hip (one translation unit; #included there, after world_state.inc): batched scene queries (include/mi_physics.h): ray casts
 // (mi_world_raycast*; kernels in kernels_query.hpp), volume overlaps (mi_world_overlap*; kernels in kernels_overlap.hpp), shape casts (mi_world_sweep*;
-// kernels in kernels_sweep.hpp) and the contact manifolds of
+// kernels in kernels_sweep.hpp), distance queries (mi_world_distance*; kernels in kernels_distance.hpp) and the contact manifolds of
 // query volumes (mi_world_volume_contacts*; kernels in kernels_contacts_query.hpp) and their terrain contacts (mi_world_terrain_contacts*; the step's terrain
 // kernels of heightmap.hpp under the policy of kernels_terrain_query.hpp).
 //
@@ -221,6 +221,44 @@ static int sweepHost(mi_world* w, uint32_t count, const mi_query_volume* volumes
     return MI_OK;
 }
 
+// ---- distance queries.  Volume rows (two launches), then one launch: a wave per volume writes its record; the exhaustive yardstick computes its own world rows
+// first.  maxDistancesDev: one float per volume, or null (+inf).  The terrain is not reported: the terrain bit changes nothing.
+int mi_world::distanceEnqueue(uint32_t count, const uint32_t* volumesDev, const float* maxDistancesDev, uint32_t include, const uint32_t* rangesDev, uint4* outDev, bool exhaustive) {
+    QueryCache::VolumeRows& v = query.vol; const QueryCache::Built& g = query.built;
+    if (!exhaustive) { int rc = queryBuild(); if (rc != MI_OK) return rc; }
+    Launcher& L = query.L;
+    L.begin(false, false);
+    if (exhaustive) { int rc = exhaustiveRowsEnqueue(true); if (rc != MI_OK) return rc; }
+    const OverlapScene s = overlapScene(exhaustive);
+    int rc = volumeRowsEnqueue(count, volumesDev, rangesDev); if (rc != MI_OK) return rc;
+    const dim3 grid(divUp(count, kOvWaves)), block(64 * kOvWaves);
+    if (exhaustive)
+        L.launch(k_q_distance_exhaustive, grid, block, 0, stream, count, include, s, (const float4*)v.shape.p, (const float4*)v.mn.p, (const float4*)v.mx.p, (const uint32_t*)v.range.p,
+                 (const float4*)v.cPos.p, maxDistancesDev, outDev);
+    else
+        L.launch(k_q_distance, grid, block, 0, stream, count, include, s, (const float4*)v.shape.p, (const float4*)v.mn.p, (const float4*)v.mx.p, (const uint32_t*)v.range.p,
+                 (const float4*)v.cPos.p, maxDistancesDev, (const QueryGrid*)g.grid.p, (const uint32_t*)g.start.p, (const uint32_t*)g.entries.p, (const uint32_t*)g.large.p, outDev);
+    if (L.firstError != hipSuccess) return fail(MI_ERR_DEVICE, std::string("distance query: ") + hipGetErrorString(L.firstError));
+    return MI_OK;
+}
+static_assert(sizeof(mi_distance_hit) == kDistanceRecordRows * sizeof(uint4) && sizeof(mi_distance_hit) == 64, "a distance record is four rows of 16 bytes");
+// the blocking variants: volumes, ranges and the largest distances through the blocking staging, the records read back once
+static int distanceHost(mi_world* w, uint32_t count, const mi_query_volume* volumes, const float* maxDistances, uint32_t include, const uint32_t* ranges, mi_distance_hit* out, bool exhaustive) {
+    if (!w || (count && (!volumes || !out))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = queryPrepare(w); if (rc != MI_OK) return rc;
+    if (!count) return MI_OK;
+    mi_world::QueryCache::Blocking& h = w->query.host;
+    HIP_TRY(h.rays.ensure(count)); HIP_TRY(h.records.ensure((size_t)count * kDistanceRecordRows));
+    if (maxDistances) HIP_TRY(hipMemcpyAsync(h.rays.p, maxDistances, (size_t)count * sizeof(float), hipMemcpyHostToDevice, w->stream));
+    const uint32_t *volumesDev, *rangesDev;
+    rc = stageVolumes(w, count, volumes, &volumesDev); if (rc != MI_OK) return rc;
+    rc = stageRanges(w, count, ranges, &rangesDev); if (rc != MI_OK) return rc;
+    rc = w->distanceEnqueue(count, volumesDev, maxDistances ? h.rays.p : nullptr, include, rangesDev, h.records.p, exhaustive); if (rc != MI_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, h.records.p, (size_t)count * sizeof(mi_distance_hit), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));   // (the inputs were pageable host memory as well)
+    return MI_OK;
+}
+
 // ---- contact manifolds of query volumes.  Candidates by the overlap passes in boxes-only mode, then narrow phase, GJK queue, scan and write: no read-back
 // between them.  `bound` = the candidates evaluated, at most what contactsReserve() sized the staging for.
 int mi_world::contactsReserve(uint32_t maxCandidates) {
@@ -396,6 +434,20 @@ MI_API int mi_world_sweep_device_async(mi_world* w, uint32_t count, const mi_que
     int rc = queryPrepare(w); if (rc != MI_OK) return rc;
     if (!count) return MI_OK;
     return w->sweepEnqueue(count, reinterpret_cast<const uint32_t*>(volumesDev), reinterpret_cast<const float4*>(displacements4Dev), include, ranges2Dev, reinterpret_cast<uint4*>(outDev), false);
+}
+
+MI_API int mi_world_distance(mi_world* w, uint32_t count, const mi_query_volume* volumes, const float* maxDistances, uint32_t include, const uint32_t* ranges2, mi_distance_hit* out) {
+    return distanceHost(w, count, volumes, maxDistances, include, ranges2, out, false);
+}
+MI_API int mi_debug_distance_exhaustive(mi_world* w, uint32_t count, const mi_query_volume* volumes, const float* maxDistances, uint32_t include, const uint32_t* ranges2, mi_distance_hit* out) {
+    return distanceHost(w, count, volumes, maxDistances, include, ranges2, out, true);
+}
+MI_API int mi_world_distance_device_async(mi_world* w, uint32_t count, const mi_query_volume* volumesDev, const float* maxDistancesDev, uint32_t include, const uint32_t* ranges2Dev,
+                                          mi_distance_hit* outDev) {
+    if (!w || (count && (!volumesDev || !outDev))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = queryPrepare(w); if (rc != MI_OK) return rc;
+    if (!count) return MI_OK;
+    return w->distanceEnqueue(count, reinterpret_cast<const uint32_t*>(volumesDev), maxDistancesDev, include, ranges2Dev, reinterpret_cast<uint4*>(outDev), false);
 }
 
 MI_API int mi_world_volume_contacts(mi_world* w, uint32_t count, const mi_query_volume* volumes, uint32_t include, const uint32_t* ranges2, uint32_t* outOffsets,

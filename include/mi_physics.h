@@ -446,6 +446,57 @@ MI_API int mi_debug_sweep_exhaustive(mi_world* world, uint32_t count, const mi_q
                                      uint32_t include, const uint32_t* entity_ranges2, mi_sweep_hit* out);
 
 /*
+ * Batched distance queries: how far is a shape from the nearest collider, and which two points realise that distance (what PhysX calls
+ * computeDistance and Bullet closest points: proximity sensors, clearance checks, placement, steering, observations).  The volumes, their
+ * validation (an invalid one is a miss, never an error), their pose handling, the include flags, entity_ranges2, the pose read
+ * (physics_transform1, pending edits included) and the pose epoch are those of mi_world_sweep; the queries share the grid of the other
+ * queries and change nothing a step computes.  A sharded world returns MI_ERR_UNSUPPORTED.
+ *   - Reported for volume v: the admitted collider (object type selected by include, entity in [lo_v, hi_v), a finite world AABB) with the
+ *     smallest distance, if that distance is <= max_distance_v; ties go to the lowest world collider index.  max_distances NULL = +inf for
+ *     every volume; +inf is allowed; a negative or NaN max_distance is a miss.  A world without colliders reports misses.
+ *   - distance is the distance between the two float32 world shapes; point_collider lies on the collider's surface, point_volume on the
+ *     volume's; normal = normalize(point_volume - point_collider), unit, from the collider towards the volume.  Spheres and capsules are a
+ *     point or segment core plus a radius, as in the casts, so their figures are exact up to rounding.  Where the closest points are not
+ *     unique (parallel faces, edges, a cap flat on a face) any pair that realises the distance may be reported.
+ *   - Shapes that touch or overlap: distance = 0, MI_DISTANCE_OVERLAP is set, both points are the volume's pose position and normal is 0.
+ *     For penetration data call mi_world_volume_contacts.  Among several overlapping colliders the lowest index wins (the tie rule).  The
+ *     decision is the shape cast's for an initial overlap: no support plane separates the shapes by more than the search's tolerance.
+ *   - Termination: the pair test (GJK on the cores' Minkowski difference) runs at most 64 iterations and stops by a tolerance relative to the
+ *     coordinates (2e-6 x the largest coordinate, no absolute threshold).  Its running distance is an upper bound of the true one, so a
+ *     pair that reaches the limit, or whose search stalls more than 16 tolerances from its lower bound, reports its current distance with
+ *     MI_DISTANCE_UNCONVERGED: too far, never too near.
+ *   - The reported distance is never below the gap of the two world AABBs (the bound candidates are skipped by): it is the pair test's
+ *     distance raised to that gap, which differs from it by roundings only.
+ *   - Accuracy (float32, measured against a float64 reference): see INTEGRATION.md, section 6g.
+ *   - Not reported: the terrain (MI_QUERY_TERRAIN is accepted and ignored, as by mi_world_overlap) and cloth.  Also out of scope: k-nearest
+ *     and all-within variants.
+ *   - Result: one record per volume, out[count].
+ */
+typedef struct mi_distance_hit {   /* 64 bytes, four 16-byte rows: usable from the host and as a device buffer */
+    uint32_t entity, collider;     /* MI_RAY_MISS when nothing lies within max_distance; collider = world collider index */
+    float distance;                /* >= 0; +inf on a miss */
+    uint32_t object_type;          /* mi_object_type of the collider; 0 on a miss */
+    float point_collider[3];       /* world space, on the collider's surface (0 on a miss) */
+    uint32_t flags;                /* MI_DISTANCE_* */
+    float point_volume[3];         /* world space, on the volume's surface (0 on a miss) */
+    uint32_t volume;               /* index of the query */
+    float normal[3];               /* world space, unit, from the collider towards the volume (0 on a miss or an overlap) */
+    uint32_t pad;
+} mi_distance_hit;
+enum { MI_DISTANCE_OVERLAP = 1, MI_DISTANCE_UNCONVERGED = 2 };
+/* max_distances: one float per volume, or NULL (+inf). */
+MI_API int mi_world_distance(mi_world* world, uint32_t count, const mi_query_volume* volumes, const float* max_distances,
+                             uint32_t include, const uint32_t* entity_ranges2, mi_distance_hit* out);
+/* Device buffers (16-byte aligned records and volumes), only enqueued on the world's stream: no reservation and no host synchronisation.
+ * max_distances_dev (one float per volume) and ranges2_dev may be NULL. */
+MI_API int mi_world_distance_device_async(mi_world* world, uint32_t count, const mi_query_volume* volumes_dev, const float* max_distances_dev,
+                                          uint32_t include, const uint32_t* ranges2_dev, mi_distance_hit* out_dev);
+/* The same result from every collider tested against every volume, without the grid, without skipping by the best distance so far and from
+ * collider rows computed for the call (the yardstick of the accelerated path): byte for byte equal. */
+MI_API int mi_debug_distance_exhaustive(mi_world* world, uint32_t count, const mi_query_volume* volumes, const float* max_distances,
+                                        uint32_t include, const uint32_t* entity_ranges2, mi_distance_hit* out);
+
+/*
  * Batched contact-manifold queries: where a shape touches the world, along which normal and how deep (what PhysX calls
  * computePenetration and Bullet contactTest).  The volumes, their validation (an invalid one yields an empty segment), the include
  * flags, entity_ranges2, the pose read (physics_transform1, pending edits included), the CSR result in ascending world collider index

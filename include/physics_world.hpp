@@ -11,6 +11,7 @@
 #include <functional>
 #include <array>
 #include <cmath>
+#include <limits>
 #include "mi_physics.h"
 #include "mi_constraints.h"
 #include "mi_shard.h"
@@ -175,6 +176,25 @@ public:
         mi_query_volume v{}; v.type = MI_COLLIDER_CAPSULE; v.rotation[3] = 1.f;
         v.shape[0] = a.x; v.shape[1] = a.y; v.shape[2] = a.z; v.shape[3] = b.x; v.shape[4] = b.y; v.shape[5] = b.z; v.shape[6] = radius;
         return sweep(std::vector<mi_query_volume>{v}, std::vector<vec3>{displacement}, include)[0];
+    }
+    // The collider nearest to each volume (mi_world_distance): one record per volume with the distance, the closest points on the collider and on the volume and
+    // the unit direction from the collider towards the volume; entity MI_RAY_MISS when nothing lies within the volume's maximum distance; touching shapes report
+    // distance 0 with MI_DISTANCE_OVERLAP; the terrain is not reported; read-only.  maxDistances: empty = unbounded, otherwise one per volume.
+    // entityRanges: empty = the whole scene, otherwise one [lo, hi) pair of entity ids per volume.  distanceToSphere: one query of the whole scene.
+    std::vector<mi_distance_hit> distance(const std::vector<mi_query_volume>& volumes, const std::vector<float>& maxDistances = {}, uint32_t include = MI_QUERY_DEFAULT,
+                                          const std::vector<uint32_t>& entityRanges = {}) {
+        if (!maxDistances.empty() && maxDistances.size() != volumes.size()) throw std::invalid_argument("distance: one maximum distance per volume");
+        if (!entityRanges.empty() && entityRanges.size() != 2 * volumes.size()) throw std::invalid_argument("distance: entityRanges holds one [lo, hi) pair per volume");
+        std::vector<mi_distance_hit> out(volumes.size());
+        if (!volumes.empty())
+            check(mi_world_distance(w_, (uint32_t)volumes.size(), volumes.data(), maxDistances.empty() ? nullptr : maxDistances.data(), include,
+                                    entityRanges.empty() ? nullptr : entityRanges.data(), out.data()), "mi_world_distance");
+        return out;
+    }
+    mi_distance_hit distanceToSphere(vec3 center, float radius, float maxDistance = std::numeric_limits<float>::infinity(), uint32_t include = MI_QUERY_DEFAULT) {
+        mi_query_volume v{}; v.type = MI_COLLIDER_SPHERE; v.rotation[3] = 1.f;
+        v.shape[0] = center.x; v.shape[1] = center.y; v.shape[2] = center.z; v.shape[3] = radius;
+        return distance(std::vector<mi_query_volume>{v}, std::vector<float>{maxDistance}, include)[0];
     }
     // Where each volume touches the world (mi_world_volume_contacts): CSR offsets [volumes + 1] and one manifold per (volume, collider) in ascending
     // collider index; normal from A to B, bit 8 of count_flags set when the volume was B (include/mi_physics.h); read-only.
