@@ -411,6 +411,10 @@ MI_API int mi_debug_overlap_exhaustive(mi_world* world, uint32_t count, const mi
  *     dot(normal, displacement) <= 0: a volume that comes from below gets a normal that points down.  Spheres and capsules keep their
  *     point / segment-plus-radius treatment; on flat ground the normal of a round volume of radius r is within 2 sqrt(tolerance / r) of
  *     the surface's (the distance tolerance above; the touch may be found on a neighbouring triangle that far beside the foot point).
+ *     A volume without a radius (a box, a hull, a cylinder's flat end, a sphere of radius 0) that meets an edge or a vertex of the terrain
+ *     reports the last clip plane's normal: a separating direction of the volume and the triangle hit (moving the volume along it leaves
+ *     the terrain), not the normal of a neighbouring face; for a sphere of radius 0 it lies between the reversed direction of travel and
+ *     the faces' normals (measured: up to 25 degrees off them), where mi_world_raycast reports the face's normal.
  *     A collider wins a tie in t against the terrain, as in the ray cast; among triangles the lowest (gz * n + gx) * 2 + tri wins
  *     (n = chunks per dimension x 128), so both kernels give the same point and normal.  Initial overlap (the volume touches a triangle at
  *     its pose) is reported as for colliders.  A volume wholly below the surface touches no triangle: it is cast from where it is and

@@ -46,32 +46,129 @@ def rolling_map():
     return scenes.rolling_heightmap(2, 32.0, 6.0, holes=((1, 0),))
 
 
+WIDE_CELL = 8.0 / 128.0
+WIDE_FLOOR, WIDE_NEAR, WIDE_FAR = 1000, 30000, 60000   # height counts of amplitude 24: the floor, the lower bump at the near end, the higher at the far end
+WIDE_BUMPS = ((16, WIDE_NEAR), (622, WIDE_FAR))         # (first vertex of the 3 x 3 raised vertices along the long axis, counts)
+
+
+def wide_map():
+    """5 x 5 chunks of 8 m (cells of 1 / 16 m, 640 a side; x and z in [-20, 20]) of which only the middle row (z in [-4, 4]) and the middle
+    column (x in [-4, 4]) have heights: the constant WIDE_FLOOR but for two bumps of 3 x 3 vertices each, on the row's centre line at cells 16 and
+    622 along x and on the column's at the same cells along z.  A volume more than 512 cells long lying along the row or the column and coming
+    down onto the bump at the far end puts its only touch behind the first 64 blocks of its footprint."""
+    chunks = {(x, z): np.full((129, 129), WIDE_FLOOR, np.uint16) for x in range(5) for z in range(5) if x == 2 or z == 2}
+    for at, counts in WIDE_BUMPS:
+        for along_x in (True, False):
+            for k in range(at, at + 3):
+                for j in range(319, 322):
+                    gx, gz = (k, j) if along_x else (j, k)
+                    for (cx, cz), h in chunks.items():    # (a vertex on a chunk's edge row belongs to both chunks)
+                        if 0 <= gx - 128 * cx <= 128 and 0 <= gz - 128 * cz <= 128:
+                            h[gz - 128 * cz, gx - 128 * cx] = counts
+    return dict(chunks_per_dim=5, chunk_size=8.0, restitution=0.05, friction=0.8, min_corner=np.array([-20.0, 0.0, -20.0], np.float32), amplitude=24.0,
+                chunks=chunks)
+
+
 MAPS = {"flat": flat_map, "tilted": tilted_map, "rolling": rolling_map}
 _TRIANGLES = {}
+
+
+def map_of(name):
+    """The heightmap of a map of MAPS, of raycast_terrain_matrix.MAPS (offset, floor) or the wide map."""
+    if name in MAPS:
+        return MAPS[name]()
+    if name == "wide":
+        return wide_map()
+    import raycast_terrain_matrix
+    return raycast_terrain_matrix.MAPS[name]()
 
 
 def triangles(name):
     """(vertices [M, 3, 3], lower bounds [M, 3], upper bounds [M, 3]) of a map of MAPS, computed once per process."""
     if name not in _TRIANGLES:
-        a, b, c = raycast_ref.terrain_triangles(MAPS[name]())
+        a, b, c = raycast_ref.terrain_triangles(map_of(name))
         v = np.stack([a, b, c], axis=1)
         v.setflags(write=False)
         _TRIANGLES[name] = (v, v.min(axis=1), v.max(axis=1))
     return _TRIANGLES[name]
 
 
-def culled(name, vol, d, grow=1e-6):
-    """The triangles whose AABB meets the swept bounds of `vol` moved along d (grown by `grow`), as sweep_ref shapes."""
+def _culled(name, vol, d, grow=1e-6):
+    """(indices, entry times) of the triangles whose AABB meets the swept bounds of `vol` moved along d (grown by `grow`) and, of those, the ones
+    whose AABB grown by the volume's half-extents the displacement from the volume's centre passes through (sweep_ref.slab_entry on all of them at
+    once, `grow` wider: a cast from 1e4 away keeps the triangles along its way, not every one under its swept bounds)."""
     v, lo, hi = triangles(name)
-    mn, mx = S.bounds(("swept", vol, np.asarray(d, np.float64)))
+    mn, mx = S.bounds(("swept", vol, d))
     keep = np.flatnonzero(((hi >= mn - grow) & (lo <= mx + grow)).all(axis=1))
-    return [("pts", v[k], 0.0) for k in keep]
+    vmn, vmx = S.bounds(vol)
+    origin, half = (vmn + vmx) / 2, (vmx - vmn) / 2 + grow
+    a, b = lo[keep] - half - origin, hi[keep] + half - origin
+    t0, t1, ok = np.zeros(len(keep)), np.ones(len(keep)), np.ones(len(keep), bool)
+    for i in range(3):
+        if d[i] == 0:
+            ok &= (a[:, i] <= 0) & (b[:, i] >= 0)
+        else:
+            ta, tb = a[:, i] / d[i], b[:, i] / d[i]
+            t0, t1 = np.maximum(t0, np.minimum(ta, tb)), np.minimum(t1, np.maximum(ta, tb))
+    # (the slab's own rounding: a time is off by a few ulps of its size, which `slack` covers)
+    slack = 1e-12 * (1.0 + np.maximum(np.abs(t0), np.abs(t1)))
+    ok &= t0 <= t1 + slack
+    return keep[ok], t0[ok]
+
+
+def culled(name, vol, d, grow=1e-6):
+    """The triangles of _culled as sweep_ref shapes."""
+    v = triangles(name)[0]
+    return [("pts", v[k], 0.0) for k in _culled(name, vol, np.asarray(d, np.float64), grow)[0]]
+
+
+def _directions(count=96):
+    """Unit vectors spread over the sphere (a Fibonacci lattice) and the six axes."""
+    k = np.arange(count) + 0.5
+    y, phi = 1.0 - 2.0 * k / count, np.pi * (1.0 + 5.0 ** 0.5) * k
+    r = np.sqrt(1.0 - y * y)
+    return np.concatenate([np.stack([r * np.cos(phi), y, r * np.sin(phi)], axis=1), np.eye(3), -np.eye(3)])
+
+
+_DIRECTIONS = _directions()
 
 
 def cast(name, vol, d):
-    """The first touch of `vol` moved along d with the terrain of map `name`: (t, unit normal from the terrain to the volume, point, initial overlap) or None."""
-    hit = S.cast(vol, d, culled(name, vol, d))
-    return None if hit is None else hit[1:]
+    """The first touch of `vol` moved along d with the terrain of map `name`: (t, unit normal from the terrain to the volume, point, initial overlap)
+    or None.  The smallest sweep_ref.time_of_impact over the culled triangles, taken in the order of a lower bound of each one's time and ended
+    once that bound lies behind the best time found.  The bound: along a unit direction a the volume and the triangle are g_a apart at the start
+    (the volume's lowest projection less the triangle's highest) and close at the rate -a . d, so they cannot touch before g_a / -(a . d), and never
+    when they are apart and do not close; the largest of that over _DIRECTIONS, -d, the normals of the touches found so far and the slab's entry
+    time (the box of a wide round or tilted volume reaches a thousand triangles long before the volume does)."""
+    d = np.asarray(d, np.float64)
+    keep, lb = _culled(name, vol, d)
+    if not len(keep):
+        return None
+    v = triangles(name)[0][keep]
+    if len(keep) <= 300:     # few candidates: sweep_ref.cast's own order (by the slab's entry time)
+        hit = S.cast(vol, d, [("pts", t, 0.0) for t in v])
+        return None if hit is None else hit[1:]
+    length = np.linalg.norm(d)
+
+    def bounded(lb, a):
+        gap = -(S.support(vol, -a) @ -a + S.margin(vol)) - (v @ a).max(axis=1)
+        rate = -(a @ d)
+        return np.maximum(lb, (gap - 1e-9) / rate) if rate > 0 else np.where(gap > 1e-9, np.inf, lb)
+    for a in (_DIRECTIONS if length == 0 else np.concatenate([_DIRECTIONS, [-d / length]])):
+        lb = bounded(lb, a)
+    best = None
+    left = np.ones(len(keep), bool)
+    while left.any():
+        k = int(np.argmin(np.where(left, lb, np.inf)))
+        if lb[k] > 1.0 or (best is not None and lb[k] > best[0]):
+            break
+        left[k] = False
+        hit = S.time_of_impact(vol, ("pts", v[k], 0.0), d)
+        if hit is not None and (best is None or hit[0] < best[0]):
+            best = hit
+            if not hit[3] and np.any(hit[1] != 0):
+                lb = bounded(lb, hit[1])      # (the touch's own normal: a slab's face, which no direction of the fixed set equals)
+    return best
 
 
 def min_gap(name, shape, reach, axis=None):
@@ -84,6 +181,10 @@ def min_gap(name, shape, reach, axis=None):
     if axis is not None:
         axis = np.asarray(axis, np.float64)
         lb = np.maximum(lb, S.support(shape, -axis) @ axis - S.margin(shape) - (v @ axis).max(axis=1))
+    near = np.flatnonzero(lb <= reach)
+    if len(near) > 500:     # (a wide round volume: its box is near a thousand triangles that its flank is far from; the same bound along _DIRECTIONS)
+        for a in _DIRECTIONS:
+            lb[near] = np.maximum(lb[near], S.support(shape, -a) @ a - S.margin(shape) - (v[near] @ a).max(axis=1))
     best = np.inf
     for k in np.argsort(lb, kind="stable"):
         if lb[k] > reach or lb[k] >= best:
@@ -105,7 +206,7 @@ def scale_of(vol, d):
 def scene(name):
     """A world of the map alone, with the hull geometry the hull volumes use."""
     return scenes.Scene("sweep_terrain_" + name, scenes.make_entities(0), np.zeros(0, np.uint32), scenes.make_colliders(0, capi.SPHERE), 10,
-                        hulls=[R.volume_hull()], heightmap=MAPS[name]())
+                        hulls=[R.volume_hull()], heightmap=map_of(name))
 
 
 def comparison_casts(seed=SEED):
