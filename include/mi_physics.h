@@ -230,6 +230,11 @@ MI_API int mi_entity_set_force(mi_world* world, uint32_t entity, const float* fo
  * Sphere, capsule, AABB and OBB colliders of rigid bodies collide with the terrain triangles (one contact per touched
  * triangle plus the lowest-point contact, at most 255 per collider); cylinders and hulls do not (the reference reads an
  * uninitialised point for them).  mi_contact::collider_b of a terrain contact is 0xFFFFFFFF and its body_b is the static dummy.
+ * A stated deviation: the terrain stays at rest.  In the reference every terrain contact solves against one shared static body, and
+ * an impulse that is not finite (a rigid body without mass: a sphere of radius 0, a box with a zero extent; its pose is NaN after its
+ * first step wherever it is) enters that body's velocity as NaN x 0, so every body that touches the terrain in that step leaves it
+ * with a NaN pose.  Here the static body's velocity is the constant 0: the NaN stays with the massless body and with what it touches
+ * through collider contacts.  With finite numbers the two are the same bits.
  */
 MI_API int mi_heightmap_create(mi_world* world, uint32_t chunks_per_dim, float chunk_size, float restitution, float friction);
 MI_API int mi_heightmap_set_chunk_heights(mi_world* world, uint32_t chunk_x, uint32_t chunk_z, const uint16_t* heights129x129);
