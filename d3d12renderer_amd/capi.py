@@ -454,6 +454,42 @@ class World:
         self.L.check(self.L.fn("world_distance_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_void_p(max_distances_ptr or None), C.c_uint32(include),
                                                                C.c_void_p(ranges_ptr or None), C.c_void_p(out_ptr)), "world_distance_device_async")
 
+    # --- terrain distance scene queries (the heightmap triangle nearest to a volume: ground clearance; read-only)
+    def _terrain_distance(self, name, volumes, max_distances, merge_into):
+        v = np.ascontiguousarray(volumes, dtype=query_volume_dtype).reshape(-1)
+        m = None
+        if max_distances is not None:
+            m = np.asarray(max_distances, np.float32)
+            if m.ndim > 1 or (m.ndim == 1 and len(m) != len(v)):
+                raise ValueError(f"{name}: max_distances is a scalar or one value per volume ({len(v)}), got shape {m.shape}")
+            m = np.ascontiguousarray(np.broadcast_to(m, (len(v),)))
+        if merge_into is None:
+            out = np.zeros(len(v), dtype=distance_hit_dtype)
+        else:
+            have = np.asarray(merge_into)
+            if have.dtype != distance_hit_dtype or have.shape != (len(v),):
+                raise ValueError(f"{name}: merge_into holds one distance_hit_dtype record per volume ({len(v)}), got {have.dtype} of shape {have.shape}")
+            out = np.ascontiguousarray(have).copy()
+        self.L.check(self.L.fn(name)(self.h, C.c_uint32(len(v)), _ptr(v), _ptr(m), C.c_uint32(0 if merge_into is None else 1), _ptr(out)), name)
+        return out
+
+    def terrain_distance(self, volumes, max_distances=None, merge_into=None):
+        """mi_world_terrain_distance: per volume the nearest collision triangle of the heightmap no farther than max_distances (None = unbounded, a
+        scalar or one per volume) as a `distance_hit_dtype` array with entity = collider = RAY_TERRAIN: ground clearance, the closest points on the
+        terrain and on the volume, the unit direction between them.  merge_into: the records of `distance` for the same volumes; the result is a copy
+        in which the terrain has replaced the misses and the records it is strictly nearer than."""
+        return self._terrain_distance("world_terrain_distance", volumes, max_distances, merge_into)
+
+    def debug_terrain_distance_exhaustive(self, volumes, max_distances=None, merge_into=None):
+        """mi_debug_terrain_distance_exhaustive: the same records from every triangle against every volume (byte for byte what terrain_distance returns)."""
+        return self._terrain_distance("debug_terrain_distance_exhaustive", volumes, max_distances, merge_into)
+
+    def terrain_distance_device_async(self, n, volumes_ptr, out_ptr, max_distances_ptr=0, merge=0):
+        """mi_world_terrain_distance_device_async: device buffers (volumes: n x 96 bytes; max distances: n float32 or 0 for unbounded; out: n x 64 bytes,
+        read as well when merge is set: the records distance_device_async left there), enqueued on the world's stream without a host synchronisation."""
+        self.L.check(self.L.fn("world_terrain_distance_device_async")(self.h, C.c_uint32(n), C.c_void_p(volumes_ptr), C.c_void_p(max_distances_ptr or None), C.c_uint32(merge),
+                                                                       C.c_void_p(out_ptr)), "world_terrain_distance_device_async")
+
     # --- contact-manifold scene queries (where a shape touches the world, along which normal, how deep; read-only)
     def volume_contacts(self, volumes, include=QUERY_DEFAULT, entity_ranges=None):
         """mi_world_volume_contacts: (offsets[count + 1], records) in CSR form, `volume_contact_dtype` records in ascending world collider index per

@@ -51,12 +51,17 @@ __device__ inline Shape dsClipBox(const Shape& b, V3 mn, V3 mx) {
 // far, never too near).  The shapes count as touching (kDistanceOverlap, distance 0; points and normal
 // are the caller's) unless some support plane separated them by more than the margins, the sweep's rule for an initial overlap, or when the
 // origin lies inside the simplex.  pointCollider / pointVolume: on the surfaces, the witnesses moved by the margins along normal = v / |v|.
-// The result depends on (A, B) alone; one body (not inlined) serves the candidate test and the record writer of both kernels.
-__device__ __noinline__ DistanceResult distancePair(const Shape& A, V3 volumeMin, V3 volumeMax, const Shape& collider, const HullSet& hs) {
+// The result depends on (A, B) alone; one body (distancePair below, not inlined) serves the candidate test and the record writer of both kernels.
+// kTriangle: the collider is a terrain triangle (swTerrainShape; no margin, nothing to clip), its support swTriangleSupport — an instance of its own, as
+// sweepPairBody has one, so that the world's pair test is compiled without the triangle case (kSwTriangle, kernels_sweep.hpp).
+template <bool kTriangle> __device__ __forceinline__ Shape dsColliderShape(const Shape& collider, V3 volumeMin, V3 volumeMax) {
+    if constexpr (kTriangle) return collider; else return dsClipBox(collider, volumeMin, volumeMax);
+}
+template <bool kTriangle> __device__ __forceinline__ DistanceResult distancePairBody(const Shape& A, V3 volumeMin, V3 volumeMax, const Shape& collider, const HullSet& hs) {
     DistanceResult r; r.distance = 0.f; r.flags = kDistanceOverlap;
-    const Shape B = dsClipBox(collider, volumeMin, volumeMax);
-    const float mA = swMargin(A), mB = swMargin(B), R = mA + mB;
-    V3 witness = swSupport(B, hs, V3());   // on B's core; the one on A's is witness + v, or witnessA where A's simplex points lie closer together
+    const Shape B = dsColliderShape<kTriangle>(collider, volumeMin, volumeMax);
+    const float mA = swMargin(A), mB = swMargin(B), R = mA + mB;   // (a triangle's type has no margin)
+    V3 witness = swColliderSupport<kTriangle>(B, hs, V3());   // on B's core; the one on A's is witness + v, or witnessA where A's simplex points lie closer together
     SwSimplex s; s.n = 0u;
     {
         const V3 pa = swSupport(A, hs, V3());
@@ -69,7 +74,7 @@ __device__ __noinline__ DistanceResult distancePair(const Shape& A, V3 volumeMin
     float lv = len(v);
     for (uint32_t it = 0; it < kDistanceMaxIter; ++it) {
         if (!(lv > 0.f)) return r;   // the cores meet
-        const V3 pb = swSupport(B, hs, v), pa = swSupport(A, hs, V3() - v), p = pb - pa;
+        const V3 pb = swColliderSupport<kTriangle>(B, hs, v), pa = swSupport(A, hs, V3() - v), p = pb - pa;
         scale = qmax(scale, qmax(swMaxAbs(pa), swMaxAbs(pb)));
         const float tol = kSweepTolRel * qmax(scale, R);
         const float lower = -dot(v, p) / lv - R, slack = (lv - R) - lower;
@@ -118,6 +123,14 @@ __device__ __noinline__ DistanceResult distancePair(const Shape& A, V3 volumeMin
     r.pointCollider = witness + r.normal * mB;
     r.pointVolume = (witness + v) - r.normal * mA;
     return r;
+}
+__device__ __noinline__ DistanceResult distancePair(const Shape& A, V3 volumeMin, V3 volumeMax, const Shape& collider, const HullSet& hs) {
+    return distancePairBody<false>(A, volumeMin, volumeMax, collider, hs);
+}
+// ... against a terrain triangle (swTerrainShape): one body (not inlined) for the candidate test and the record writer of both terrain kernels
+// (kernels_terrain_distance.hpp)
+__device__ __noinline__ DistanceResult distanceTrianglePair(const Shape& A, const Shape& triangle, const HullSet& hs) {
+    return distancePairBody<true>(A, V3(), V3(), triangle, hs);
 }
 
 // ---- kernels

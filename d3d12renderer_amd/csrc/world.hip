@@ -36,6 +36,7 @@
 #include "kernels_overlap.hpp"
 #include "kernels_sweep.hpp"
 #include "kernels_distance.hpp"
+#include "kernels_terrain_distance.hpp"
 #include "kernels_contacts_query.hpp"
 #include "kernels_terrain_query.hpp"
 
@@ -466,6 +467,7 @@ struct mi_world {
     int contactsEnqueue(uint32_t count, uint32_t bound, uint32_t capacity, uint4* contactsDev, uint32_t* offsetsDev, uint32_t* totals2Dev, bool exhaustive);
     int sweepEnqueue(uint32_t count, const uint32_t* volumesDev, const float4* displacementsDev, uint32_t include, const uint32_t* rangesDev, uint4* outDev, bool exhaustive);
     int distanceEnqueue(uint32_t count, const uint32_t* volumesDev, const float* maxDistancesDev, uint32_t include, const uint32_t* rangesDev, uint4* outDev, bool exhaustive);
+    int terrainDistanceEnqueue(uint32_t count, const uint32_t* volumesDev, const float* maxDistancesDev, uint32_t merge, uint4* outDev, bool exhaustive);
 };
 
 int mi_world::init(int dev) {

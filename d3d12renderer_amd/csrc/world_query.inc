@@ -259,6 +259,44 @@ static int distanceHost(mi_world* w, uint32_t count, const mi_query_volume* volu
     return MI_OK;
 }
 
+// ---- terrain distance queries (kernels_terrain_distance.hpp).  Volume rows (two launches), then one launch: a wave per volume writes its record, or merges it
+// into the record a distanceEnqueue left in outDev (merge != 0).  The kernels read the heightmap buffers themselves (no cache of their own), as the terrain casts
+// do.  A world without a heightmap: misses (k_q_terrain_distance_none), or nothing when merging.
+int mi_world::terrainDistanceEnqueue(uint32_t count, const uint32_t* volumesDev, const float* maxDistancesDev, uint32_t merge, uint4* outDev, bool exhaustive) {
+    QueryCache::VolumeRows& v = query.vol;
+    if (heightmap && hmParams.chunksPerDim > 256u) return fail(MI_ERR_UNSUPPORTED, "terrain distance query: a heightmap of more than 256 chunks per dimension (the triangle index has 32 bits)");
+    if (!heightmap && merge) return MI_OK;
+    Launcher& L = query.L;
+    L.begin(false, false);
+    if (!heightmap) {
+        L.launch(k_q_terrain_distance_none, dim3(divUp(count, 256)), dim3(256), 0, stream, count, outDev);
+    } else {
+        int rc = volumeRowsEnqueue(count, volumesDev, nullptr); if (rc != MI_OK) return rc;
+        const HullSet hs{hullVerts.p, hullRanges.p};
+        const dim3 grid(divUp(count, kOvWaves)), block(64 * kOvWaves);
+        L.launch(exhaustive ? k_q_terrain_distance_exhaustive : k_q_terrain_distance, grid, block, 0, stream, count, merge, hmParams, hs, (const float4*)v.shape.p, (const float4*)v.mn.p,
+                 (const float4*)v.mx.p, (const uint32_t*)v.range.p, (const float4*)v.cPos.p, maxDistancesDev, outDev);
+    }
+    if (L.firstError != hipSuccess) return fail(MI_ERR_DEVICE, std::string("terrain distance query: ") + hipGetErrorString(L.firstError));
+    return MI_OK;
+}
+// the blocking variants: volumes and the largest distances through the blocking staging; with merge the caller's records go up first; the records read back once
+static int terrainDistanceHost(mi_world* w, uint32_t count, const mi_query_volume* volumes, const float* maxDistances, uint32_t merge, mi_distance_hit* out, bool exhaustive) {
+    if (!w || (count && (!volumes || !out))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = queryPrepare(w); if (rc != MI_OK) return rc;
+    if (!count) return MI_OK;
+    mi_world::QueryCache::Blocking& h = w->query.host;
+    HIP_TRY(h.rays.ensure(count)); HIP_TRY(h.records.ensure((size_t)count * kDistanceRecordRows));
+    if (maxDistances) HIP_TRY(hipMemcpyAsync(h.rays.p, maxDistances, (size_t)count * sizeof(float), hipMemcpyHostToDevice, w->stream));
+    if (merge) HIP_TRY(hipMemcpyAsync(h.records.p, out, (size_t)count * sizeof(mi_distance_hit), hipMemcpyHostToDevice, w->stream));
+    const uint32_t* volumesDev;
+    rc = stageVolumes(w, count, volumes, &volumesDev); if (rc != MI_OK) return rc;
+    rc = w->terrainDistanceEnqueue(count, volumesDev, maxDistances ? h.rays.p : nullptr, merge, h.records.p, exhaustive); if (rc != MI_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, h.records.p, (size_t)count * sizeof(mi_distance_hit), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));   // (the inputs were pageable host memory as well)
+    return MI_OK;
+}
+
 // ---- contact manifolds of query volumes.  Candidates by the overlap passes in boxes-only mode, then narrow phase, GJK queue, scan and write: no read-back
 // between them.  `bound` = the candidates evaluated, at most what contactsReserve() sized the staging for.
 int mi_world::contactsReserve(uint32_t maxCandidates) {
@@ -448,6 +486,19 @@ MI_API int mi_world_distance_device_async(mi_world* w, uint32_t count, const mi_
     int rc = queryPrepare(w); if (rc != MI_OK) return rc;
     if (!count) return MI_OK;
     return w->distanceEnqueue(count, reinterpret_cast<const uint32_t*>(volumesDev), maxDistancesDev, include, ranges2Dev, reinterpret_cast<uint4*>(outDev), false);
+}
+
+MI_API int mi_world_terrain_distance(mi_world* w, uint32_t count, const mi_query_volume* volumes, const float* maxDistances, uint32_t merge, mi_distance_hit* out) {
+    return terrainDistanceHost(w, count, volumes, maxDistances, merge, out, false);
+}
+MI_API int mi_debug_terrain_distance_exhaustive(mi_world* w, uint32_t count, const mi_query_volume* volumes, const float* maxDistances, uint32_t merge, mi_distance_hit* out) {
+    return terrainDistanceHost(w, count, volumes, maxDistances, merge, out, true);
+}
+MI_API int mi_world_terrain_distance_device_async(mi_world* w, uint32_t count, const mi_query_volume* volumesDev, const float* maxDistancesDev, uint32_t merge, mi_distance_hit* outDev) {
+    if (!w || (count && (!volumesDev || !outDev))) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = queryPrepare(w); if (rc != MI_OK) return rc;
+    if (!count) return MI_OK;
+    return w->terrainDistanceEnqueue(count, reinterpret_cast<const uint32_t*>(volumesDev), maxDistancesDev, merge, reinterpret_cast<uint4*>(outDev), false);
 }
 
 MI_API int mi_world_volume_contacts(mi_world* w, uint32_t count, const mi_query_volume* volumes, uint32_t include, const uint32_t* ranges2, uint32_t* outOffsets,

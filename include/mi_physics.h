@@ -428,7 +428,7 @@ MI_API int mi_debug_overlap_exhaustive(mi_world* world, uint32_t count, const mi
  *     colliders': a terrain hit does not shorten the collider pass.  Heightmaps of more than 256 chunks per dimension return
  *     MI_ERR_UNSUPPORTED when the terrain is asked for.
  *   - Not hit: cloth.  Also out of scope: rotation during the sweep, all-hits and any-hit variants, and the terrain in mi_world_overlap
- *     and mi_world_volume_contacts.
+ *     and mi_world_volume_contacts.  The distance of a volume from the terrain (ground clearance) comes from mi_world_terrain_distance.
  *   - Result: one record per cast, out[count].
  */
 typedef struct mi_sweep_hit {   /* 48 bytes, 16-byte aligned rows: usable from the host and as a device buffer */
@@ -477,8 +477,9 @@ MI_API int mi_debug_sweep_exhaustive(mi_world* world, uint32_t count, const mi_q
  *   - The reported distance is never below the gap of the two world AABBs (the bound candidates are skipped by): it is the pair test's
  *     distance raised to that gap, which differs from it by roundings only.
  *   - Accuracy (float32, measured against a float64 reference): see INTEGRATION.md, section 6g.
- *   - Not reported: the terrain (MI_QUERY_TERRAIN is accepted and ignored, as by mi_world_overlap) and cloth.  Also out of scope: k-nearest
- *     and all-within variants.
+ *   - Not reported: the terrain (the MI_QUERY_TERRAIN bit changes nothing here; the distance to the heightmap comes from
+ *     mi_world_terrain_distance, below, which can merge into these records) and cloth.  Also out of scope: k-nearest and all-within
+ *     variants.
  *   - Result: one record per volume, out[count].
  */
 typedef struct mi_distance_hit {   /* 64 bytes, four 16-byte rows: usable from the host and as a device buffer */
@@ -504,6 +505,51 @@ MI_API int mi_world_distance_device_async(mi_world* world, uint32_t count, const
  * collider rows computed for the call (the yardstick of the accelerated path): byte for byte equal. */
 MI_API int mi_debug_distance_exhaustive(mi_world* world, uint32_t count, const mi_query_volume* volumes, const float* max_distances,
                                         uint32_t include, const uint32_t* entity_ranges2, mi_distance_hit* out);
+
+/*
+ * Batched terrain distance queries: how far is a shape from the heightmap terrain, and which two points realise that distance (ground
+ * clearance of a foot capsule, a wheel hull or a chassis box over rolling ground; the nearest terrain point for steering and placement).
+ * The terrain's own entry point beside mi_world_distance, as mi_world_terrain_contacts stands beside mi_world_volume_contacts; the
+ * volumes, their validation (mi_world_overlap's) and their pose handling are those of mi_world_distance, the record is mi_distance_hit.
+ * There are no include flags and no entity ranges.  Read-only for the step.  A sharded world returns MI_ERR_UNSUPPORTED.
+ *   - The terrain is what the ray cast and the shape cast hit: the heightmap's collision triangles, two per cell, (A, B, C) and
+ *     (C, B, D): two-sided surfaces with no volume below them; chunks without heights are holes.  A volume wholly below the surface has a
+ *     positive distance and a normal that points down.  Unlike a cast, a volume beside the map still has a nearest triangle, on the rim:
+ *     this is a distance, not an intersection.
+ *   - Reported for volume v: the triangle with the smallest distance, if that distance is <= max_distance_v, as entity = collider =
+ *     MI_RAY_TERRAIN and object_type = MI_OBJECT_STATIC_COLLIDER; otherwise a miss of mi_world_distance's shape.  max_distances NULL =
+ *     +inf for every volume; a negative or NaN max_distance is a miss.  point_collider lies on the triangle, point_volume on the volume,
+ *     normal = normalize(point_volume - point_collider).  Spheres and capsules stay a point or segment core plus a radius.  Among
+ *     triangles at equal distance the lowest (gz * n + gx) * 2 + tri wins (cell (gx, gz) of the whole map, n = chunks per dimension x
+ *     128), the casts' rule; which of two neighbours that share the closest edge or vertex is meant is not observable in the record.
+ *   - A volume that touches a triangle: distance = 0, MI_DISTANCE_OVERLAP, both points the pose position, normal 0.  The decision is the
+ *     shape cast's for an initial overlap.  MI_DISTANCE_UNCONVERGED means what it means for colliders: too far, never too near.
+ *   - The reported distance is the pair test's raised to the gap of the volume's AABB and the triangle's (roundings only): the bound by
+ *     which cells, 8 x 8 blocks and chunks are skipped through the height mips, strictly, so the accelerated walk and the exhaustive
+ *     yardstick agree byte for byte.
+ *   - An invalid volume is a miss when merge == 0 and is left untouched when merge != 0.
+ *   - merge != 0: out holds the records of a mi_world_distance call for the same volumes (the blocking call reads and writes out).  A
+ *     record is replaced only when it is a miss or the terrain is strictly nearer: a collider wins a tie, as in the casts.  The
+ *     existing distance also bounds the search.  Every record that is not replaced keeps its bytes.  Two enqueues thus give "the
+ *     nearest of anything" without host work.
+ *   - A world without a heightmap returns MI_OK: misses when merge == 0, nothing written when merge != 0.  A heightmap of more than 256
+ *     chunks per dimension returns MI_ERR_UNSUPPORTED (the casts' limit).
+ *   - The heightmap buffers are read as the casts read them: mi_heightmap_set_chunk_heights and mi_heightmap_update are followed by
+ *     the next query.
+ *   - Accuracy (float32, measured against a float64 reference): see INTEGRATION.md, section 6h.
+ *   - Result: one record per volume, out[count].
+ */
+MI_API int mi_world_terrain_distance(mi_world* world, uint32_t count, const mi_query_volume* volumes, const float* max_distances,
+                                     uint32_t merge, mi_distance_hit* out);
+/* Device buffers (16-byte aligned records and volumes), only enqueued on the world's stream: no reservation and no host synchronisation.
+ * max_distances_dev (one float per volume) may be NULL.  With merge != 0 out_dev is read and written: enqueue it behind
+ * mi_world_distance_device_async on the same buffers. */
+MI_API int mi_world_terrain_distance_device_async(mi_world* world, uint32_t count, const mi_query_volume* volumes_dev,
+                                                  const float* max_distances_dev, uint32_t merge, mi_distance_hit* out_dev);
+/* The same result from every triangle of every chunk that has heights, without the height mips and without skipping by the best distance
+ * so far (the yardstick of the accelerated path): byte for byte equal. */
+MI_API int mi_debug_terrain_distance_exhaustive(mi_world* world, uint32_t count, const mi_query_volume* volumes, const float* max_distances,
+                                                uint32_t merge, mi_distance_hit* out);
 
 /*
  * Batched contact-manifold queries: where a shape touches the world, along which normal and how deep (what PhysX calls

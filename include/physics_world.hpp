@@ -196,6 +196,32 @@ public:
         v.shape[0] = center.x; v.shape[1] = center.y; v.shape[2] = center.z; v.shape[3] = radius;
         return distance(std::vector<mi_query_volume>{v}, std::vector<float>{maxDistance}, include)[0];
     }
+    // The heightmap triangle nearest to each volume (mi_world_terrain_distance): ground clearance.  One record per volume with entity = collider = MI_RAY_TERRAIN,
+    // the distance, the closest points on the terrain and on the volume and the unit direction from the terrain towards the volume (it points down for a volume
+    // below the surface); entity MI_RAY_MISS when the terrain lies beyond the volume's maximum distance or the world has no heightmap; a volume that touches a
+    // triangle reports distance 0 with MI_DISTANCE_OVERLAP; read-only.  maxDistances: empty = unbounded, otherwise one per volume.
+    // distanceWithTerrain: the nearest of anything — mi_world_distance, then the terrain merged into its records (a collider wins a tie).
+    std::vector<mi_distance_hit> terrainDistance(const std::vector<mi_query_volume>& volumes, const std::vector<float>& maxDistances = {}) {
+        if (!maxDistances.empty() && maxDistances.size() != volumes.size()) throw std::invalid_argument("terrainDistance: one maximum distance per volume");
+        std::vector<mi_distance_hit> out(volumes.size());
+        if (!volumes.empty())
+            check(mi_world_terrain_distance(w_, (uint32_t)volumes.size(), volumes.data(), maxDistances.empty() ? nullptr : maxDistances.data(), 0u, out.data()),
+                  "mi_world_terrain_distance");
+        return out;
+    }
+    mi_distance_hit terrainClearanceOfSphere(vec3 center, float radius, float maxDistance = std::numeric_limits<float>::infinity()) {
+        mi_query_volume v{}; v.type = MI_COLLIDER_SPHERE; v.rotation[3] = 1.f;
+        v.shape[0] = center.x; v.shape[1] = center.y; v.shape[2] = center.z; v.shape[3] = radius;
+        return terrainDistance(std::vector<mi_query_volume>{v}, std::vector<float>{maxDistance})[0];
+    }
+    std::vector<mi_distance_hit> distanceWithTerrain(const std::vector<mi_query_volume>& volumes, const std::vector<float>& maxDistances = {}, uint32_t include = MI_QUERY_DEFAULT,
+                                                     const std::vector<uint32_t>& entityRanges = {}) {
+        std::vector<mi_distance_hit> out = distance(volumes, maxDistances, include, entityRanges);
+        if (!volumes.empty())
+            check(mi_world_terrain_distance(w_, (uint32_t)volumes.size(), volumes.data(), maxDistances.empty() ? nullptr : maxDistances.data(), 1u, out.data()),
+                  "mi_world_terrain_distance");
+        return out;
+    }
     // Where each volume touches the world (mi_world_volume_contacts): CSR offsets [volumes + 1] and one manifold per (volume, collider) in ascending
     // collider index; normal from A to B, bit 8 of count_flags set when the volume was B (include/mi_physics.h); read-only.
     struct volume_contacts_result { std::vector<uint32_t> offsets; std::vector<mi_volume_contact> contacts; };
